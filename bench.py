@@ -23,6 +23,15 @@ torch.distributed.run, one rank per GPU.  One JSON line on rank 0.
              (10 x sum n_k^3 flop against 78.6 TFLOP/s), which is what actually bounds the kernel, rides beside it under "mfma".
   * cpu_baseline: the C++/OpenMP port of the same ADMM iteration (oracle/c, LAPACK dsyevd per clique) timed on the host
              cores for a bounded sample, plus its estimated time to the certificates the GPU solves reached.
+
+A plain run sets up, burns in, warms up, times the K steps and prints the line (`value`, `ms_per_step`, `roofline` from the
+same window).  Everything else - the replica leg of N > 1, hipGraph replay, the late window, the round-1 window, time to
+certificate, the batched leg, the wide-block leg, the hipIpc leg and the CPU baseline - runs only with `--full`.
+
+`--dump-outputs DIR` writes, after the timed steps, what a caller of the timed path receives as float64 .npy files:
+nu_multipliers (the solver's multiplier block right after the last timed step), residuals ([pres, dres, pobj, dobj] of the
+check iteration that follows), and from nnsdp_solver_finish objective, gamma_in, gamma_out, gamma_ac1, gamma_ac2 and Z.
+The inputs are the committed fixture, so two builds run with the same arguments can be compared file by file.
 """
 import argparse
 import json
@@ -115,6 +124,23 @@ def cpu_baseline(workload: str, beta: int, seconds: float, gpu_iters_to_cert=Non
     return out
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(dirname: str, arrays: dict) -> None:
+    """Each array as DIR/<name>.npy in float64.  Every array gets an equal share of the 64 MB budget; one larger than its share is
+    replaced by a fixed, seeded sample of its flattened entries (DIR/<name>.npy) beside their flat indices (DIR/<name>_index.npy)."""
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(len(arrays), 1) - 4096       # (less room for the .npy headers)
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float64)
+        if a.size * 8 > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // 16, replace=False))
+            np.save(os.path.join(dirname, f"{name}_index.npy"), idx.astype(np.float64))
+            a = a.ravel()[idx]
+        np.save(os.path.join(dirname, f"{name}.npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -139,6 +165,11 @@ def main():
     ap.add_argument("--no-torch", action="store_true",
                     help="N = 1 only: do not import torch (device synchronisation through the HIP runtime directly); a diagnostic that separated "
                          "torch from the library when rocprofv3 --pmc died at start-up (the cause was neither: the load order, see below)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the headline figure (replicas, graph replay, late and round-1 windows, time to "
+                         "certificate, batched, wide blocks, hipIpc, CPU baseline); the options above that size those legs apply only here")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the timed path's outputs after its last step to DIR/<name>.npy (float64)")
     args = ap.parse_args()
 
     if os.environ.get("NNSDP_BENCH_WATCHDOG"):      # (diagnostic) Python stack of every thread after that many seconds, then exit: where does a run hang?
@@ -216,7 +247,7 @@ def main():
     transport = None
     shard_error = None
     replicas = None
-    if world > 1:
+    if args.full and world > 1:
         # replica leg: one independent SDP per GPU, no data-path collective
         rs = na.Solver(q, opts)
         dt_r, _ = timed_leg(rs)
@@ -254,23 +285,26 @@ def main():
             else:
                 transport = "hipIpc"
     dt, eig_ms = timed_leg(solver)
+    nu_last = solver.raw_multipliers() if args.dump_outputs else None     # (a copy of the state; runs no iteration)
     pres, dres, pobj, dobj = solver.residuals()
     soln = solver.finish()
     sm = soln.summary
 
-    # hipGraph replay rate of the same iteration (what nnsdp_solve itself uses): the graph is captured and instantiated by an untimed
-    # call first, and at least 256 iterations are timed whatever --steps is (a 20-step window used to contain the capture)
-    solver.iterate(64)                  # every rank runs these too (sharded mode: collective inside)
-    dev_sync()
-    g_steps = max(args.steps, 2048)
-    tg0 = time.perf_counter()
-    solver.iterate(g_steps)
-    dev_sync()
-    graph_ips = g_steps / (time.perf_counter() - tg0)
+    graph_ips = g_steps = None
+    if args.full:
+        # hipGraph replay rate of the same iteration (what nnsdp_solve itself uses): the graph is captured and instantiated by an untimed
+        # call first, and at least 256 iterations are timed whatever --steps is (a 20-step window used to contain the capture)
+        solver.iterate(64)                  # every rank runs these too (sharded mode: collective inside)
+        dev_sync()
+        g_steps = max(args.steps, 2048)
+        tg0 = time.perf_counter()
+        solver.iterate(g_steps)
+        dev_sync()
+        graph_ips = g_steps / (time.perf_counter() - tg0)
     # the same measurement deep in the solve: a solve to residuals 1e-6 takes 59 000 iterations in this decomposition, and from about
     # 10 000 on the projection kernel's refinement stage carries nearly every block (the sweeps are the early-phase path)
     late = None
-    if args.late_burn_in > 0 and world == 1:
+    if args.full and args.late_burn_in > 0 and world == 1:
         solver.advance(args.late_burn_in)
         solver.iterate(args.warmup, time_eig=True)
         dev_sync()
@@ -288,7 +322,7 @@ def main():
     solver.close()
 
     ipc_leg = None
-    if shard and world > 1 and transport == "rccl":
+    if args.full and shard and world > 1 and transport == "rccl":
         # the same clique-sharded SDP over the library's own device-side transport (hipIpc-mapped peer buffers: one-shot all-gather +
         # local reduce in rank order, no library collective in the iteration) - reported beside the RCCL figure, never instead of it
         import torch as _t
@@ -367,18 +401,20 @@ def main():
                                   "algorithmic_flops_per_launch": flops,
                                   "note": "what bounds the kernel: one SDP's 19 blocks occupy 19 of 256 CUs and live on those CUs' fp64 matrix pipes (DESIGN.md section 4)"}},
             "eig_share_of_step": eig_avg_s / (dt / args.steps), "avg_jacobi_sweeps": sm["avg_sweeps"],
-            "graph_replay": {"value": graph_ips, "unit": "ADMM iters/s", "steps": g_steps, "ms_per_step": 1e3 / graph_ips,
-                             "note": "the mode nnsdp_solve itself runs in (7 iterations per hipGraph replay + the check iteration as a graph of its own, no per-launch events); `value` above is the eager rate with HIP events around every projection launch"},
-            "graph_replay_iters_per_s": graph_ips, "graph_replay_steps_timed": g_steps,
             "refine_blocks_until_window": sm.get("refine_blocks"),
             "iterate": {"pres": pres, "dres": dres, "objective": pobj, "dual_objective": dobj},
         }
+        if graph_ips is not None:
+            out.update({
+                "graph_replay": {"value": graph_ips, "unit": "ADMM iters/s", "steps": g_steps, "ms_per_step": 1e3 / graph_ips,
+                                 "note": "the mode nnsdp_solve itself runs in (7 iterations per hipGraph replay + the check iteration as a graph of its own, no per-launch events); `value` above is the eager rate with HIP events around every projection launch"},
+                "graph_replay_iters_per_s": graph_ips, "graph_replay_steps_timed": g_steps})
         if late:
             fl = flops / (late["kernel_avg_us"] * 1e-6) / 1e12
             late.update(roofline_frac=byts_basis / (late["kernel_avg_us"] * 1e-6) / 1e9 / HBM_PEAK_GBS, mfma_frac=fl / FP64_PEAK_TFLOPS, achieved_TFLOPs=fl,
                         note="second timed window of the same handle, same K steps and per-launch events; `value` and `roofline` above are the first window")
             out["late_window"] = late
-    if rank == 0 and world == 1 and not shard:
+    if args.full and rank == 0 and world == 1 and not shard:
         # round 1's default window (5 warmup + 20 timed iterations of a FRESH solver, no burn-in), kept for a like-for-like
         # comparison with BENCH_r01.json: the first iterations of a solve are not the regime it spends its time in
         s0 = na.Solver(q, opts)
@@ -392,7 +428,7 @@ def main():
         out["round1_window"] = {"warmup": 5, "steps": 20, "burn_in_iters": 0, "iters_per_s": 20 / dt0, "kernel_avg_us": 1e3 * ms0 / 20,
                                 "note": "the window BENCH_r01.json used; same-box comparison of the two trees: profiles/r02_vs_r01_same_box.log "
                                         "(round-1 tree 4 974 it/s / 161.0 us, this tree 5 421 it/s / 152.3 us in this window)"}
-    if rank == 0 and world == 1 and args.cert_seconds > 0 and not shard:
+    if args.full and rank == 0 and world == 1 and args.cert_seconds > 0 and not shard:
         # wall-clock to certificate on fresh solves (setup + ADMM to eps_rel = 1e-6 + feasibility polish)
         out["time_to_cert"] = {}
         for mode in (na.SingleDecomp(), na.DoubleDecomp(), na.PathDecomp()):   # Single / Double: chordal_sdp.jl:8-9; Path: finer cliques, an extension
@@ -424,7 +460,7 @@ def main():
                                       "certified_gap_1e-3: stop as soon as the polished (exactly feasible) objective is within 1e-3 of the "
                                       "ADMM primal/dual estimates. rho = objective of the polished point; lambda_max = eigmax(Z(gamma)) "
                                       "in the reference's coordinates (reference acceptance: 1e-6 .. 1e-4)")
-    if rank == 0 and world == 1 and args.batch > 1 and not shard:
+    if args.full and rank == 0 and world == 1 and args.batch > 1 and not shard:
         # the same kernels with `batch` independent SDPs in lockstep on one GPU: batch handle (one launch per stage for
         # all SDPs), and for comparison the older form with one HIP stream + hipGraph per SDP
         sb = na.SolverBatch([q] * args.batch, opts)
@@ -445,7 +481,7 @@ def main():
                           "eig_frac_of_fp64_peak_if_same_share": agg * float(sm["eig_flops_per_iter"]) / 1e12 / FP64_PEAK_TFLOPS,
                           "note": "independent SDPs (beta sweep of experiments/scale.jl:28, hyperplanes of findReach2Dpoly, ACAS sub-queries) in lockstep on one GPU, "
                                   "nnsdp_batch_*: one launch per stage for all SDPs, hipGraph replay; 13 x 19 blocks = 247 of the 256 CUs"}
-    if rank == 0 and world == 1 and args.wide_burn_in > 0 and not shard:
+    if args.full and rank == 0 and world == 1 and args.wide_burn_in > 0 and not shard:
         # BASELINE config 5's shape on ONE GPU: an ACAS-Xu shaped network (5-50x6-5, random weights), reach-hyperplane query, plain interval
         # arithmetic (no neuron stable), the reference's Single cliques = 106 + 4 x 151: the packed-triangle variant of the projection kernel
         from nnsdp_amd import frontend as F
@@ -482,13 +518,19 @@ def main():
                 out["wide_blocks"][label] = {"wall_s": time.perf_counter() - t2, "solve_s": s3.solve_time, "status": s3.termination_status, "iters": s3.summary["iters"],
                                              "bound": s3.objective_value, "blocks": s3.summary["n_cliques"], "max_block": s3.summary["max_clique"],
                                              "lambda_max": s3.summary["lambda_max"], "us_per_iter": 1e6 * s3.solve_time / max(s3.summary["iters"], 1)}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         need = None
         if "time_to_cert" in out:
             need = {k.split("/")[1]: v["iters"] for k, v in out["time_to_cert"].items() if isinstance(v, dict) and k.startswith("DoubleDecomp/")}
         out["cpu_baseline"] = cpu_baseline(args.workload, args.beta, args.cpu_seconds, need)
     elif rank == 0:
         out["cpu_baseline"] = None
+    if rank == 0 and args.dump_outputs:
+        vals = soln.values
+        dump_outputs(args.dump_outputs, {
+            "nu_multipliers": nu_last, "residuals": [pres, dres, pobj, dobj], "objective": [soln.objective_value],
+            "gamma_in": vals["γin"], "gamma_out": vals.get("γout", np.zeros(0)), "gamma_ac1": vals["γac1"], "gamma_ac2": vals["γac2"],
+            "Z": vals["Z"]})
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()

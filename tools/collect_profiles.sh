@@ -13,7 +13,7 @@ export TMPDIR=/tmp
 export DEBUG_CLR_GRAPH_PACKET_CAPTURE=0
 cd /tmp
 BURN=2000; WARM=50; STEPS=200; LATE=18000
-ARGS="--steps $STEPS --warmup $WARM --burn-in $BURN --late-burn-in $LATE --batch 0 --no-cpu-baseline --cert-seconds 0 --wide-burn-in 0"
+ARGS="--full --steps $STEPS --warmup $WARM --burn-in $BURN --late-burn-in $LATE --batch 0 --no-cpu-baseline --cert-seconds 0 --wide-burn-in 0"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $R/bench.py $ARGS > $OUT/${TAG}_bench_under_rocprof.json 2> $OUT/stats.err
 # Counter passes (round 4): rocprofv3 --pmc segfaults in one of its own threads when bench.py itself is the profiled process (5 of 5
 # runs with these arguments, torch or not, set-up thread or not, graph packet capture on or off: tools/pmc_probe.sh; the first cause
