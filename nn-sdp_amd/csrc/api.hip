@@ -93,25 +93,48 @@ static void require_gpu() {
 
 static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
-// projection kernel variant for a launch whose largest block is nmax.  Default: ping-pong odd-even sweeps for
-// 41..96, register-resident systolic sweeps for 97..128, LDS round robin for small blocks.
-// Diagnostic overrides: NNSDP_PROJ_ALG=0/1/2/3, NNSDP_BLOCK=1.
-// warm_refine: the launches are a solver's warm iterations with the refinement stage on.  Blocks 97 .. 128 then take the packed variant as
-// well: its stage carries most of a solve (width-50 networks in the Path decomposition, 101-wide blocks: 565 -> 347 us per iteration,
-// tools/width50_variants.py), while the systolic variant - faster sweeps, no stage - stays the choice for cold one-off projections.
-static int proj_algorithm(int nmax, bool warm_refine = false) {
-  if (nnsdp::proj_packed_ok(nmax)) return nnsdp::kProjPacked;      // 129 .. 160: packed lower triangle in LDS (the only variant that fits)
-  if (warm_refine && nmax > 96 && nmax <= 128 && !std::getenv("NNSDP_PROJ_ALG")) return nnsdp::kProjPacked;
-  int alg = nnsdp::proj_pp_ok(nmax) ? nnsdp::kProjPingPong : (nnsdp::proj_sys_ok(nmax) ? nnsdp::kProjSystolic : nnsdp::kProjRoundRobin);
-  if (const char* e = std::getenv("NNSDP_PROJ_ALG")) alg = std::atoi(e);
-  if (alg == nnsdp::kProjPacked && nmax > 96 && nmax <= nnsdp::kMaxLdsBlock) return alg;      // (diagnostic: the packed variant for 97 .. 128 as well)
-  if (const char* e = std::getenv("NNSDP_BLOCK")) { if (std::atoi(e) != 0) alg = nnsdp::kProjBlock; }
-  if (alg == nnsdp::kProjSystolic && !nnsdp::proj_sys_ok(nmax)) alg = nnsdp::kProjRoundRobin;
-  if (alg == nnsdp::kProjBlock && !nnsdp::proj_block_ok(nmax)) alg = nnsdp::kProjRoundRobin;
-  if (alg == nnsdp::kProjPingPong && !nnsdp::proj_pp_ok(nmax)) alg = nnsdp::kProjRoundRobin;
-  if (alg < 0 || alg > 3) alg = nnsdp::kProjRoundRobin;
-  return alg;
-}
+// tuning of the projection kernel's refinement stage (ProjArgs::refine_*, gram_credit), with the diagnostic environment overrides applied:
+// read once per solver and once per warm test-entry call
+struct RefineTuning {
+  double acc = 30.0, kcap = 0.05, loose = 1.0;
+  // |K|_F^2 above which the refinement step is not taken (NNSDP_REFINE_KMAX overrides |K|_F).  Round 3 had 0.09 (|K|_F <= 0.3, from the
+  // Frobenius bound |K|^4 / 4 on the defect of I + K + K^2 / 2); that bound is 50x pessimistic on these blocks (a step with |K|_F = 0.28
+  // leaves |I - V'V|_F = 2.7e-5), the 151-wide blocks of width-50 networks sit at |K|_F = 0.35 .. 0.45 with a predicted error INSIDE the
+  // accepted level for thousands of iterations, and one such block in back-off makes every launch a sweep launch: 0.64 takes the
+  // ACAS-shaped Single solve from 13.3 to 8.3 s (28.0 -> 15.1 s on bench.py's network) and leaves W40-D20 unchanged; the measured
+  // defect (Gram visits, forced by the estimate) and the r2 <= 1e-4 guard stay in charge of orthogonality.
+  double k2cap = 0.64;
+  int pivots = 2, gram_credit = 3;
+  static RefineTuning from_env() {
+    RefineTuning t;
+    if (const char* e = std::getenv("NNSDP_REFINE_ACC")) t.acc = std::atof(e);
+    if (const char* e = std::getenv("NNSDP_REFINE_KCAP")) t.kcap = std::atof(e);
+    if (const char* e = std::getenv("NNSDP_REFINE_LOOSE")) t.loose = std::atof(e);
+    if (const char* e = std::getenv("NNSDP_REFINE_KMAX")) t.k2cap = std::atof(e) * std::atof(e);
+    if (const char* e = std::getenv("NNSDP_REFINE_PIVOTS")) t.pivots = std::atoi(e);
+    if (const char* e = std::getenv("NNSDP_GRAM_EVERY")) t.gram_credit = std::min(std::max(std::atoi(e) - 1, 0), 15);
+    return t;
+  }
+  void bind(ProjArgs& a) const {
+    a.refine_acc = acc; a.refine_kcap = kcap; a.refine_loose = loose; a.refine_k2cap = k2cap; a.refine_pivots = pivots; a.gram_credit = gram_credit;
+  }
+};
+
+// scratch of two workgroups per block for the warm-start congruence (ProjArgs::split): helper tiles, hand-over counters, error flag
+struct SplitScratch {
+  DBuf<double> B;
+  DBuf<unsigned> ack, seen, xcc;
+  DBuf<int> err;
+  bool on() const { return B.p != nullptr; }
+  void alloc(int nblk) {
+    B.alloc((size_t)nblk * kSplitTileDoubles);
+    ack.alloc(nblk); ack.zero(); seen.alloc(nblk); seen.zero(); xcc.alloc(nblk); xcc.zero(); err.alloc(1); err.zero();
+  }
+  void bind(ProjArgs& a, int nblk) const {
+    a.split = 1; a.nblk = nblk; a.sB = B.p; a.sack = ack.p; a.sseen = seen.p; a.sxcc = xcc.p; a.serr = err.p; a.spin_limit = 20000000;
+  }
+  bool failed() const { return on() && err.download()[0] != 0; }
+};
 
 // device-resident operator (CSR + CSC + pattern)
 struct DevOperator {
@@ -327,23 +350,13 @@ struct nnsdp_solver {
   DBuf<rocblas_int> big_info;
   DBuf<int> big_flag;                   // sticky: some library eigensolve of this process reported info != 0 (k_sticky_info)
   int big_flag_host = 0;
-  bool v_lds = true;
-  int proj_alg = 0;
-  size_t lds_bytes = 0;
+  nnsdp::ProjPlan plan;                // projection kernel of the blocks up to kMaxLdsBlock
   int ldm = 0;
   // device state
   DBuf<int> d_cn, d_sptr, d_stats, d_long, d_rstate, d_medrows, d_medsrc, d_colcls;
   int ncs = 0;                            // multipliers whose column of A holds at most kShortCol nonzeros (listed first in d_colcls)
   int nmed = 0, nmsrc = 0, nnz_A = 0;     // rows of A with 3 .. kLongRow nonzeros / pattern entries with more than two sources (16 lanes each)
-  double refine_acc = 30.0, refine_kcap = 0.05, refine_loose = 1.0;
-  // |K|_F^2 above which the refinement step is not taken (NNSDP_REFINE_KMAX overrides |K|_F).  Round 3 had 0.09 (|K|_F <= 0.3, from the
-  // Frobenius bound |K|^4 / 4 on the defect of I + K + K^2 / 2); that bound is 50x pessimistic on these blocks (a step with |K|_F = 0.28
-  // leaves |I - V'V|_F = 2.7e-5), the 151-wide blocks of width-50 networks sit at |K|_F = 0.35 .. 0.45 with a predicted error INSIDE the
-  // accepted level for thousands of iterations, and one such block in back-off makes every launch a sweep launch: 0.64 takes the
-  // ACAS-shaped Single solve from 13.3 to 8.3 s (28.0 -> 15.1 s on bench.py's network) and leaves W40-D20 unchanged; the measured
-  // defect (Gram visits, forced by the estimate) and the r2 <= 1e-4 guard stay in charge of orthogonality.
-  double refine_k2cap = 0.64;
-  int refine_pivots = 2, gram_credit = 3;
+  RefineTuning tune;
   int nlong = 0;
   DBuf<long long> d_coff, d_soff;
   DBuf<unsigned char> d_isdiag;
@@ -411,11 +424,7 @@ struct nnsdp_solver {
   nnsdp::IpcArgs ipa{};
   std::vector<void*> ipc_opened;
   bool ipc_fine = false;               // exchange buffers in fine-grained device memory
-  // two workgroups per block for the warm-start congruence (ProjArgs::split): ping-pong variant, one SDP, no compacted block list
-  DBuf<double> split_B;
-  DBuf<unsigned> split_ack, split_seen, split_xcc;
-  DBuf<int> split_err;
-  bool split_on = false;
+  SplitScratch split;                   // two workgroups per block (ProjArgs::split): ping-pong variant, one SDP, no compacted block list
 
   ~nnsdp_solver() {
     if (comm) (void)Rccl::get().CommDestroy(comm);
@@ -511,9 +520,8 @@ struct nnsdp_solver {
     }
     const int nsm = std::max(nmax_small, 1);
     if (const char* e = std::getenv("NNSDP_REFINE")) opt.proj_refine = std::atoi(e);                   // (diagnostic override, read before the variant is chosen)
-    proj_alg = proj_algorithm(nsm, opt.proj_refine != 0);
-    v_lds = proj_alg != nnsdp::kProjPacked && proj_lds_bytes(nsm, true, proj_alg) <= 160 * 1024;
-    lds_bytes = proj_lds_bytes(nsm, v_lds, proj_alg);
+    tune = RefineTuning::from_env();
+    plan = nnsdp::plan_projection(nsm, opt.proj_refine != 0);
     {
       // two workgroups per block for the warm-start congruence (ProjArgs::split): only where the second workgroup finds a free CU (one
       // SDP's blocks; the batch handle fills the chip already and keeps the one-workgroup form) and where it pays (a block above 80:
@@ -525,11 +533,7 @@ struct nnsdp_solver {
       // faster per launch (56.8 against 59.9 us, W40-D20 76.5 against 78.1 us per step; profiles/r04_split_probe.log)
       int want = nsm > 80 ? 1 : 0;
       if (const char* e = std::getenv("NNSDP_SPLIT")) want = std::atoi(e);                              // (diagnostic override)
-      split_on = want != 0 && proj_alg == nnsdp::kProjPingPong && v_lds && big_idx.empty() && ncl <= 120;
-      if (split_on) {
-        split_B.alloc((size_t)ncl * nnsdp::kSplitTileDoubles);
-        split_ack.alloc(ncl); split_ack.zero(); split_seen.alloc(ncl); split_seen.zero(); split_xcc.alloc(ncl); split_xcc.zero(); split_err.alloc(1); split_err.zero();
-      }
+      if (want != 0 && plan.split_ok() && big_idx.empty() && ncl <= 120) split.alloc(ncl);
     }
     // gather sources: entry e <- (clique k, lower element (i,j))
     std::vector<int> sptr(S.NE + 1, 0);
@@ -571,13 +575,6 @@ struct nnsdp_solver {
     giters = graph_iters_for(opt.check_every);
     if (const char* e = std::getenv("NNSDP_PIPE")) pipe_mode = std::atoi(e);                             // (diagnostic override)
     d_rstate.alloc(4 * (size_t)std::max(ncl, 1)); d_rstate.zero();      // (4 ints per block: kernels.hip, ProjArgs::rstate)
-    if (const char* e = std::getenv("NNSDP_REFINE")) opt.proj_refine = std::atoi(e);                   // diagnostic overrides
-    if (const char* e = std::getenv("NNSDP_REFINE_ACC")) refine_acc = std::atof(e);
-    if (const char* e = std::getenv("NNSDP_REFINE_KCAP")) refine_kcap = std::atof(e);
-    if (const char* e = std::getenv("NNSDP_REFINE_LOOSE")) refine_loose = std::atof(e);
-    if (const char* e = std::getenv("NNSDP_REFINE_KMAX")) refine_k2cap = std::atof(e) * std::atof(e);
-    if (const char* e = std::getenv("NNSDP_REFINE_PIVOTS")) refine_pivots = std::atoi(e);
-    if (const char* e = std::getenv("NNSDP_GRAM_EVERY")) gram_credit = std::min(std::max(std::atoi(e) - 1, 0), 15);
     {
       std::vector<int> lr;
       for (int e = 0; e < S.NE; ++e)
@@ -638,7 +635,7 @@ struct nnsdp_solver {
     }
     // iteration state
     nu.alloc(ng + nmat); w.alloc(ng + nmat); Vg.alloc(nmat);
-    if (proj_alg == nnsdp::kProjPacked) { Tg.alloc(nmat); Tg.zero(); Ug.alloc(nmat); Ug.zero(); }      // scratch of the packed variant (warm start, rotation log; new basis of its refinement stage)
+    if (plan.packed()) { Tg.alloc(nmat); Tg.zero(); Ug.alloc(nmat); Ug.zero(); }      // scratch of the packed variant (warm start, rotation log; new basis of its refinement stage)
     x.alloc(S.NE); g.alloc(S.NE); p.alloc(ng); qv.alloc(ldm); ww.alloc(ng); gs.alloc(ng);
     scal.alloc(4); acc.alloc(8 + (size_t)ng); acc.zero();
     nb_upd = cdiv(ng + nmat, kThreads);
@@ -657,7 +654,7 @@ struct nnsdp_solver {
     if (const char* e = std::getenv("NNSDP_PROJ_TOL_CAP")) { if (!(opt.proj_tol > 0)) proj_tol = std::atof(e); }
     double sc[4] = {sigma, 1.0, proj_tol, 0.0};
     HIPCHK(hipMemcpy(scal.p, sc, sizeof(sc), hipMemcpyHostToDevice));
-    if (lds_bytes > 64 * 1024) HIPCHK(proj_allow_big_lds());
+    HIPCHK(proj_allow_big_lds(plan));
     k0 = 0; k1 = ncl;
     build_pipe();
     lap("state buffers");
@@ -959,7 +956,7 @@ struct nnsdp_solver {
     pipe.release();
     pipe_on = false;
     if (pipe_mode == 0 || opt.proj_refine != 1 || opt.warm_start == 0) return;
-    if (proj_alg != nnsdp::kProjPingPong && proj_alg != nnsdp::kProjPacked) return;      // (the variants whose kernel has the stage: 41 .. 160)
+    if (!plan.has_refine_stage()) return;
     std::vector<int> lst;
     if (big_idx.empty()) lst.assign(cn.begin() + k0, cn.begin() + k1);
     else for (int k : proj_small) lst.push_back(cn[k]);
@@ -976,22 +973,21 @@ struct nnsdp_solver {
     a.warm = warm ? 1 : 0;
     a.max_sweeps = 15;
     a.tol = kProjTol;
-    a.refine = opt.proj_refine; a.rstate = d_rstate.p + 4 * k0; a.refine_acc = refine_acc; a.refine_kcap = refine_kcap; a.refine_loose = refine_loose; a.refine_k2cap = refine_k2cap; a.refine_pivots = refine_pivots; a.gram_credit = gram_credit;
+    a.refine = opt.proj_refine; a.rstate = d_rstate.p + 4 * k0;
+    tune.bind(a);
     const bool use_pipe = warm && pipe_on && pipe.ready;
-    if (split_on && warm && big_idx.empty()) {
-      a.split = 1; a.nblk = k1 - k0; a.sB = split_B.p; a.sack = split_ack.p; a.sseen = split_seen.p; a.sxcc = split_xcc.p; a.serr = split_err.p; a.spin_limit = 20000000;
-    }
+    if (split.on() && warm && big_idx.empty()) split.bind(a, k1 - k0);
     if (big_idx.empty()) {
       if (k1 > k0) {
         if (use_pipe) { pipe.launch(pipe.args(a), st); a.pmode = pipe.pmode; }
-        nnsdp::launch_proj(a, k1 - k0, nmax, v_lds, lds_bytes, st, proj_alg);
+        nnsdp::launch_proj(plan, a, k1 - k0, st);
       }
       return;
     }
     if (!proj_small.empty()) {
       a.cn = d_cn_s.p; a.coff = d_coff_s.p; a.rstate = d_rstate.p;      // (compacted block list: the first proj_small.size() slots)
       if (use_pipe) { pipe.launch(pipe.args(a), st); a.pmode = pipe.pmode; }
-      nnsdp::launch_proj(a, (int)proj_small.size(), nmax_small, v_lds, lds_bytes, st, proj_alg);
+      nnsdp::launch_proj(plan, a, (int)proj_small.size(), st);
     }
     enqueue_big_blocks(st);
     HIPCHK(hipGetLastError());
@@ -1190,7 +1186,7 @@ struct nnsdp_solver {
     // rocSOLVER's convergence report of the library eigensolves, sticky since the solver was created.  Clique-sharded: only a block's
     // owner runs dsyevd, so the flag rides in the all-reduced control block (acc[7] >= 1024) and all ranks leave the loop together;
     // a rank-local exit would strand the others in the next iteration's all-reduce.
-    if (split_on && split_err.download()[0] != 0) throw HipError("projection kernel, two workgroups per block: a helper workgroup did not deliver its tiles in time, or ran on another XCD than its leader");
+    if (split.failed()) throw HipError("projection kernel, two workgroups per block: a helper workgroup did not deliver its tiles in time, or ran on another XCD than its leader");
     if (ipc && ipc_err.download()[0] != 0) throw HipError("clique-sharded exchange over hipIpc: a peer did not publish its partial sum in time (rank stopped or not co-scheduled)");
     if (!big_idx.empty()) {
       if (sharded) big_fail = big_fail || acc_host[7] >= 1024.0;
@@ -1679,9 +1675,9 @@ struct nnsdp_batch {
   DBuf<IterArgs> d_it;
   DBuf<ProjArgs> d_pw, d_pc;           // warm / cold projection arguments
   DBuf<int2> d_map;
-  int nblocks = 0, nmax = 0, alg = 0;
-  bool v_lds = true, any_structured = false, any_big = false;
-  size_t lds = 0;
+  int nblocks = 0, nmax = 0;
+  bool any_structured = false, any_big = false;
+  ProjPlan plan;
   int gx_gather = 0, gx_gather_med = 0, gx_at_s = 0, gx_at_l = 0, gx_gemv = 0, gx_ax = 0, gx_ax_med = 0, gx_long = 0, gx_upd = 0, gx_tiles = 0, gx_nb = 0;
   hipGraph_t graph = nullptr;
   hipGraphExec_t gexec = nullptr;
@@ -1751,7 +1747,8 @@ struct nnsdp_batch {
       q.nu = s->nu.p + s->S.ng; q.w = s->w.p + s->S.ng; q.Vg = s->Vg.p; q.eig = nullptr; q.Tg = s->Tg.p; q.Ug = s->Ug.p;
       q.kappa = s->d_kappa(); q.tol_dev = s->scal.p + 2; q.stats = s->d_stats.p;
       q.max_sweeps = 15; q.tol = nnsdp_solver::kProjTol;
-      q.refine = s->opt.proj_refine; q.rstate = s->d_rstate.p; q.refine_acc = s->refine_acc; q.refine_kcap = s->refine_kcap; q.refine_loose = s->refine_loose; q.refine_k2cap = s->refine_k2cap; q.refine_pivots = s->refine_pivots; q.gram_credit = s->gram_credit;
+      q.refine = s->opt.proj_refine; q.rstate = s->d_rstate.p;
+      s->tune.bind(q);
       q.warm = 1; pw.push_back(q);
       q.warm = 0; pc.push_back(q);
       // blocks up to 128 of every SDP share ONE launch of the LDS-resident kernel; blocks above (the reference's 151-wide cliques of
@@ -1777,21 +1774,19 @@ struct nnsdp_batch {
     }
     nblocks = (int)map.size();
     nmax = std::max(nmax, 1);
-    alg = proj_algorithm(nmax, !act.empty() && act[0]->opt.proj_refine != 0);
-    if (alg == nnsdp::kProjPacked)          // one launch for all members in the packed variant: every member needs its warm-start scratch
+    plan = plan_projection(nmax, !act.empty() && act[0]->opt.proj_refine != 0);
+    if (plan.packed())          // one launch for all members in the packed variant: every member needs its warm-start scratch
       for (size_t b = 0; b < act.size(); ++b) {
         if (!act[b]->Tg.p) { act[b]->Tg.alloc(act[b]->nmat); act[b]->Tg.zero(); pw[b].Tg = pc[b].Tg = act[b]->Tg.p; }
         if (!act[b]->Ug.p) { act[b]->Ug.alloc(act[b]->nmat); act[b]->Ug.zero(); pw[b].Ug = pc[b].Ug = act[b]->Ug.p; }
       }
-    v_lds = proj_lds_bytes(nmax, true, alg) <= 160 * 1024;
-    lds = proj_lds_bytes(nmax, v_lds, alg);
-    if (lds > 64 * 1024) HIPCHK(proj_allow_big_lds());
+    HIPCHK(proj_allow_big_lds(plan));
     d_it.upload(it); d_pw.upload(pw); d_pc.upload(pc); d_map.upload(map);
   }
 
   void enqueue_iteration(bool warm) {
     const int B = (int)act.size();
-    if (nblocks > 0) launch_proj_batched(warm ? d_pw.p : d_pc.p, d_map.p, nblocks, nmax, v_lds, lds, st, alg);
+    if (nblocks > 0) launch_proj_batched(plan, warm ? d_pw.p : d_pc.p, d_map.p, nblocks, st);
     if (any_big) for (nnsdp_solver* s : act) s->enqueue_big_blocks(st);
     hipLaunchKernelGGL(k_gather_g_b, dim3(gx_gather + gx_gather_med, B), dim3(kThreads), 0, st, d_it.p, gx_gather);
     hipLaunchKernelGGL(k_spmv_At_b, dim3(std::max(gx_at_s + gx_at_l, 1), B), dim3(kThreads), 0, st, d_it.p, gx_at_s);
@@ -2238,13 +2233,11 @@ int nnsdp_project_psd_batched(int32_t batch, const int32_t* n, const double* mat
   dnu.alloc(tot); dw.alloc(tot); dV.alloc(tot); dE.alloc(etot);
   HIPCHK(hipMemcpy(dnu.p, mats, tot * sizeof(double), hipMemcpyHostToDevice));
   nmax = std::max(nmax, 1);
-  const int alg = proj_algorithm(nmax);
-  bool v_lds = proj_lds_bytes(nmax, true, alg) <= 160 * 1024;
-  size_t lds = proj_lds_bytes(nmax, v_lds, alg);
-  if (lds > 64 * 1024) HIPCHK(proj_allow_big_lds());
+  const ProjPlan plan = plan_projection(nmax);
+  HIPCHK(proj_allow_big_lds(plan));
   ProjArgs a{};
   DBuf<double> dT;
-  if (alg == nnsdp::kProjPacked) dT.alloc(tot);       // the packed variant's sweeps log their rotations there
+  if (plan.packed()) dT.alloc(tot);       // the packed variant's sweeps log their rotations there
   a.cn = dcn.p; a.coff = dco.p; a.eoff = deo.p; a.nu = dnu.p; a.w = dw.p; a.Vg = dV.p; a.eig = dE.p; a.Tg = dT.p;
   a.kappa = nullptr; a.tol_dev = nullptr; a.stats = nullptr; a.warm = 0; a.max_sweeps = 30; a.tol = 1e-13;
   a.refine = 0; a.rstate = nullptr; a.refine_acc = 0.0; a.refine_kcap = 0.0; a.refine_loose = 1.0; a.refine_k2cap = 0.09; a.refine_pivots = 0;
@@ -2261,7 +2254,7 @@ int nnsdp_project_psd_batched(int32_t batch, const int32_t* n, const double* mat
     }
     DBuf<int> dcs; DBuf<long long> dos, des;
     if (!big.empty() && !cs.empty()) { dcs.upload(cs); dos.upload(os); des.upload(es); a.cn = dcs.p; a.coff = dos.p; a.eoff = des.p; }
-    if (!cs.empty()) launch_proj(a, (int)cs.size(), nmax, v_lds, lds, nullptr, alg);
+    if (!cs.empty()) launch_proj(plan, a, (int)cs.size(), nullptr);
     if (!big.empty()) {
       RocHandle rh;
       RBCHK(rocblas_set_stream(rh.h, nullptr));
@@ -2331,26 +2324,18 @@ int nnsdp_project_psd_warm_state(int32_t batch, const int32_t* n, const double* 
   // behind it (refine = 1) takes the blocks the pipeline leaves
   const bool use_pipe = refine == 4;
   if (use_pipe) refine = 1;
-  const int alg = proj_algorithm(nmax, refine != 0);      // (97 .. 128 with the stage on: the packed variant, as in a solver's warm iterations)
-  bool v_lds = alg != nnsdp::kProjPacked && proj_lds_bytes(nmax, true, alg) <= 160 * 1024;
-  size_t lds = proj_lds_bytes(nmax, v_lds, alg);
-  if (lds > 64 * 1024) HIPCHK(proj_allow_big_lds());
+  const ProjPlan plan = plan_projection(nmax, refine != 0);      // (97 .. 128 with the stage on: the packed variant, as in a solver's warm iterations)
+  HIPCHK(proj_allow_big_lds(plan));
   nnsdp::RefinePipe pp;
   if (use_pipe) HIPCHK(pp.build(cn.data(), batch, tot));
   ProjArgs a{};
   a.cn = dcn.p; a.coff = dco.p; a.eoff = nullptr; a.nu = dnu.p; a.w = dw.p; a.Vg = dV.p; a.eig = nullptr; a.Tg = dT.p; a.Ug = dU.p;
   a.kappa = nullptr; a.tol_dev = nullptr; a.stats = dst.p; a.warm = 1; a.max_sweeps = 30; a.tol = tol;
-  a.refine = refine; a.rstate = drs.p; a.refine_acc = 30.0; a.refine_kcap = 0.05; a.refine_loose = 1.0; a.refine_k2cap = 0.64; a.refine_pivots = 2; a.gram_credit = 3;
-  if (const char* e = std::getenv("NNSDP_REFINE_KMAX")) a.refine_k2cap = std::atof(e) * std::atof(e);
-  if (const char* e = std::getenv("NNSDP_REFINE_ACC")) a.refine_acc = std::atof(e);
-  if (const char* e = std::getenv("NNSDP_REFINE_KCAP")) a.refine_kcap = std::atof(e);
-  if (const char* e = std::getenv("NNSDP_REFINE_PIVOTS")) a.refine_pivots = std::atoi(e);
-  DBuf<double> sB; DBuf<unsigned> sack, sseen, sxcc; DBuf<int> serr;
+  a.refine = refine; a.rstate = drs.p;
+  RefineTuning::from_env().bind(a);
+  SplitScratch split;
   if (const char* e = std::getenv("NNSDP_SPLIT_WARM")) {       // (test hook) two workgroups per block, as a solver's warm launches run
-    if (std::atoi(e) != 0 && alg == nnsdp::kProjPingPong && v_lds && batch <= 120) {
-      sB.alloc((size_t)batch * nnsdp::kSplitTileDoubles); sack.alloc(batch); sack.zero(); sseen.alloc(batch); sseen.zero(); sxcc.alloc(batch); sxcc.zero(); serr.alloc(1); serr.zero();
-      a.split = 1; a.nblk = batch; a.sB = sB.p; a.sack = sack.p; a.sseen = sseen.p; a.sxcc = sxcc.p; a.serr = serr.p; a.spin_limit = 20000000;
-    }
+    if (std::atoi(e) != 0 && plan.split_ok() && batch <= 120) { split.alloc(batch); split.bind(a, batch); }
   }
   struct Events {
     hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -2369,14 +2354,14 @@ int nnsdp_project_psd_warm_state(int32_t batch, const int32_t* n, const double* 
 #endif
     pp.launch(pa, nullptr); a.pmode = pp.pmode;
   }
-  launch_proj(a, batch, nmax, v_lds, lds, nullptr, alg);
+  launch_proj(plan, a, batch, nullptr);
   HIPCHK(hipEventRecord(ev.e1, nullptr));
   HIPCHK(hipGetLastError());
   HIPCHK(hipDeviceSynchronize());
   float ms = 0;
   HIPCHK(hipEventElapsedTime(&ms, ev.e0, ev.e1));
   if (kernel_ms) *kernel_ms = ms;
-  if (a.split && serr.download()[0] != 0) throw HipError("projection kernel, two workgroups per block: a helper workgroup did not deliver its tiles in time");
+  if (split.failed()) throw HipError("projection kernel, two workgroups per block: a helper workgroup did not deliver its tiles in time");
   {
     std::vector<unsigned char> gb(kGuard * sizeof(double));
     const char* names[] = {"nu", "w", "V", "T scratch", "U scratch"};

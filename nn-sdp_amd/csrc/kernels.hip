@@ -265,15 +265,10 @@ static constexpr int kPpLda = 99;          // ping-pong variant: fixed stride of
 static constexpr int kPpLdp = 100;         // ping-pong variant: stride of the sweep layout (even: aligned 16-byte row pairs)
 static constexpr int kSysHead = 16 + 66;   // red[16], sel[npg + 2 <= 130 ints] in front of A (fixed offsets)
 
-// BLOCK = true: block Jacobi.  Indices are grouped in blocks of 8; a round pairs the blocks (round robin),
-// one wave diagonalises each 16x16 diagonal sub-problem in place (one cyclic sweep, rotations accumulated
-// in a 16x16 J), then A <- J'AJ and V <- VJ are applied as 16x16x16 products on v_mfma_f64_16x16x4_f64.
-// 3 workgroup barriers per block round (nb-1 block rounds per sweep) instead of 2 per element round.
 // ALG = 2: register-resident systolic sweeps (below).  SPW = pair slots (2 matrix rows each) per wave, RPW = eigenvector
 // rows per wave; NT/64 * SPW >= ceil(n/2) and NT/64 * RPW >= n + 1 for every block of the launch.
 template <bool V_LDS, int NT, int ALG = 0, int SPW = 1, int RPW = 1>
 __device__ __forceinline__ void proj_body(const ProjArgs& a, const int k, const int role = 0) {      // role: 0 alone, 1 leader, 2 helper (ProjArgs::split)
-  constexpr bool BLOCK = ALG == 1;
   constexpr bool SYS = ALG == 2;
   constexpr bool PP = ALG == 3;
   // ALG = 4: blocks 129 .. 160 (the reference's 151-wide cliques of width-50 networks, chordal_cliques.jl:33-36).  The full matrix does
@@ -301,15 +296,13 @@ __device__ __forceinline__ void proj_body(const ProjArgs& a, const int k, const 
   // element (i, j) of the lower triangle (i >= j) / of the symmetric matrix in the variant's storage
   auto ixl = [&](int i, int j) { return PK ? ((i * (i + 1)) >> 1) + j : i * lda + j; };
   auto ixs = [&](int i, int j) { return i >= j ? ixl(i, j) : ixl(j, i); };
-  double* red = SYS ? lds : desc + (BLOCK ? 0 : 4 * npg);   // 16 doubles of reduction scratch (block mode: no pair descriptors)
+  double* red = SYS ? lds : desc + 4 * npg;   // 16 doubles of reduction scratch
   int* sel = reinterpret_cast<int*>(red + 16);  // npg + 2 ints: eigen-indices on the chosen side, counters
   double* V;
   int ldv;
   if (V_LDS) { V = SYS ? desc : red + 16 + (npg >> 1) + 2; ldv = lda; }
   else { V = a.Vg + a.coff[k]; ldv = n; }
   const double* nuk = a.nu + a.coff[k];
-  // block mode scratch: per block pair a 16x16 J (row-major) and 16 doubles of rotation parameters
-  double* Jall = V + (size_t)npg * ldv;
 
 #ifdef NNSDP_STAMPS
   long long sec_t[6]; sec_t[0] = clock64();
@@ -545,11 +538,6 @@ __device__ __forceinline__ void proj_body(const ProjArgs& a, const int k, const 
       if (tid == 0) a.sseen[k] = want;
     }
     __syncthreads();
-    if (BLOCK) {   // block mode reads both triangles: mirror the lower one
-      for (int j = tid >> 6; j < npg; j += NT >> 6)
-        for (int i = (tid & 63) + j + 1; i < npg; i += 64) A[j * lda + i] = A[i * lda + j];
-      __syncthreads();
-    }
   };
   auto pk_congruence = [&]() {
     // A <- V' A V for the packed variant, both products on the matrix cores with the streamed operand staged through LDS ONCE:
@@ -2000,124 +1988,6 @@ __device__ __forceinline__ void proj_body(const ProjArgs& a, const int k, const 
     if (V_LDS)
       for (int idx = tid; idx < (npg - np) * np; idx += NT) { int r = np + idx / np, col = idx - (r - np) * np; V[r + (size_t)col * ldv] = 0.0; }
     __syncthreads();
-  } else
-  if (BLOCK) {
-    constexpr int NW = NT / 64;
-    const int nb = npg >> 3, hb = nb >> 1, Mb = nb - 1, ntile = npg >> 4;
-    const int lane = tid & 63, wv = tid >> 6;
-    const int lr = lane & 15, lc = lane >> 4;
-    for (;;) {
-      double off2 = 0.0;
-      for (int j = tid >> 6; j < np; j += NT >> 6)
-        for (int i = (tid & 63) + j + 1; i < np; i += 64) { double v = A[i * lda + j]; off2 += v * v; }
-      off2 = 2.0 * block_sum(off2, red);
-      if (off2 <= thresh2 || sweeps >= a.max_sweeps) break;
-      for (int br = 0; br < Mb; ++br) {
-#ifdef NNSDP_STAMPS
-        long long tprev = clock64();
-#endif
-        // ---- phase S: one wave per block pair diagonalises A[I,I] in place (one cyclic sweep), J accumulates
-        if (wv < hb) {
-          const int P = pair_top(wv, br, Mb, hb), Q = pair_bot(wv, br, Mb, hb);
-          double* Jb = Jall + (size_t)wv * 272;
-          double* ics = Jb + 256;
-#pragma unroll
-          for (int t = 0; t < 4; ++t) { int e = lane + 64 * t; Jb[e] = ((e >> 4) == (e & 15)) ? 1.0 : 0.0; }
-          auto gi = [&](int l) { return l < 8 ? 8 * P + l : 8 * Q + l - 8; };   // local 0..15 -> matrix index
-          wave_lds_sync();
-          for (int ir = 0; ir < 15; ++ir) {
-            if (lane < 8) {
-              int p = gi(pair_top(lane, ir, 15, 8)), q = gi(pair_bot(lane, ir, 15, 8));
-              double c, sn;
-              jacobi_cs(A[p * lda + p], A[q * lda + q], A[p * lda + q], rot_thr, c, sn);
-              ics[2 * lane] = c; ics[2 * lane + 1] = sn;
-            }
-            wave_lds_sync();
-            {
-              int sa = lane >> 3, sb = lane & 7;
-              int l1p = pair_top(sa, ir, 15, 8), l1q = pair_bot(sa, ir, 15, 8);
-              int l2p = pair_top(sb, ir, 15, 8), l2q = pair_bot(sb, ir, 15, 8);
-              int p1 = gi(l1p), q1 = gi(l1q), p2 = gi(l2p), q2 = gi(l2q);
-              double c1 = ics[2 * sa], s1 = ics[2 * sa + 1], c2 = ics[2 * sb], s2 = ics[2 * sb + 1];
-              double b00 = A[p1 * lda + p2], b01 = A[p1 * lda + q2], b10 = A[q1 * lda + p2], b11 = A[q1 * lda + q2];
-              double t00 = c1 * b00 - s1 * b10, t01 = c1 * b01 - s1 * b11;
-              double t10 = s1 * b00 + c1 * b10, t11 = s1 * b01 + c1 * b11;
-              double n00 = t00 * c2 - t01 * s2, n01 = t00 * s2 + t01 * c2;
-              double n10 = t10 * c2 - t11 * s2, n11 = t10 * s2 + t11 * c2;
-              if (sa == sb) { n01 = 0.0; n10 = 0.0; }
-              A[p1 * lda + p2] = n00; A[p1 * lda + q2] = n01; A[q1 * lda + p2] = n10; A[q1 * lda + q2] = n11;
-              // J <- J R : (row, slot) items, 2 per lane
-#pragma unroll
-              for (int t = 0; t < 2; ++t) {
-                int it = lane + 64 * t;
-                int row = it & 15, sl = it >> 4;
-                int jp = pair_top(sl, ir, 15, 8), jq = pair_bot(sl, ir, 15, 8);
-                double c = ics[2 * sl], sn = ics[2 * sl + 1];
-                double xp = Jb[row * 16 + jp], xq = Jb[row * 16 + jq];
-                Jb[row * 16 + jp] = c * xp - sn * xq;
-                Jb[row * 16 + jq] = sn * xp + c * xq;
-              }
-            }
-            wave_lds_sync();
-          }
-        }
-        STAMP(0, tprev)
-        __syncthreads();
-        STAMP(1, tprev)
-        // ---- phase U1: A[:, I] <- A[:, I] J (rows outside I) and V[:, I] <- V[:, I] J, one 16-row tile per task
-        for (int task = wv; task < 2 * hb * ntile; task += NW) {
-          const bool isV = task >= hb * ntile;
-          int tt = isV ? task - hb * ntile : task;
-          int pi = tt / ntile, tile = tt - pi * ntile;
-          const int P = pair_top(pi, br, Mb, hb), Q = pair_bot(pi, br, Mb, hb);
-          const double* Jb = Jall + (size_t)pi * 272;
-          const int r0 = 16 * tile;
-          d4_t c = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-          for (int kk = 0; kk < 4; ++kk) {
-            int kl = 4 * kk + lc;
-            int kg = kl < 8 ? 8 * P + kl : 8 * Q + kl - 8;
-            double av = isV ? V[(r0 + lr) + (size_t)kg * ldv] : A[(r0 + lr) * lda + kg];
-            c = __builtin_amdgcn_mfma_f64_16x16x4f64(av, Jb[kl * 16 + lr], c, 0, 0, 0);
-          }
-          int cg = lr < 8 ? 8 * P + lr : 8 * Q + lr - 8;
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            int row = r0 + lc + 4 * r;
-            if (isV) V[row + (size_t)cg * ldv] = c[r];
-            else if ((row >> 3) != P && (row >> 3) != Q) A[row * lda + cg] = c[r];
-          }
-        }
-        __syncthreads();
-        STAMP(2, tprev)
-        // ---- phase U2: A[I, :] <- J' A[I, :] (columns outside I), one 16-column tile per task
-        for (int task = wv; task < hb * ntile; task += NW) {
-          int pi = task / ntile, tile = task - pi * ntile;
-          const int P = pair_top(pi, br, Mb, hb), Q = pair_bot(pi, br, Mb, hb);
-          const double* Jb = Jall + (size_t)pi * 272;
-          const int c0 = 16 * tile;
-          d4_t c = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-          for (int kk = 0; kk < 4; ++kk) {
-            int kl = 4 * kk + lc;
-            int kg = kl < 8 ? 8 * P + kl : 8 * Q + kl - 8;
-            c = __builtin_amdgcn_mfma_f64_16x16x4f64(Jb[kl * 16 + lr], A[kg * lda + c0 + lr], c, 0, 0, 0);
-          }
-          int col = c0 + lr;
-          if ((col >> 3) != P && (col >> 3) != Q) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              int il = lc + 4 * r;
-              int ig = il < 8 ? 8 * P + il : 8 * Q + il - 8;
-              A[ig * lda + col] = c[r];
-            }
-          }
-        }
-        __syncthreads();
-        STAMP(3, tprev)
-      }
-      ++sweeps;
-    }
   } else {
   double* const Tlog = PK ? a.Tg + a.coff[k] : nullptr;     // packed variant: the sweep's rotation log (the warm-start scratch, free by now)
   for (;;) {
@@ -2497,87 +2367,20 @@ __global__ __launch_bounds__(NT) void k_proj_jacobi_b(const ProjArgs* __restrict
   proj_body<V_LDS, NT, ALG, SPW, RPW>(a, blk);
 }
 
-// launch: projection algorithm by the largest block of the launch.
-//   kProjSystolic (default for 49 <= nmax <= 128): 512 threads, matrix + eigenvectors in registers
-//   kProjRoundRobin: LDS-resident round robin, NT = 1024 above kSmallBlock, 256 below (default for small blocks)
-//   kProjBlock: block Jacobi on MFMA (diagnostic; slower)
-enum { kProjRoundRobin = 0, kProjBlock = 1, kProjSystolic = 2, kProjPingPong = 3, kProjPacked = 4 };
+// Projection variants (the numbers NNSDP_PROJ_ALG takes; any other value, 1 included, selects round robin):
+//   kProjRoundRobin  LDS-resident round robin, 1024 threads above kSmallBlock, 256 up to it (default for small blocks)
+//   kProjSystolic    512 threads, matrix + eigenvectors in registers (blocks 49 .. 128; default for 97 .. 128)
+//   kProjPingPong    odd-even sweeps on two bordered matrices, V in LDS, 1024 threads (default for 41 .. 96)
+//   kProjPacked      packed lower triangle in LDS, V in HBM, 1024 threads (129 .. 160: the only variant that fits)
+enum { kProjRoundRobin = 0, kProjSystolic = 2, kProjPingPong = 3, kProjPacked = 4 };
 static constexpr int kMaxLdsBlock = 160;      // largest block the LDS-resident kernel takes (packed variant); above: library path
 inline bool proj_packed_ok(int nmax) { return nmax > 128 && nmax <= kMaxLdsBlock; }
 static constexpr int kSmallBlock = 40;
 static constexpr int kSysMin = 49;
 inline bool proj_sys_ok(int nmax) { return nmax >= kSysMin && nmax <= 128; }
 inline bool proj_pp_ok(int nmax) { return nmax > kSmallBlock && nmax <= 96; }   // V in LDS, 1024 threads
-#define NNSDP_PROJ_VARIANTS(X) \
-  X((k_proj_jacobi<true, 1024, 1>)) X((k_proj_jacobi<true, 256, 1>)) X((k_proj_jacobi<true, 1024>)) X((k_proj_jacobi<false, 1024>)) \
-  X((k_proj_jacobi<true, 256>)) X((k_proj_jacobi<false, 256>)) X((k_proj_jacobi<true, 512, 2, 6, 12>)) X((k_proj_jacobi<false, 512, 2, 8, 16>)) X((k_proj_jacobi<false, 512, 2, 7, 14>)) X((k_proj_jacobi<true, 1024, 3, 1, 5>)) X((k_proj_jacobi<true, 1024, 3, 1, 6>)) X((k_proj_jacobi<true, 1024, 3, 1, 7>)) \
-  X((k_proj_jacobi<false, 1024, 4>)) X((k_proj_jacobi_b<false, 1024, 4>)) \
-  X((k_proj_jacobi_b<true, 1024>)) X((k_proj_jacobi_b<false, 1024>)) X((k_proj_jacobi_b<true, 256>)) X((k_proj_jacobi_b<false, 256>)) \
-  X((k_proj_jacobi_b<true, 512, 2, 6, 12>)) X((k_proj_jacobi_b<false, 512, 2, 8, 16>)) X((k_proj_jacobi_b<false, 512, 2, 7, 14>)) X((k_proj_jacobi_b<true, 1024, 3, 1, 5>)) X((k_proj_jacobi_b<true, 1024, 3, 1, 6>)) X((k_proj_jacobi_b<true, 1024, 3, 1, 7>))
-inline void launch_proj(const ProjArgs& a, int nblocks, int nmax, bool v_lds, size_t lds, hipStream_t st, int alg = kProjRoundRobin) {
-  if (alg == kProjPacked) { hipLaunchKernelGGL((k_proj_jacobi<false, 1024, 4>), dim3(nblocks), dim3(1024), lds, st, a); return; }
-  if (alg == kProjPingPong && proj_pp_ok(nmax) && v_lds) {
-    const bool split = a.split != 0 && a.warm != 0 && a.nblk == nblocks;
-    ProjArgs b = a;
-    b.split = split ? 1 : 0;
-    const int grid = split ? ((nblocks + 7) & ~7) + nblocks : nblocks;
-    if (nmax <= 74) hipLaunchKernelGGL((k_proj_jacobi<true, 1024, 3, 1, 5>), dim3(grid), dim3(1024), lds, st, b);
-    else if (nmax <= 90) hipLaunchKernelGGL((k_proj_jacobi<true, 1024, 3, 1, 6>), dim3(grid), dim3(1024), lds, st, b);
-    else hipLaunchKernelGGL((k_proj_jacobi<true, 1024, 3, 1, 7>), dim3(grid), dim3(1024), lds, st, b);
-    return;
-  }
-  if (alg == kProjSystolic && proj_sys_ok(nmax)) {
-    if (v_lds) hipLaunchKernelGGL((k_proj_jacobi<true, 512, 2, 6, 12>), dim3(nblocks), dim3(512), lds, st, a);
-    else if (nmax <= 110) hipLaunchKernelGGL((k_proj_jacobi<false, 512, 2, 7, 14>), dim3(nblocks), dim3(512), lds, st, a);   // width-50 path cliques (101..103)
-    else hipLaunchKernelGGL((k_proj_jacobi<false, 512, 2, 8, 16>), dim3(nblocks), dim3(512), lds, st, a);
-    return;
-  }
-  if (alg == kProjBlock && v_lds) {
-    if (nmax > kSmallBlock) hipLaunchKernelGGL((k_proj_jacobi<true, 1024, 1>), dim3(nblocks), dim3(1024), lds, st, a);
-    else hipLaunchKernelGGL((k_proj_jacobi<true, 256, 1>), dim3(nblocks), dim3(256), lds, st, a);
-    return;
-  }
-  if (nmax > kSmallBlock) {
-    if (v_lds) hipLaunchKernelGGL((k_proj_jacobi<true, 1024>), dim3(nblocks), dim3(1024), lds, st, a);
-    else hipLaunchKernelGGL((k_proj_jacobi<false, 1024>), dim3(nblocks), dim3(1024), lds, st, a);
-  } else {
-    if (v_lds) hipLaunchKernelGGL((k_proj_jacobi<true, 256>), dim3(nblocks), dim3(256), lds, st, a);
-    else hipLaunchKernelGGL((k_proj_jacobi<false, 256>), dim3(nblocks), dim3(256), lds, st, a);
-  }
-}
-// batched form: `nblocks` blocks in total over the SDPs of a batch handle (device arrays args / map)
-inline void launch_proj_batched(const ProjArgs* dargs, const int2* dmap, int nblocks, int nmax, bool v_lds, size_t lds, hipStream_t st,
-                                int alg) {
-  if (alg == kProjPacked) { hipLaunchKernelGGL((k_proj_jacobi_b<false, 1024, 4>), dim3(nblocks), dim3(1024), lds, st, dargs, dmap); return; }
-  if (alg == kProjPingPong && proj_pp_ok(nmax) && v_lds) {
-    if (nmax <= 74) hipLaunchKernelGGL((k_proj_jacobi_b<true, 1024, 3, 1, 5>), dim3(nblocks), dim3(1024), lds, st, dargs, dmap);
-    else if (nmax <= 90) hipLaunchKernelGGL((k_proj_jacobi_b<true, 1024, 3, 1, 6>), dim3(nblocks), dim3(1024), lds, st, dargs, dmap);
-    else hipLaunchKernelGGL((k_proj_jacobi_b<true, 1024, 3, 1, 7>), dim3(nblocks), dim3(1024), lds, st, dargs, dmap);
-    return;
-  }
-  if (alg == kProjSystolic && proj_sys_ok(nmax)) {
-    if (v_lds) hipLaunchKernelGGL((k_proj_jacobi_b<true, 512, 2, 6, 12>), dim3(nblocks), dim3(512), lds, st, dargs, dmap);
-    else if (nmax <= 110) hipLaunchKernelGGL((k_proj_jacobi_b<false, 512, 2, 7, 14>), dim3(nblocks), dim3(512), lds, st, dargs, dmap);
-    else hipLaunchKernelGGL((k_proj_jacobi_b<false, 512, 2, 8, 16>), dim3(nblocks), dim3(512), lds, st, dargs, dmap);
-    return;
-  }
-  if (nmax > kSmallBlock) {
-    if (v_lds) hipLaunchKernelGGL((k_proj_jacobi_b<true, 1024>), dim3(nblocks), dim3(1024), lds, st, dargs, dmap);
-    else hipLaunchKernelGGL((k_proj_jacobi_b<false, 1024>), dim3(nblocks), dim3(1024), lds, st, dargs, dmap);
-  } else {
-    if (v_lds) hipLaunchKernelGGL((k_proj_jacobi_b<true, 256>), dim3(nblocks), dim3(256), lds, st, dargs, dmap);
-    else hipLaunchKernelGGL((k_proj_jacobi_b<false, 256>), dim3(nblocks), dim3(256), lds, st, dargs, dmap);
-  }
-}
-inline hipError_t proj_allow_big_lds() {
-  hipError_t e = hipSuccess;
-#define NNSDP_SET_LDS(K) if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&K), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  NNSDP_PROJ_VARIANTS(NNSDP_SET_LDS)
-#undef NNSDP_SET_LDS
-  return e;
-}
 
-inline size_t proj_lds_bytes(int nmax, bool v_lds, int alg = kProjRoundRobin) {
+inline size_t proj_lds_bytes(int nmax, bool v_lds, int alg) {
   int np = (nmax + 15) & ~15;
   if (alg == kProjPacked)    // packed lower triangle, desc[2][half][4], red, sel, the 32-row eigenvector panel (stride 161) and the rotation-log ring (2 x 4 rounds of (c, s) and of the packed pair indices)
     return ((((size_t)np * (np + 1)) / 2 + 1) + 4 * (size_t)np + 16 + (np >> 1) + 2 + 2 + 32 * 161 + 10 * (size_t)np) * sizeof(double);
@@ -2593,12 +2396,74 @@ inline size_t proj_lds_bytes(int nmax, bool v_lds, int alg = kProjRoundRobin) {
   }
   size_t d = (size_t)np * (np + 1) + 1 + 16 + (np >> 1) + 2;           // A, red, sel[np+2] (ints)
   if (v_lds) d += (size_t)np * (np + 1);
-  if (alg == kProjBlock) d += (size_t)(np >> 4) * 272;                 // J + rotation parameters per block pair
-  else d += 4 * (size_t)np;                                            // desc[2][half][4]
+  d += 4 * (size_t)np;                                                 // desc[2][half][4]
   return d * sizeof(double);
 }
-// block mode needs V in LDS and its scratch next to it
-inline bool proj_block_ok(int nmax) { return proj_lds_bytes(nmax, true, kProjBlock) <= 160 * 1024; }
+
+// everything a launch of the projection kernel needs, decided once from the largest block of the launch (plan_projection)
+struct ProjPlan {
+  int alg = kProjRoundRobin;
+  bool v_lds = false;          // eigenvectors in LDS (else in ProjArgs::Vg)
+  size_t lds = 0;              // dynamic LDS bytes
+  int nt = 0;                  // threads per workgroup
+  void (*kernel)(ProjArgs) = nullptr;                          // the k_proj_jacobi instantiation
+  void (*kernel_b)(const ProjArgs*, const int2*) = nullptr;    // the same instantiation of the batched form
+  bool packed() const { return alg == kProjPacked; }          // needs the Tg / Ug scratch (warm start, rotation log; basis of the refinement stage)
+  bool split_ok() const { return alg == kProjPingPong; }       // may take two workgroups per block (ProjArgs::split)
+  bool has_refine_stage() const { return alg == kProjPingPong || alg == kProjPacked; }   // (blocks 41 .. 160)
+  template <bool V_LDS, int NT, int ALG = 0, int SPW = 1, int RPW = 1>
+  void use() { nt = NT; kernel = k_proj_jacobi<V_LDS, NT, ALG, SPW, RPW>; kernel_b = k_proj_jacobi_b<V_LDS, NT, ALG, SPW, RPW>; }
+};
+// warm_refine: the launches are a solver's warm iterations with the refinement stage on.  Blocks 97 .. 128 then take the packed variant as
+// well: its stage carries most of a solve (width-50 networks in the Path decomposition, 101-wide blocks: 565 -> 347 us per iteration,
+// tools/width50_variants.py), while the systolic variant - faster sweeps, no stage - stays the choice for cold one-off projections.
+// NNSDP_PROJ_ALG (diagnostic) is read on every call: tests change it between calls in one process.
+inline ProjPlan plan_projection(int nmax, bool warm_refine = false) {
+  const char* env = std::getenv("NNSDP_PROJ_ALG");
+  ProjPlan p;
+  if (proj_packed_ok(nmax) || (warm_refine && nmax > 96 && nmax <= 128 && !env)) p.alg = kProjPacked;
+  else {
+    p.alg = env ? std::atoi(env) : proj_pp_ok(nmax) ? kProjPingPong : proj_sys_ok(nmax) ? kProjSystolic : kProjRoundRobin;
+    const bool fits = p.alg == kProjPacked ? nmax > 96 && nmax <= kMaxLdsBlock      // (diagnostic: the packed variant for 97 .. 128 as well)
+                    : p.alg == kProjPingPong ? proj_pp_ok(nmax) : p.alg == kProjSystolic && proj_sys_ok(nmax);
+    if (!fits) p.alg = kProjRoundRobin;
+  }
+  p.v_lds = !p.packed() && proj_lds_bytes(nmax, true, p.alg) <= 160 * 1024;
+  p.lds = proj_lds_bytes(nmax, p.v_lds, p.alg);
+  if (p.alg == kProjPacked) p.use<false, 1024, 4>();
+  else if (p.alg == kProjPingPong) {      // (V always fits LDS: 160 400 bytes at 96)
+    if (nmax <= 74) p.use<true, 1024, 3, 1, 5>();
+    else if (nmax <= 90) p.use<true, 1024, 3, 1, 6>();
+    else p.use<true, 1024, 3, 1, 7>();
+  } else if (p.alg == kProjSystolic) {
+    if (p.v_lds) p.use<true, 512, 2, 6, 12>();
+    else if (nmax <= 110) p.use<false, 512, 2, 7, 14>();   // width-50 path cliques (101..103)
+    else p.use<false, 512, 2, 8, 16>();
+  } else if (nmax > kSmallBlock) {
+    if (p.v_lds) p.use<true, 1024>(); else p.use<false, 1024>();
+  } else {
+    if (p.v_lds) p.use<true, 256>(); else p.use<false, 256>();
+  }
+  return p;
+}
+// the plan's kernel, both forms, may take more than the default 64 KB of LDS
+inline hipError_t proj_allow_big_lds(const ProjPlan& p) {
+  if (p.lds <= 64 * 1024) return hipSuccess;
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(p.kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(p.kernel_b), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  return e;
+}
+// one launch over `nblocks` blocks; a warm ping-pong launch over all a.nblk blocks with a.split set takes the split grid (kernel above)
+inline void launch_proj(const ProjPlan& p, const ProjArgs& a, int nblocks, hipStream_t st) {
+  ProjArgs b = a;
+  b.split = p.split_ok() && a.split != 0 && a.warm != 0 && a.nblk == nblocks ? 1 : 0;
+  const int grid = b.split ? ((nblocks + 7) & ~7) + nblocks : nblocks;
+  hipLaunchKernelGGL(p.kernel, dim3(grid), dim3(p.nt), p.lds, st, b);
+}
+// batched form: `nblocks` blocks in total over the SDPs of a batch handle (device arrays args / map)
+inline void launch_proj_batched(const ProjPlan& p, const ProjArgs* dargs, const int2* dmap, int nblocks, hipStream_t st) {
+  hipLaunchKernelGGL(p.kernel_b, dim3(nblocks), dim3(p.nt), p.lds, st, dargs, dmap);
+}
 
 // everything one plain ADMM iteration of one SDP needs besides the projection (batch handles: one launch per stage
 // for all SDPs, blockIdx.y = SDP)
