@@ -1252,7 +1252,7 @@ struct nnsdp_solver {
     if (trace_polish > 0 && lead() && iters_done >= next_trace) {
       next_trace = iters_done + trace_polish;
       double tp = now_s();
-      hipLaunchKernelGGL(k_extract_gamma, dim3(cdiv(S.ng, 256)), dim3(256), 0, st, S.ng, nu.p, d_sigma(), gs.p);
+      hipLaunchKernelGGL(k_extract_gamma, dim3(cdiv(S.ng, 256)), dim3(256), 0, st, S.ng, nu.p, d_sigma(), d_kappa(), gs.p);
       HIPCHK(hipStreamSynchronize(st));
       std::vector<double> gp = gs.download();
       bool ok = polish(gp);
@@ -1281,7 +1281,7 @@ struct nnsdp_solver {
       std::string err;
       if (lead()) {
         try {
-          hipLaunchKernelGGL(k_extract_gamma, dim3(cdiv(S.ng, 256)), dim3(256), 0, st, S.ng, nu.p, d_sigma(), gs.p);
+          hipLaunchKernelGGL(k_extract_gamma, dim3(cdiv(S.ng, 256)), dim3(256), 0, st, S.ng, nu.p, d_sigma(), d_kappa(), gs.p);
           HIPCHK(hipStreamSynchronize(st));
           std::vector<double> gp = gs.download();
           if (polish(gp)) {
@@ -1489,7 +1489,7 @@ struct nnsdp_solver {
   // libraries behind the polish round like.  finish() is therefore a collective call in sharded mode.
   void certificate(std::vector<double>& gam, double& lmax, bool& polished, DBuf<double>& Zd) {
     int ng = S.ng;
-    hipLaunchKernelGGL(k_extract_gamma, dim3(cdiv(ng, 256)), dim3(256), 0, st, ng, nu.p, d_sigma(), gs.p);
+    hipLaunchKernelGGL(k_extract_gamma, dim3(cdiv(ng, 256)), dim3(256), 0, st, ng, nu.p, d_sigma(), d_kappa(), gs.p);
     HIPCHK(hipStreamSynchronize(st));
     std::vector<double> gsh = gs.download();
     {

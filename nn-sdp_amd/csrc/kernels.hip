@@ -496,6 +496,10 @@ __device__ __forceinline__ void proj_body(const ProjArgs& a, const int k, const 
       // (every element is an agent-scope store of its own - coherent at the device's memory side without an L2 write-back - so the
       // hand-over only has to ORDER them in front of the count: wait for this wave's stores, meet the other waves, then count)
       if (tid == 0) __hip_atomic_store(a.sxcc + k, (unsigned)__builtin_amdgcn_s_getreg(kHwRegXccId), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      // every wave drains its OWN stores before the barrier: the workgroup-scope release below emits no vmcnt wait (not tgsplit
+      // mode), and the agent-scope release of tid 0 waits on wave 0's counter only - without this, tiles of waves 1 .. NW-1 could
+      // still be in flight when a leader on another CU sees the count advance
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
       __syncthreads();
       // ONE agent-scope release for the whole workgroup (the barrier orders every wave's stores in front of it): the L2 write-back it
@@ -3055,9 +3059,12 @@ __global__ __launch_bounds__(kThreads) void k_acc_reduce(const double* __restric
 
 
 // gs[g] = max(-ys[g], 0), ys = sigma * min(nu_s, 0)
-__global__ void k_extract_gamma(int ng, const double* __restrict__ nu, const double* __restrict__ sigma, double* __restrict__ gs) {
+// gamma_s = max(-y_s, 0), y = sigma (nu - w).  A penalty change still pending (kappa != 1: the next projection rescales
+// nu <- w + kappa (nu - w)) is part of the state, so y = sigma kappa (nu - w) - as when a solve ends on an adaptation check.
+__global__ void k_extract_gamma(int ng, const double* __restrict__ nu, const double* __restrict__ sigma, const double* __restrict__ kappa,
+                                double* __restrict__ gs) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < ng) { double v = nu[i]; gs[i] = v < 0.0 ? -(*sigma) * v : 0.0; }
+  if (i < ng) { double v = nu[i]; gs[i] = v < 0.0 ? -((*sigma) * (*kappa)) * v : 0.0; }
 }
 
 // K1 (assembly, reference coordinates): z[e] = z0[e] + sum_g A[e,g] gamma[g]; then scatter to dense

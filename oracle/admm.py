@@ -148,6 +148,23 @@ class AdmmState:
         self.nu = nu + self.alpha * res
         return w, x, res, Kxq
 
+    def check_quantities(self, nu_prev, w, x, res, Kxq):
+        """(pres, dres, objective, dual objective) of the step just taken from nu_prev (its outputs w, x, res, Kxq)"""
+        P = self.P
+        y = self.sigma * (nu_prev - w)
+        Kty = self.Kt(y)
+        rp = np.linalg.norm(res) / max(np.linalg.norm(Kxq), np.linalg.norm(w), 1e-300)
+        rd = np.linalg.norm(Kty - P.z0) / max(np.linalg.norm(Kty), np.linalg.norm(P.z0), 1e-300)
+        obj = -(P.c @ y[:self.ng]) / (P.zscale * P.cscale)
+        dobj = (P.z0 @ x) / (P.zscale * P.cscale)
+        return rp, rd, obj, dobj
+
+    def gamma(self) -> np.ndarray:
+        """the full-length multipliers of the current state, unscaled (gamma = max(-y, 0) of the multiplier block)"""
+        w = self.proj(self.nu)
+        y = self.sigma * (self.nu - w)
+        return self.P.unscale_gamma(np.maximum(-y[:self.ng], 0.0))
+
     def set_sigma(self, new_sigma: float):
         """keep (w, y) and re-express nu = w + y/sigma for the new penalty."""
         w = self.proj(self.nu)
@@ -171,12 +188,7 @@ def admm_solve(L: LmiOperator, opts: Optional[AdmmOptions] = None) -> AdmmResult
         nu_prev = S.nu
         w, x, res, Kxq = S.step()
         if it % opts.check_every == 0 or it == opts.max_iters:
-            y = S.sigma * (nu_prev - w)
-            Kty = S.Kt(y)
-            rp = np.linalg.norm(res) / max(np.linalg.norm(Kxq), np.linalg.norm(w), 1e-300)
-            rd = np.linalg.norm(Kty - P.z0) / max(np.linalg.norm(Kty), np.linalg.norm(P.z0), 1e-300)
-            obj = -(P.c @ y[:S.ng]) / (P.zscale * P.cscale)
-            dobj = (P.z0 @ x) / (P.zscale * P.cscale)
+            rp, rd, obj, dobj = S.check_quantities(nu_prev, w, x, res, Kxq)
             hist.append((it, rp, rd, obj, dobj, S.sigma))
             if opts.verbose:
                 print(f"it {it:6d} pres {rp:.3e} dres {rd:.3e} obj {obj:.8g} dobj {dobj:.8g} sigma {S.sigma:.3g}")
@@ -189,10 +201,7 @@ def admm_solve(L: LmiOperator, opts: Optional[AdmmOptions] = None) -> AdmmResult
                 ratio = np.sqrt(max(rp, 1e-300) / max(rd, 1e-300))
                 if ratio > 1.5 or ratio < 0.67:
                     S.set_sigma(S.sigma * min(max(ratio, 0.2), 5.0))
-    w = S.proj(S.nu)
-    y = S.sigma * (S.nu - w)
-    gs = np.maximum(-y[:S.ng], 0.0)
-    gam = P.unscale_gamma(gs)
+    gam = S.gamma()
     return AdmmResult(gamma=gam, objective=float(L.c @ gam), iters=it, pres=float(rp), dres=float(rd),
                       status=status, history=hist, x=x)
 

@@ -195,16 +195,20 @@ def make_congruence(q: Query, eliminate: bool = True, identity: bool = False, gu
     return Congruence(m=m, h=h, newpos=newpos, nred=int(keep.sum()))
 
 
-def build_operator(q: Query, mode: str = "single", normalize: bool = False) -> LmiOperator:
+def build_operator(q: Query, mode: str = "single", normalize: bool = False, merge_identical: bool = False) -> LmiOperator:
     """normalize=False: the reference's coordinates (used for assembly parity and for Z(gamma)).
     normalize=True : the solver's internal coordinates (Congruence above); generators whose
-    image vanishes (e.g. gac1 of an eliminated neuron) become zero columns."""
+    image vanishes (e.g. gac1 of an eliminated neuron) become zero columns.
+    merge_identical: keep one block per distinct index set (first occurrence), as the library does
+    (csrc/api.hip reduced_cliques: a sum of NSD matrices on one index set is NSD)."""
     net = q.net
     Zdim = net.Zdim
     a = Zdim - 1
     cg = make_congruence(q, eliminate=q.is_reach, identity=not normalize)
     cl_full = clique_index_sets(net, q.beta, mode)
     cl = [sorted({int(cg.newpos[i]) for i in c if cg.newpos[i] >= 0}) for c in cl_full]
+    if merge_identical:
+        cl = [c for k, c in enumerate(cl) if c not in cl[:k]]
     pat = build_pattern(cg.nred, cl)
     nin, nout, n1, n2 = q.gamma_dims()
     ng = nin + nout + n1 + n2
