@@ -178,6 +178,19 @@ int nnsdp_solve(const nnsdp_problem* p, const nnsdp_options* o, nnsdp_result* r)
 /* Handle form of the same solve, used by bench.py to time exactly K iterations. */
 typedef struct nnsdp_solver nnsdp_solver;
 int nnsdp_solver_create(const nnsdp_problem* p, const nnsdp_options* o, nnsdp_solver** out);
+/* Solver families (no reference analogue): a SIBLING of `parent` solves a problem that differs from the parent's in the output data
+ * only - normal / S / yc, invP, and the last affine layer Ms[K] (generators are built from layers 1 .. K-1; the output QC and the
+ * last layer enter the constant term z0 and nothing else).  Everything else must be equal, compared exactly: K, xdims, Ms[1 .. K-1],
+ * x1min / x1max, acymin / acymax, smin / smax, beta, activ, query_kind, out_kind (circle and ellipsoid count as one kind: the
+ * same gout generator; hyperplane and ellipsoid do not); -1 with a message naming the first field that differs.  Options are the parent's (an AUTO decomposition as the parent resolved it; a sibling whose z0 does not fit the parent's
+ * pattern - PATH with an S12 coupling - is refused, not re-decomposed).  A clique-sharded parent, or one that has been given a
+ * communicator, is refused, and a family member cannot be given one.  The sibling owns its z0, its iteration state, scratch, stream,
+ * graphs and statistics and SHARES BY REFERENCE COUNT what the set-up builds: the device operator (CSR / CSC, Dinv, c), the gather
+ * tables, the row and column class lists, the block lists, and M^-1 (dense, or the structured factors).  Any member, the parent
+ * included, may be destroyed first.  Inside a batch handle the members of a family whose M^-1 is dense are served by ONE pass over
+ * the matrix per 16 members (always, also a member alone in its batch: the stage's bits do not depend on who else is there);
+ * nnsdp_solver_iterate / _run on a member outside a batch use the single-solver stage like any solver. */
+int nnsdp_solver_create_sibling(nnsdp_solver* parent, const nnsdp_problem* p, nnsdp_solver** out);
 /* run `iters` ADMM iterations (no convergence test); eig_ms (may be NULL) receives the HIP-event
  * time of the projection kernel summed over these iterations. */
 int nnsdp_solver_iterate(nnsdp_solver* s, int32_t iters, double* eig_ms);
@@ -196,13 +209,20 @@ int nnsdp_solver_residuals(nnsdp_solver* s, double* pres, double* dres, double* 
 /* test / diagnostic entry: out = M^-1 q for a full-length multiplier vector q (entries of dropped multipliers are ignored and
  * returned as 0), through whichever form the handle uses; *structured (may be NULL) tells which, *operand_bytes its size */
 int nnsdp_solver_apply_minv(nnsdp_solver* s, const double* q, double* out, int32_t* structured, int64_t* operand_bytes);
+/* test / diagnostic entry, the multi-vector form: Q and out hold `nrhs` full-length multiplier vectors back to back (dropped
+ * multipliers ignored / returned 0); runs the fused kernel of the solver families on the handle's dense M^-1, 16 vectors per pass
+ * (-1 for a handle whose M^-1 is structured).  Vector j of a call equals a one-vector call on the same vector bit for bit.
+ * kernel_ms (may be NULL) receives the HIP-event time of the launch. */
+int nnsdp_solver_apply_minv_multi(nnsdp_solver* s, int32_t nrhs, const double* Q, double* out, double* kernel_ms);
 /* test / diagnostic entry: the multiplier block of the solver's fixed-point variable nu (solver coordinates and scaling), one
  * entry per multiplier of the problem (dropped multipliers 0).  In clique-sharded mode this block is replicated; the two-rank
  * test compares it bit for bit between ranks. */
 int nnsdp_solver_raw_multipliers(nnsdp_solver* s, double* out);
-/* diagnostic: what = 0 hipGraph launches so far, 1 whether an ncclAllReduce could be captured into a hipGraph (sharded mode over RCCL),
+/* diagnostic: what = 0 hipGraph launches that advanced this solver so far (its own and those of a batch handle it is a member of), 1 whether an ncclAllReduce could be captured into a hipGraph (sharded mode over RCCL),
  * 2 clique-sharded mode on, 3 iterations done, 4 PSD blocks, 5 largest block, 6 the hipIpc transport (0 off, 1 on with ordinary device
- * memory behind the exchange buffers, 2 on with fine-grained device memory - the default) */
+ * memory behind the exchange buffers, 2 on with fine-grained device memory - the default), 7 family id (0 for a solver that shares
+ * nothing, otherwise equal for all members of a family and distinct between the families of a process), 8 bytes of device memory this
+ * handle owns exclusively, 9 bytes it shares with other members of its family (buffers with more than one holder) */
 int nnsdp_solver_info(nnsdp_solver* s, int32_t what, double* out);
 /* iterate until converged / limits; fills r like nnsdp_solve */
 int nnsdp_solver_run(nnsdp_solver* s, nnsdp_result* r);
@@ -225,6 +245,8 @@ int nnsdp_batch_destroy(nnsdp_batch* b);
 /* re-establish lockstep after members of the batch were advanced individually (nnsdp_solver_residuals / _iterate / _advance):
  * the next batched iteration is a cold one for every member and the launch tables are rebuilt */
 int nnsdp_batch_resync(nnsdp_batch* b);
+/* diagnostic: what = 0 members still active, 1 fused family groups in the current launch tables, 2 members covered by them */
+int nnsdp_batch_info(nnsdp_batch* b, int32_t what, double* out);
 /* result of a solver that stopped with `status` (as returned by nnsdp_batch_run): certificate polish, gamma, Z */
 int nnsdp_solver_finish_status(nnsdp_solver* s, int32_t status, nnsdp_result* r);
 

@@ -7,6 +7,7 @@
 
 #include <dlfcn.h>
 
+#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -53,23 +54,31 @@ template <class T>
 struct DBuf {
   T* p = nullptr;
   size_t n = 0;
+  // the allocation is reference-counted: the members of a solver family (nnsdp_solver_create_sibling) hold the same set-up
+  // buffers, and the last holder frees them
+  std::shared_ptr<void> own;
   DBuf() = default;
   DBuf(const DBuf&) = delete;
   DBuf& operator=(const DBuf&) = delete;
-  ~DBuf() { if (p) (void)hipFree(p); }
+  void release() { own.reset(); p = nullptr; }
+  void adopt(void* q) { own = std::shared_ptr<void>(q, [](void* x) { (void)hipFree(x); }); p = static_cast<T*>(q); }
   void alloc(size_t count) {
-    if (p) { (void)hipFree(p); p = nullptr; }
+    release();
     n = count;
-    if (count) HIPCHK(hipMalloc(&p, count * sizeof(T)));
+    if (count) { void* q = nullptr; HIPCHK(hipMalloc(&q, count * sizeof(T))); adopt(q); }
   }
+  // a second holder of o's allocation (read-only use)
+  void share(const DBuf& o) { own = o.own; p = o.p; n = o.n; }
+  size_t bytes() const { return p ? n * sizeof(T) : 0; }
+  bool shared() const { return own && own.use_count() > 1; }
   // fine-grained device memory: coherent across devices WHILE kernels run (the hipIpc exchange buffers: a peer's kernel polls a flag
   // and reads data another device's kernel is publishing; coarse-grained memory only promises that at kernel boundaries)
   bool alloc_finegrained(size_t count) {
-    if (p) { (void)hipFree(p); p = nullptr; }
+    release();
     n = count;
     void* q = nullptr;
     if (hipExtMallocWithFlags(&q, count * sizeof(T), hipDeviceMallocFinegrained) != hipSuccess) { (void)hipGetLastError(); n = 0; return false; }
-    p = static_cast<T*>(q);
+    adopt(q);
     return true;
   }
   void upload(const std::vector<T>& h) {
@@ -440,8 +449,28 @@ struct nnsdp_solver {
   double* d_sigma() { return scal.p; }
   double* d_kappa() { return scal.p + 1; }
 
+  // A solver is set up in two parts: setup_shared() builds what depends on the network, the input box, the intervals, beta and
+  // the KIND of output QC only - the operator, the gather tables, the row / column classes and M^-1 - and setup_member() what one
+  // SDP owns: its iteration state, scratch, graphs.  nnsdp_solver_create runs both; a sibling (nnsdp_solver_create_sibling) takes
+  // the first part from its parent by reference count (share_from) and only builds its own z0.
+  int family = 0;                       // nnsdp_solver_info(7): 0 = shares nothing
+  bool setup_tm = false;
+  double setup_tl = 0.0;
+  void lap(const char* what) { if (setup_tm) { const double t = now_s(); std::fprintf(stderr, "[nnsdp setup] %-28s %7.2f ms\n", what, 1e3 * (t - setup_tl)); setup_tl = t; } }
+
   void setup(const nnsdp_problem* prob, const nnsdp_options* o) {
     t_create0 = now_s();
+    check_options(o);
+    setup_tm = std::getenv("NNSDP_SETUP_TIMING") != nullptr;     // diagnostic: where the set-up time goes (stderr)
+    setup_tl = now_s();
+    P.load(prob);
+    open_device();
+    setup_shared();
+    setup_member();
+    t_setup = now_s() - t_create0;
+  }
+
+  void check_options(const nnsdp_options* o) {
     opt = *o;
     if (opt.max_iters <= 0) throw std::invalid_argument("max_iters must be > 0");
     if (!(opt.alpha > 0.0 && opt.alpha < 2.0)) throw std::invalid_argument("alpha must be in (0,2)");
@@ -449,10 +478,12 @@ struct nnsdp_solver {
     if (opt.check_every <= 0) opt.check_every = 50;
     if (opt.decomp_mode < NNSDP_DECOMP_DENSE || opt.decomp_mode > NNSDP_DECOMP_AUTO)
       throw std::invalid_argument("unrecognized decomp_mode");
-    const bool tm = std::getenv("NNSDP_SETUP_TIMING") != nullptr;     // diagnostic: where the set-up time goes (stderr)
-    double tl = now_s();
-    auto lap = [&](const char* what) { if (tm) { const double t = now_s(); std::fprintf(stderr, "[nnsdp setup] %-28s %7.2f ms\n", what, 1e3 * (t - tl)); tl = t; } };
-    P.load(prob);
+    if (!(opt.interval_guard >= 0.0 && opt.interval_guard < 0.1)) throw std::invalid_argument("interval_guard must be in [0, 0.1)");
+    if (opt.minv_mode < 0 || opt.minv_mode > 2) throw std::invalid_argument("minv_mode must be 0 (auto), 1 (dense) or 2 (structured)");
+  }
+
+  // the certificate's host half on a second thread, the device, the stream and the library handle of this SDP (P is loaded)
+  void open_device() {
     if (!std::getenv("NNSDP_NO_ASYNC_SETUP")) {
       std::unique_ptr<FullOperator> fo(new FullOperator());
       fo->P = P;
@@ -461,7 +492,12 @@ struct nnsdp_solver {
     require_gpu();
     if (opt.device >= 0) HIPCHK(hipSetDevice(opt.device));
     HIPCHK(hipStreamCreate(&st));
-    if (!(opt.interval_guard >= 0.0 && opt.interval_guard < 0.1)) throw std::invalid_argument("interval_guard must be in [0, 0.1)");
+    roc.reset(new RocHandle());
+    RBCHK(rocblas_set_stream(roc->h, st));
+    lap("stream + rocBLAS handle");
+  }
+
+  void setup_shared() {
     C = make_congruence(P, opt.normalize != 0, opt.interval_guard);
     // NNSDP_DECOMP_AUTO: the finest exact decomposition the query allows - the path cliques {x_k, x_k+1, affine} when the output QC
     // does not couple x_1 with x_K (every reach query, hyperplane safety sets: the generator table then fits their pattern, which
@@ -512,29 +548,11 @@ struct nnsdp_solver {
       if (cn[k] <= nnsdp::kMaxLdsBlock) { small_idx.push_back(k); nmax_small = std::max(nmax_small, cn[k]); }
       else big_idx.push_back(k);
     }
-    if (!big_idx.empty()) {
-      build_compact_lists(0, ncl);
-      big_A.alloc((size_t)nmax * nmax); big_T.alloc((size_t)nmax * nmax); big_D.alloc(nmax); big_E.alloc(nmax);
-      big_info.alloc(big_idx.size()); big_info.zero();
-      big_flag.alloc(1); big_flag.zero();
-    }
+    if (!big_idx.empty()) build_compact_lists(0, ncl);
     const int nsm = std::max(nmax_small, 1);
     if (const char* e = std::getenv("NNSDP_REFINE")) opt.proj_refine = std::atoi(e);                   // (diagnostic override, read before the variant is chosen)
     tune = RefineTuning::from_env();
     plan = nnsdp::plan_projection(nsm, opt.proj_refine != 0);
-    {
-      // two workgroups per block for the warm-start congruence (ProjArgs::split): only where the second workgroup finds a free CU (one
-      // SDP's blocks; the batch handle fills the chip already and keeps the one-workgroup form) and where it pays (a block above 80:
-      // six tile columns; at five and fewer the two forms tie - W40-D20 Double 57.8 / 58.3 us per step).  What the hand-over may cost
-      // decided everything: with an agent-scope fence in every wave and an acquire in every poll (an L2 write-back / invalidate each)
-      // the launch was SLOWER (66.4 against 61.8 us at n = 85); with workgroup-scope ordering only it was fast and WRONG under
-      // multi-process contention (the two-rank test saw stale tiles in 2 runs of 3: the pair does not always share an L2 then); with
-      // ONE agent-scope release behind the helper's barrier and ONE acquire fence after the leader's poll it is right and 3-4 us
-      // faster per launch (56.8 against 59.9 us, W40-D20 76.5 against 78.1 us per step; profiles/r04_split_probe.log)
-      int want = nsm > 80 ? 1 : 0;
-      if (const char* e = std::getenv("NNSDP_SPLIT")) want = std::atoi(e);                              // (diagnostic override)
-      if (want != 0 && plan.split_ok() && big_idx.empty() && ncl <= 120) split.alloc(ncl);
-    }
     // gather sources: entry e <- (clique k, lower element (i,j))
     std::vector<int> sptr(S.NE + 1, 0);
     for (int k = 0; k < ncl; ++k) {
@@ -564,17 +582,7 @@ struct nnsdp_solver {
     d_cn.upload(cn); d_coff.upload(coff); d_sptr.upload(sptr); d_soff.upload(soff);
     d_isdiag.upload(isdiag); d_gidx.upload(gidx);
     lap("gather tables + upload");
-    d_stats.alloc(14); d_stats.zero();
-    {
-      void* hp = nullptr;
-      HIPCHK(hipHostMalloc(&hp, 8 * sizeof(double) + 16 * sizeof(int), hipHostMallocDefault));
-      std::memset(hp, 0, 8 * sizeof(double) + 16 * sizeof(int));
-      acc_host = static_cast<double*>(hp);
-      stats_host = reinterpret_cast<int*>(acc_host + 8);
-    }
     giters = graph_iters_for(opt.check_every);
-    if (const char* e = std::getenv("NNSDP_PIPE")) pipe_mode = std::atoi(e);                             // (diagnostic override)
-    d_rstate.alloc(4 * (size_t)std::max(ncl, 1)); d_rstate.zero();      // (4 ints per block: kernels.hip, ProjArgs::rstate)
     {
       std::vector<int> lr;
       for (int e = 0; e < S.NE; ++e)
@@ -600,12 +608,8 @@ struct nnsdp_solver {
       d_colcls.upload(cc);
     }
     // M^-1 on the device (rocSOLVER potrf + potri; one-time plain-library factorisation)
-    roc.reset(new RocHandle());
-    RBCHK(rocblas_set_stream(roc->h, st));
-    lap("rocBLAS handle");
     int ng = S.ng;
     ldm = (ng + 1) & ~1;
-    if (opt.minv_mode < 0 || opt.minv_mode > 2) throw std::invalid_argument("minv_mode must be 0 (auto), 1 (dense) or 2 (structured)");
     if (opt.minv_mode == 2 || (opt.minv_mode == 0 && ng >= kStructuredMinvFrom)) {
       mplan = plan_minv(S);
       if (mplan.ok) minv_structured = true;
@@ -633,6 +637,41 @@ struct nnsdp_solver {
     if (info.download()[0] != 0) throw HipError("inverse of M = I + A'D^-1A failed (potri info != 0)");
     lap("potri + symmetrise");
     }
+  }
+
+  // what one SDP owns: scratch of the projection variants, counters, the iteration state (S, the plan and the tables are in place,
+  // built by setup_shared or taken over by share_from)
+  void setup_member() {
+    const int ng = S.ng;
+    if (!big_idx.empty()) {
+      big_A.alloc((size_t)nmax * nmax); big_T.alloc((size_t)nmax * nmax); big_D.alloc(nmax); big_E.alloc(nmax);
+      big_info.alloc(big_idx.size()); big_info.zero();
+      big_flag.alloc(1); big_flag.zero();
+    }
+    {
+      const int nsm = std::max(nmax_small, 1);
+      // two workgroups per block for the warm-start congruence (ProjArgs::split): only where the second workgroup finds a free CU (one
+      // SDP's blocks; the batch handle fills the chip already and keeps the one-workgroup form) and where it pays (a block above 80:
+      // six tile columns; at five and fewer the two forms tie - W40-D20 Double 57.8 / 58.3 us per step).  What the hand-over may cost
+      // decided everything: with an agent-scope fence in every wave and an acquire in every poll (an L2 write-back / invalidate each)
+      // the launch was SLOWER (66.4 against 61.8 us at n = 85); with workgroup-scope ordering only it was fast and WRONG under
+      // multi-process contention (the two-rank test saw stale tiles in 2 runs of 3: the pair does not always share an L2 then); with
+      // ONE agent-scope release behind the helper's barrier and ONE acquire fence after the leader's poll it is right and 3-4 us
+      // faster per launch (56.8 against 59.9 us, W40-D20 76.5 against 78.1 us per step; profiles/r04_split_probe.log)
+      int want = nsm > 80 ? 1 : 0;
+      if (const char* e = std::getenv("NNSDP_SPLIT")) want = std::atoi(e);                              // (diagnostic override)
+      if (want != 0 && plan.split_ok() && big_idx.empty() && ncl <= 120) split.alloc(ncl);
+    }
+    d_stats.alloc(14); d_stats.zero();
+    {
+      void* hp = nullptr;
+      HIPCHK(hipHostMalloc(&hp, 8 * sizeof(double) + 16 * sizeof(int), hipHostMallocDefault));
+      std::memset(hp, 0, 8 * sizeof(double) + 16 * sizeof(int));
+      acc_host = static_cast<double*>(hp);
+      stats_host = reinterpret_cast<int*>(acc_host + 8);
+    }
+    if (const char* e = std::getenv("NNSDP_PIPE")) pipe_mode = std::atoi(e);                             // (diagnostic override)
+    d_rstate.alloc(4 * (size_t)std::max(ncl, 1)); d_rstate.zero();      // (4 ints per block: kernels.hip, ProjArgs::rstate)
     // iteration state
     nu.alloc(ng + nmat); w.alloc(ng + nmat); Vg.alloc(nmat);
     if (plan.packed()) { Tg.alloc(nmat); Tg.zero(); Ug.alloc(nmat); Ug.zero(); }      // scratch of the packed variant (warm start, rotation log; new basis of its refinement stage)
@@ -658,6 +697,109 @@ struct nnsdp_solver {
     k0 = 0; k1 = ncl;
     build_pipe();
     lap("state buffers");
+  }
+
+  // ---- solver families ---------------------------------------------------------------------------------------------------------
+  // The output QC (normal / S / yc, invP) and the last affine layer enter z0 and nothing else (OperatorBuilder::build_z0): two SDPs
+  // that agree in everything else have the same generators, cost, kept set, column scales, pattern, tables and M^-1.
+  // First field in which q cannot share p's set-up, or nullptr.
+  static const char* family_mismatch(const ProblemCopy& p, const ProblemCopy& q) {
+    if (p.K != q.K) return "K";
+    if (p.xdims != q.xdims) return "xdims";
+    for (int k = 0; k + 1 < p.K; ++k) if (p.W[k] != q.W[k] || p.b[k] != q.b[k]) return "M (an affine layer before the last one)";
+    if (p.x1min != q.x1min) return "x1min";
+    if (p.x1max != q.x1max) return "x1max";
+    if (p.acymin != q.acymin) return "acymin";
+    if (p.acymax != q.acymax) return "acymax";
+    if (p.smin != q.smin) return "smin";
+    if (p.smax != q.smax) return "smax";
+    if (p.beta != q.beta) return "beta";
+    if (p.activ != q.activ) return "activ";
+    if (p.query_kind != q.query_kind) return "query_kind";
+    // (circle and ellipsoid are one kind here: both give the gout generator the coefficient -0.5, the hyperplane -1)
+    auto gout_kind = [](int k) { return k == NNSDP_OUT_ELLIPSOID ? (int)NNSDP_OUT_CIRCLE : k; };
+    if (gout_kind(p.out_kind) != gout_kind(q.out_kind)) return "out_kind";
+    return nullptr;
+  }
+
+  // every set-up buffer of `o`, by reference
+  void share_from(nnsdp_solver& o) {
+    C = o.C; pat = o.pat; S = o.S;
+    cn = o.cn; coff = o.coff; nmat = o.nmat; ncl = o.ncl; nmax = o.nmax; nmax_small = o.nmax_small;
+    small_idx = o.small_idx; big_idx = o.big_idx; plan = o.plan; tune = o.tune; ldm = o.ldm; giters = o.giters;
+    ncs = o.ncs; nmed = o.nmed; nmsrc = o.nmsrc; nnz_A = o.nnz_A; nlong = o.nlong;
+    D.NE = o.D.NE; D.ng = o.D.ng; D.n = o.D.n;
+    D.csr_ptr.share(o.D.csr_ptr); D.csr_col.share(o.D.csr_col); D.csr_val.share(o.D.csr_val);
+    D.csc_ptr.share(o.D.csc_ptr); D.csc_row.share(o.D.csc_row); D.csc_val.share(o.D.csc_val);
+    D.c.share(o.D.c); D.Dinv.share(o.D.Dinv); D.erow.share(o.D.erow); D.ecol.share(o.D.ecol);
+    d_cn.share(o.d_cn); d_coff.share(o.d_coff); d_sptr.share(o.d_sptr); d_soff.share(o.d_soff); d_isdiag.share(o.d_isdiag);
+    d_gidx.share(o.d_gidx); d_long.share(o.d_long); d_medrows.share(o.d_medrows); d_medsrc.share(o.d_medsrc); d_colcls.share(o.d_colcls);
+    if (!big_idx.empty()) {      // (the compact lists of all blocks: a family member is never sharded)
+      proj_small = o.proj_small; proj_big = o.proj_big; nmax_proj_small = o.nmax_proj_small;
+      d_cn_s.share(o.d_cn_s); d_coff_s.share(o.d_coff_s);
+    }
+    minv_structured = o.minv_structured;
+    if (!minv_structured) Minv.share(o.Minv);
+    else {
+      mplan = o.mplan; m_nslots = o.m_nslots;
+      m_clo.share(o.m_clo); m_chi.share(o.m_chi); m_w0.share(o.m_w0); m_w1.share(o.m_w1); m_hslot0.share(o.m_hslot0);
+      m_chunk_of.share(o.m_chunk_of); m_sep_of.share(o.m_sep_of); m_sep_gen.share(o.m_sep_gen); m_slot_chunk.share(o.m_slot_chunk);
+      m_slotA.share(o.m_slotA); m_slotB.share(o.m_slotB); m_poff.share(o.m_poff); m_hoff.share(o.m_hoff);
+      m_P.share(o.m_P); m_H.share(o.m_H); m_HT.share(o.m_HT); m_Sc.share(o.m_Sc); m_v.share(o.m_v); m_kap.share(o.m_kap);
+      bind_minv_dev(o.mdev.r);
+    }
+  }
+
+  // device bytes this handle holds alone / together with other members of its family (nnsdp_solver_info 8, 9)
+  void device_bytes(size_t& own, size_t& shared_b) const {
+    own = shared_b = 0;
+    auto add = [&](size_t b, bool sh) { (sh ? shared_b : own) += b; };
+#define NNSDP_B(x) add((x).bytes(), (x).shared());
+    NNSDP_B(D.csr_ptr) NNSDP_B(D.csr_col) NNSDP_B(D.csr_val) NNSDP_B(D.csc_ptr) NNSDP_B(D.csc_row) NNSDP_B(D.csc_val) NNSDP_B(D.z0) NNSDP_B(D.c)
+    NNSDP_B(D.Dinv) NNSDP_B(D.erow) NNSDP_B(D.ecol) NNSDP_B(d_cn_s) NNSDP_B(d_coff_s) NNSDP_B(big_A) NNSDP_B(big_T) NNSDP_B(big_D) NNSDP_B(big_E)
+    NNSDP_B(big_info) NNSDP_B(big_flag) NNSDP_B(d_cn) NNSDP_B(d_sptr) NNSDP_B(d_stats) NNSDP_B(d_long) NNSDP_B(d_rstate) NNSDP_B(d_medrows)
+    NNSDP_B(d_medsrc) NNSDP_B(d_colcls) NNSDP_B(d_coff) NNSDP_B(d_soff) NNSDP_B(d_isdiag) NNSDP_B(d_gidx) NNSDP_B(Tg) NNSDP_B(Ug) NNSDP_B(nu) NNSDP_B(w)
+    NNSDP_B(Vg) NNSDP_B(x) NNSDP_B(g) NNSDP_B(p) NNSDP_B(qv) NNSDP_B(ww) NNSDP_B(Minv) NNSDP_B(scal) NNSDP_B(acc) NNSDP_B(gs) NNSDP_B(accp)
+    NNSDP_B(m_clo) NNSDP_B(m_chi) NNSDP_B(m_w0) NNSDP_B(m_w1) NNSDP_B(m_hslot0) NNSDP_B(m_chunk_of) NNSDP_B(m_sep_of) NNSDP_B(m_sep_gen)
+    NNSDP_B(m_slot_chunk) NNSDP_B(m_slotA) NNSDP_B(m_slotB) NNSDP_B(m_poff) NNSDP_B(m_hoff) NNSDP_B(m_P) NNSDP_B(m_H) NNSDP_B(m_HT) NNSDP_B(m_Sc)
+    NNSDP_B(m_v) NNSDP_B(m_kap) NNSDP_B(m_t) NNSDP_B(m_rpart) NNSDP_B(m_rvec) NNSDP_B(m_xS) NNSDP_B(m_coef) NNSDP_B(m_dpart) NNSDP_B(symv_part)
+    NNSDP_B(split.B) NNSDP_B(split.ack) NNSDP_B(split.seen) NNSDP_B(split.xcc) NNSDP_B(split.err)
+#undef NNSDP_B
+  }
+
+  // a member of `parent`'s family for a problem that differs from the parent's in the output QC (and the last affine layer) only
+  void setup_sibling(nnsdp_solver& parent, const nnsdp_problem* prob) {
+    t_create0 = now_s();
+    if (parent.sharded) throw std::invalid_argument("a clique-sharded solver (or one that has been given a communicator) cannot have siblings");
+    opt = parent.opt;                   // (decomposition as the parent resolved it)
+    setup_tm = std::getenv("NNSDP_SETUP_TIMING") != nullptr;
+    setup_tl = now_s();
+    P.load(prob);
+    if (const char* f = family_mismatch(parent.P, P))
+      throw std::invalid_argument(std::string("the sibling's problem differs from its parent's in `") + f + "`: only the output data (normal / S / yc, invP) and the last affine layer may differ");
+    open_device();
+    share_from(parent);
+    // this member's z0 on the shared pattern, scaled as scale_operator scales it
+    std::vector<double> z0;
+    try {
+      z0 = OperatorBuilder(P, C, pat).build_z0_only();
+    } catch (const std::runtime_error& e) {
+      if (opt.decomp_mode == NNSDP_DECOMP_PATH)
+        throw std::invalid_argument(std::string("PATH decomposition needs an output QC without x_1 -- x_K coupling (S12 = 0): ") + e.what());
+      throw std::invalid_argument(std::string("the sibling's output QC does not fit the parent's clique pattern: ") + e.what());
+    }
+    double zn = 0;
+    for (double v : z0) zn += v * v;
+    zn = std::sqrt(zn);
+    S.zscale = (opt.normalize != 0 && zn > 0) ? 1.0 / zn : 1.0;
+    S.z0 = std::move(z0);
+    for (auto& v : S.z0) v *= S.zscale;
+    D.z0.upload(S.z0);
+    lap("sibling: z0 + shared set-up");
+    setup_member();
+    static std::atomic<int> next_family{0};
+    if (parent.family == 0) parent.family = ++next_family;
+    family = parent.family;
     t_setup = now_s() - t_create0;
   }
 
@@ -737,16 +879,10 @@ struct nnsdp_solver {
     m_clo.upload(Q.clo); m_chi.upload(Q.chi); m_w0.upload(Q.w0); m_w1.upload(Q.w1); m_hslot0.upload(hslot0);
     m_poff.upload(Q.poff); m_hoff.upload(Q.hoff); m_chunk_of.upload(Q.chunk_of); m_sep_of.upload(Q.sep_of);
     m_sep_gen.upload(sep_gen); m_slot_chunk.upload(slot_chunk); m_slotA.upload(slotA); m_slotB.upload(slotB);
-    m_t.alloc(ng); m_rpart.alloc(std::max(nslots, 1)); m_xS.alloc(std::max(ldS, 2)); m_rvec.alloc(std::max(ldS, 2)); m_coef.alloc(8);
     m_v.alloc((size_t)ng * std::max(Q.r, 1)); m_kap.alloc(64);
-    m_dpart.alloc(8 * kMinvParts);
-    m_v.zero(); m_kap.zero(); m_coef.zero(); m_rvec.zero(); m_xS.zero(); m_dpart.zero();
-    mdev.ng = ng; mdev.nchunk = nc; mdev.nS = nS; mdev.ldS = ldS; mdev.r = 0; mdev.nslots = nslots;
-    mdev.clo = m_clo.p; mdev.chi = m_chi.p; mdev.w0 = m_w0.p; mdev.w1 = m_w1.p; mdev.hslot0 = m_hslot0.p;
-    mdev.poff = m_poff.p; mdev.hoff = m_hoff.p; mdev.chunk_of = m_chunk_of.p; mdev.sep_of = m_sep_of.p; mdev.sep_gen = m_sep_gen.p;
-    mdev.slot_chunk = m_slot_chunk.p; mdev.slotA = m_slotA.p; mdev.slotB = m_slotB.p;
-    mdev.Pinv = m_P.p; mdev.H = m_H.p; mdev.HT = m_HT.p; mdev.Scinv = m_Sc.p; mdev.v = m_v.p; mdev.kap = m_kap.p;
-    mdev.t = m_t.p; mdev.rpart = m_rpart.p; mdev.rvec = m_rvec.p; mdev.xS = m_xS.p; mdev.coef = m_coef.p; mdev.dpart = m_dpart.p;
+    m_v.zero(); m_kap.zero();
+    m_nslots = nslots;
+    bind_minv_dev(0);
     // low-rank part: v = T^-1 U (the structured apply with r = 0), kap = (diag(1/d) + U'v)^-1 on the host (r x r, r <= 8)
     if (Q.r > 0) {
       DBuf<double> U, V;
@@ -781,6 +917,23 @@ struct nnsdp_solver {
     HIPCHK(hipStreamSynchronize(st));
   }
 
+  // scratch of one SDP's applications of the structured M^-1 and the device view of the (possibly shared) factors; r = rank of the
+  // low-rank term in use
+  int m_nslots = 0;
+  void bind_minv_dev(int r) {
+    const MinvPlan& Q = mplan;
+    const int ng = S.ng, nS = Q.nS, ldS = Q.ldS;
+    m_t.alloc(ng); m_rpart.alloc(std::max(m_nslots, 1)); m_xS.alloc(std::max(ldS, 2)); m_rvec.alloc(std::max(ldS, 2)); m_coef.alloc(8);
+    m_dpart.alloc(8 * kMinvParts);
+    m_coef.zero(); m_rvec.zero(); m_xS.zero(); m_dpart.zero();
+    mdev.ng = ng; mdev.nchunk = Q.nchunk; mdev.nS = nS; mdev.ldS = ldS; mdev.r = r; mdev.nslots = m_nslots;
+    mdev.clo = m_clo.p; mdev.chi = m_chi.p; mdev.w0 = m_w0.p; mdev.w1 = m_w1.p; mdev.hslot0 = m_hslot0.p;
+    mdev.poff = m_poff.p; mdev.hoff = m_hoff.p; mdev.chunk_of = m_chunk_of.p; mdev.sep_of = m_sep_of.p; mdev.sep_gen = m_sep_gen.p;
+    mdev.slot_chunk = m_slot_chunk.p; mdev.slotA = m_slotA.p; mdev.slotB = m_slotB.p;
+    mdev.Pinv = m_P.p; mdev.H = m_H.p; mdev.HT = m_HT.p; mdev.Scinv = m_Sc.p; mdev.v = m_v.p; mdev.kap = m_kap.p;
+    mdev.t = m_t.p; mdev.rpart = m_rpart.p; mdev.rvec = m_rvec.p; mdev.xS = m_xS.p; mdev.coef = m_coef.p; mdev.dpart = m_dpart.p;
+  }
+
   // out = M^-1 q through the structured form: four dependent launches (the second is tiny)
   void apply_structured_minv(const double* q, double* out, hipStream_t s_) {
     const int ng = S.ng;
@@ -800,6 +953,7 @@ struct nnsdp_solver {
     if (nr < 1 || rk < 0 || rk >= nr || (!id128 && !fn)) throw std::invalid_argument("bad communicator arguments");
     if (use_ipc && (!fn || nr > 8)) throw std::invalid_argument("the hipIpc transport needs the caller's host all-reduce for its set-up and at most 8 ranks");
     if (iters_done != 0) throw std::invalid_argument("set_comm must be called before the first iteration");
+    if (family != 0) throw std::invalid_argument("a member of a solver family cannot be clique-sharded (its M^-1 is shared)");
     if (sharded) throw std::invalid_argument("the solver already has a communicator");
     if (fn) { ar_fn = fn; ar_user = user; }
     else {
@@ -1675,6 +1829,12 @@ struct nnsdp_batch {
   DBuf<IterArgs> d_it;
   DBuf<ProjArgs> d_pw, d_pc;           // warm / cold projection arguments
   DBuf<int2> d_map;
+  // members of a solver family with a dense inverse: ONE pass over their common M^-1 per kFusedWidth members (k_minv_family) instead
+  // of a tiled product per member.  d_it_sym lists the members that keep the per-member stage when the batch holds families.
+  DBuf<IterArgs> d_it_sym;
+  DBuf<int> d_fmem;
+  DBuf<FusedPass> d_fpass;
+  int n_sym = 0, n_fgroups = 0, n_fmembers = 0, n_fpass = 0, gx_fused = 0;
   int nblocks = 0, nmax = 0;
   bool any_structured = false, any_big = false;
   ProjPlan plan;
@@ -1712,15 +1872,24 @@ struct nnsdp_batch {
   void rebuild() {
     if (gexec) { (void)hipGraphExecDestroy(gexec); gexec = nullptr; }
     if (graph) { (void)hipGraphDestroy(graph); graph = nullptr; }
+    n_sym = n_fgroups = n_fmembers = n_fpass = gx_fused = 0;
     if (act.empty()) return;
     std::vector<IterArgs> it;
     std::vector<ProjArgs> pw, pc;
     std::vector<int2> map;
     nmax = 0; gx_gather = gx_gather_med = gx_at_s = gx_at_l = gx_gemv = gx_ax = gx_ax_med = gx_long = gx_upd = gx_tiles = gx_nb = 0;
     any_structured = false; any_big = false;
+    std::vector<IterArgs> it_sym;
+    std::vector<std::pair<int, std::vector<int>>> fam;      // family id -> its dense members here, in batch order
     for (size_t b = 0; b < act.size(); ++b) {
       nnsdp_solver* s = act[b];
       any_structured = any_structured || s->minv_structured;
+      const bool fused = s->family != 0 && !s->minv_structured;      // (always, also alone: a member's bits must not depend on its group's size)
+      if (fused) {
+        auto f = std::find_if(fam.begin(), fam.end(), [&](const std::pair<int, std::vector<int>>& x) { return x.first == s->family; });
+        if (f == fam.end()) { fam.emplace_back(s->family, std::vector<int>()); f = fam.end() - 1; }
+        f->second.push_back((int)b);
+      }
       HIPCHK(hipStreamSynchronize(s->st));
       s->since_cold = nnsdp_solver::kColdPeriod;   // lockstep: the next batched iteration is a cold one for everybody
       IterArgs a;
@@ -1734,12 +1903,14 @@ struct nnsdp_batch {
       a.z0 = s->D.z0.p; a.Dinv = s->D.Dinv.p; a.c = s->D.c.p; a.Minv = s->Minv.p;
       a.nu = s->nu.p; a.w = s->w.p; a.g = s->g.p; a.p = s->p.p; a.qv = s->qv.p; a.ww = s->ww.p; a.x = s->x.p;
       a.sigma = s->d_sigma(); a.kappa = s->d_kappa(); a.alpha = s->opt.alpha;
-      {
+      if (fused) { a.symv_part = nullptr; gx_fused = std::max(gx_fused, cdiv(a.ng, kFusedCols)); }
+      else {
         const size_t nb = (size_t)(a.ng + 63) / 64;
         if (!s->minv_structured && s->symv_part.n != nb * nb * 64) s->symv_part.alloc(nb * nb * 64);
         a.symv_part = s->symv_part.p;
         gx_tiles = std::max(gx_tiles, cdiv((long long)(nb * (nb + 1) / 2), kThreads / 64));
         gx_nb = std::max(gx_nb, (int)nb);
+        if (!s->minv_structured) it_sym.push_back(a);
       }
       it.push_back(a);
       ProjArgs q{};
@@ -1782,6 +1953,20 @@ struct nnsdp_batch {
       }
     HIPCHK(proj_allow_big_lds(plan));
     d_it.upload(it); d_pw.upload(pw); d_pc.upload(pc); d_map.upload(map);
+    if (!fam.empty()) {
+      std::vector<int> fmem;
+      std::vector<FusedPass> fpass;
+      for (auto& f : fam)
+        for (size_t o = 0; o < f.second.size(); o += kFusedWidth) {
+          const int cnt = (int)std::min<size_t>(kFusedWidth, f.second.size() - o);
+          fpass.push_back(FusedPass{(int)fmem.size(), cnt});
+          fmem.insert(fmem.end(), f.second.begin() + o, f.second.begin() + o + cnt);
+        }
+      n_fgroups = (int)fam.size(); n_fmembers = (int)fmem.size(); n_fpass = (int)fpass.size();
+      n_sym = (int)it_sym.size();
+      d_fmem.upload(fmem); d_fpass.upload(fpass);
+      if (n_sym) d_it_sym.upload(it_sym);
+    }
   }
 
   void enqueue_iteration(bool warm) {
@@ -1791,7 +1976,18 @@ struct nnsdp_batch {
     hipLaunchKernelGGL(k_gather_g_b, dim3(gx_gather + gx_gather_med, B), dim3(kThreads), 0, st, d_it.p, gx_gather);
     hipLaunchKernelGGL(k_spmv_At_b, dim3(std::max(gx_at_s + gx_at_l, 1), B), dim3(kThreads), 0, st, d_it.p, gx_at_s);
     static const bool full_gemv = [] { const char* e = std::getenv("NNSDP_BATCH_FULL_GEMV"); return e && std::atoi(e) != 0; }();   // diagnostic
-    if (any_structured) { for (nnsdp_solver* s : act) s->enqueue_minv(st); }     // large multiplier counts: each SDP's structured M^-1
+    if (n_fpass > 0) {
+      // the batch holds family members: one pass per group over the common inverse; structured members and solvers of no family
+      // take the stage they take without families around (d_it_sym: the dense ones among them)
+      hipLaunchKernelGGL(k_minv_family, dim3(gx_fused, n_fpass), dim3(kThreads), 0, st, d_it.p, d_fmem.p, d_fpass.p);
+      if (any_structured) { for (nnsdp_solver* s : act) if (s->minv_structured || s->family == 0) s->enqueue_minv(st); }
+      else if (n_sym > 0 && full_gemv) hipLaunchKernelGGL(k_gemv_sym_b, dim3(gx_gemv, n_sym), dim3(kThreads), 0, st, d_it_sym.p);
+      else if (n_sym > 0) {
+        hipLaunchKernelGGL(k_symv_tiles_b, dim3(gx_tiles, n_sym), dim3(kThreads), 0, st, d_it_sym.p);
+        hipLaunchKernelGGL(k_symv_reduce_b, dim3(gx_nb, n_sym), dim3(64), 0, st, d_it_sym.p);
+      }
+    }
+    else if (any_structured) { for (nnsdp_solver* s : act) s->enqueue_minv(st); }     // large multiplier counts: each SDP's structured M^-1
     else if (full_gemv) hipLaunchKernelGGL(k_gemv_sym_b, dim3(gx_gemv, B), dim3(kThreads), 0, st, d_it.p);
     else {
       hipLaunchKernelGGL(k_symv_tiles_b, dim3(gx_tiles, B), dim3(kThreads), 0, st, d_it.p);
@@ -1820,6 +2016,7 @@ struct nnsdp_batch {
           HIPCHK(hipGraphInstantiate(&gexec, graph, nullptr, nullptr, 0));
         }
         HIPCHK(hipGraphLaunch(gexec, st));
+        for (nnsdp_solver* s : act) ++s->graph_launches;      // (nnsdp_solver_info 0: the replay advanced every member)
         did = giters;
       } else {
         enqueue_iteration(warm_ok);
@@ -1932,6 +2129,15 @@ int nnsdp_solver_create(const nnsdp_problem* p, const nnsdp_options* o, nnsdp_so
   API_END
 }
 
+int nnsdp_solver_create_sibling(nnsdp_solver* parent, const nnsdp_problem* p, nnsdp_solver** out) {
+  API_BEGIN
+  if (!parent || !p || !out) throw std::invalid_argument("null argument");
+  std::unique_ptr<nnsdp_solver> s(new nnsdp_solver());
+  s->setup_sibling(*parent, p);
+  *out = s.release();
+  API_END
+}
+
 int nnsdp_solver_iterate(nnsdp_solver* s, int32_t iters, double* eig_ms) {
   API_BEGIN
   if (!s) throw std::invalid_argument("null solver");
@@ -1996,6 +2202,48 @@ int nnsdp_solver_apply_minv(nnsdp_solver* s, const double* q, double* out, int32
   API_END
 }
 
+int nnsdp_solver_apply_minv_multi(nnsdp_solver* s, int32_t nrhs, const double* Q, double* out, double* kernel_ms) {
+  API_BEGIN
+  if (!s || !Q || !out) throw std::invalid_argument("null argument");
+  if (nrhs < 1) throw std::invalid_argument("nrhs must be >= 1");
+  if (s->minv_structured) throw std::invalid_argument("the fused multi-vector product needs a dense M^-1 (this handle's is structured)");
+  const int ng = s->S.ng, ldm = s->ldm, full = s->P.ng;
+  // every vector gets an IterArgs slot of its own (what the kernel reads of it: ng, ldm, Minv, qv, ww), as members of a batch have
+  DBuf<double> qd, wd;
+  std::vector<double> qh((size_t)nrhs * ldm, 0.0);
+  for (int j = 0; j < nrhs; ++j)
+    for (int g = 0; g < ng; ++g) qh[(size_t)j * ldm + g] = Q[(size_t)j * full + s->S.keep[g]];
+  qd.upload(qh);
+  wd.alloc((size_t)nrhs * ldm); wd.zero();
+  std::vector<IterArgs> it(nrhs);
+  std::vector<int> mem(nrhs);
+  std::vector<FusedPass> ps;
+  for (int j = 0; j < nrhs; ++j) {
+    std::memset(&it[j], 0, sizeof(IterArgs));
+    it[j].ng = ng; it[j].ldm = ldm; it[j].Minv = s->Minv.p; it[j].qv = qd.p + (size_t)j * ldm; it[j].ww = wd.p + (size_t)j * ldm;
+    mem[j] = j;
+    if (j % kFusedWidth == 0) ps.push_back(FusedPass{j, std::min<int>(kFusedWidth, nrhs - j)});
+  }
+  DBuf<IterArgs> dit; DBuf<int> dmem; DBuf<FusedPass> dps;
+  dit.upload(it); dmem.upload(mem); dps.upload(ps);
+  hipEvent_t e0, e1;
+  HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
+  HIPCHK(hipEventRecord(e0, s->st));
+  hipLaunchKernelGGL(k_minv_family, dim3(cdiv(ng, kFusedCols), (int)ps.size()), dim3(kThreads), 0, s->st, dit.p, dmem.p, dps.p);
+  HIPCHK(hipEventRecord(e1, s->st));
+  const hipError_t le = hipGetLastError(), se = hipStreamSynchronize(s->st);
+  float ms = 0.f;
+  if (le == hipSuccess && se == hipSuccess) (void)hipEventElapsedTime(&ms, e0, e1);
+  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+  HIPCHK(le); HIPCHK(se);
+  if (kernel_ms) *kernel_ms = ms;
+  std::vector<double> o = wd.download();
+  for (size_t i = 0; i < (size_t)nrhs * full; ++i) out[i] = 0.0;
+  for (int j = 0; j < nrhs; ++j)
+    for (int g = 0; g < ng; ++g) out[(size_t)j * full + s->S.keep[g]] = o[(size_t)j * ldm + g];
+  API_END
+}
+
 int nnsdp_solver_raw_multipliers(nnsdp_solver* s, double* out) {
   API_BEGIN
   if (!s || !out) throw std::invalid_argument("null argument");
@@ -2018,6 +2266,8 @@ int nnsdp_solver_info(nnsdp_solver* s, int32_t what, double* out) {
     case 4: *out = (double)s->ncl; break;
     case 5: *out = (double)s->nmax; break;
     case 6: *out = s->ipc ? (s->ipc_fine ? 2.0 : 1.0) : 0.0; break;
+    case 7: *out = (double)s->family; break;
+    case 8: case 9: { size_t own = 0, sh = 0; s->device_bytes(own, sh); *out = (double)(what == 8 ? own : sh); break; }
     default: throw std::invalid_argument("unknown info item");
   }
   API_END
@@ -2433,6 +2683,18 @@ int nnsdp_batch_run(nnsdp_batch* b, int32_t* status) {
   if (!b) throw std::invalid_argument("null batch");
   b->run();
   if (status) for (size_t i = 0; i < b->all.size(); ++i) status[i] = b->status[i];
+  API_END
+}
+
+int nnsdp_batch_info(nnsdp_batch* b, int32_t what, double* out) {
+  API_BEGIN
+  if (!b || !out) throw std::invalid_argument("null argument");
+  switch (what) {
+    case 0: *out = (double)b->act.size(); break;
+    case 1: *out = (double)b->n_fgroups; break;
+    case 2: *out = (double)b->n_fmembers; break;
+    default: throw std::invalid_argument("unknown info item");
+  }
   API_END
 }
 

@@ -2817,6 +2817,76 @@ __global__ __launch_bounds__(64) void k_symv_reduce_b(const IterArgs* __restrict
   if (row < n) a.ww[row] = s;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Solver families (members that share ONE M^-1): ww_b = Minv qv_b for up to kFusedWidth members in one pass over the matrix.
+// A workgroup owns kFusedCols columns of Minv (= rows: it is symmetric) over their whole height, its four waves take the
+// 128-row chunks c = wave, wave + 4, ...: per chunk one 16-byte load per lane and column (kFusedCols independent loads in
+// flight) and one 16-byte load of every member's qv (L2: the vectors of a group are a few hundred KB), then
+// 2 x kFusedCols x nb FMAs.  Both triangles are read: 8 ng ldm bytes per pass whatever nb is (W40-D20: 30.9 MB, ~1970 waves).
+// Per member the arithmetic is a fixed sequence the other members only sit beside - lane partial over the wave's chunks in chunk
+// order (two FMAs per chunk), wave_sum, the four waves' sums added in wave order through LDS - so a member's result depends neither
+// on nb nor on the slot it sits in; no atomics.  Several groups share one launch: blockIdx.y selects the pass.
+// ---------------------------------------------------------------------------------------------
+static constexpr int kFusedWidth = 16;   // members per pass
+static constexpr int kFusedCols = 4;     // columns of Minv per workgroup
+struct FusedPass { int first, count; };  // slots [first, first + count) of the member list
+__global__ __launch_bounds__(kThreads) void k_minv_family(const IterArgs* __restrict__ A, const int* __restrict__ members,
+                                                          const FusedPass* __restrict__ passes) {
+  __shared__ double red[kThreads / 64][kFusedCols][kFusedWidth];
+  const FusedPass ps = passes[blockIdx.y];
+  const int* __restrict__ mem = members + ps.first;
+  const int nb = ps.count;
+  const IterArgs& a0 = A[mem[0]];
+  const int n = a0.ng, ldm = a0.ldm;
+  const int col0 = blockIdx.x * kFusedCols;
+  if (col0 >= n) return;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const double* __restrict__ mc[kFusedCols];
+#pragma unroll
+  for (int r = 0; r < kFusedCols; ++r) mc[r] = a0.Minv + (size_t)min(col0 + r, n - 1) * ldm;   // (a column past the end repeats the last one; not written)
+  const double* __restrict__ q[kFusedWidth];
+#pragma unroll
+  for (int b = 0; b < kFusedWidth; ++b) q[b] = A[mem[b < nb ? b : 0]].qv;
+  double acc[kFusedCols][kFusedWidth];
+#pragma unroll
+  for (int r = 0; r < kFusedCols; ++r)
+#pragma unroll
+    for (int b = 0; b < kFusedWidth; ++b) acc[r][b] = 0.0;
+  for (int j = wv * 128 + lane * 2; j < n; j += (kThreads / 64) * 128) {
+    const bool two = j + 1 < n;
+    double2 m[kFusedCols];
+#pragma unroll
+    for (int r = 0; r < kFusedCols; ++r) {
+      if (two) m[r] = *reinterpret_cast<const double2*>(mc[r] + j);
+      else { m[r].x = mc[r][j]; m[r].y = 0.0; }
+    }
+#pragma unroll
+    for (int b = 0; b < kFusedWidth; ++b) {
+      if (b < nb) {        // (uniform over the workgroup)
+        double2 x;
+        if (two) x = *reinterpret_cast<const double2*>(q[b] + j);
+        else { x.x = q[b][j]; x.y = 0.0; }
+#pragma unroll
+        for (int r = 0; r < kFusedCols; ++r) acc[r][b] = fma(m[r].y, x.y, fma(m[r].x, x.x, acc[r][b]));
+      }
+    }
+  }
+#pragma unroll
+  for (int b = 0; b < kFusedWidth; ++b) {
+    if (b < nb) {
+#pragma unroll
+      for (int r = 0; r < kFusedCols; ++r) {
+        const double s = wave_sum(acc[r][b]);
+        if (lane == 0) red[wv][r][b] = s;
+      }
+    }
+  }
+  __syncthreads();
+  const int r = threadIdx.x / kFusedWidth, b = threadIdx.x % kFusedWidth;
+  if (r < kFusedCols && b < nb && col0 + r < n)
+    A[mem[b]].ww[col0 + r] = ((red[0][r][b] + red[1][r][b]) + red[2][r][b]) + red[3][r][b];
+}
+
 // x[e] = g[e] - Dinv[e] * sum_g A[e,g] ww[g]; 4 lanes per pattern entry (W40-D20: 27.6 k rows, 60 % of them with no
 // multiplier at all and 37 % with one; only 2 880 rows carry more than 16 nonzeros)
 static constexpr int kRowLanes = 8;

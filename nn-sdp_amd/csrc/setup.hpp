@@ -379,6 +379,13 @@ class OperatorBuilder {
     return std::move(op_);
   }
 
+  // z0 alone on the given pattern (svec-scaled, not normalised): all that the output QC and the last affine layer enter.  Throws
+  // like build() when an entry falls outside the pattern.
+  std::vector<double> build_z0_only() {
+    build_z0();
+    return std::move(op_.z0);
+  }
+
  private:
   static SpVec unit(int i) { return SpVec{{i}, {1.0}}; }
   static SpVec diff(const SpVec& a, const SpVec& b) {

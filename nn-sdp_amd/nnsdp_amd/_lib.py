@@ -68,12 +68,14 @@ SYMBOLS = [
     ("nnsdp_problem_dims", C.c_int, [C.POINTER(Problem), c_int32_p, c_int32_p, c_int32_p, c_int32_p]),
     ("nnsdp_solve", C.c_int, [C.POINTER(Problem), C.POINTER(Options), C.POINTER(Result)]),
     ("nnsdp_solver_create", C.c_int, [C.POINTER(Problem), C.POINTER(Options), C.POINTER(C.c_void_p)]),
+    ("nnsdp_solver_create_sibling", C.c_int, [C.c_void_p, C.POINTER(Problem), C.POINTER(C.c_void_p)]),
     ("nnsdp_solver_iterate", C.c_int, [C.c_void_p, C.c_int32, c_double_p]),
     ("nnsdp_solver_advance", C.c_int, [C.c_void_p, C.c_int32]),
     ("nnsdp_solver_iterate_async", C.c_int, [C.c_void_p, C.c_int32]),
     ("nnsdp_solver_sync", C.c_int, [C.c_void_p]),
     ("nnsdp_solver_residuals", C.c_int, [C.c_void_p, c_double_p, c_double_p, c_double_p, c_double_p]),
     ("nnsdp_solver_apply_minv", C.c_int, [C.c_void_p, c_double_p, c_double_p, c_int32_p, C.POINTER(C.c_int64)]),
+    ("nnsdp_solver_apply_minv_multi", C.c_int, [C.c_void_p, C.c_int32, c_double_p, c_double_p, c_double_p]),
     ("nnsdp_solver_raw_multipliers", C.c_int, [C.c_void_p, c_double_p]),
     ("nnsdp_solver_info", C.c_int, [C.c_void_p, C.c_int32, c_double_p]),
     ("nnsdp_solver_run", C.c_int, [C.c_void_p, C.POINTER(Result)]),
@@ -87,6 +89,7 @@ SYMBOLS = [
     ("nnsdp_batch_run", C.c_int, [C.c_void_p, c_int32_p]),
     ("nnsdp_batch_destroy", C.c_int, [C.c_void_p]),
     ("nnsdp_batch_resync", C.c_int, [C.c_void_p]),
+    ("nnsdp_batch_info", C.c_int, [C.c_void_p, C.c_int32, c_double_p]),
     ("nnsdp_solver_finish_status", C.c_int, [C.c_void_p, C.c_int32, C.POINTER(Result)]),
     ("nnsdp_eval_network", C.c_int, [C.c_int32, c_int32_p, c_double_p, C.c_int32, C.c_int64, c_double_p, c_double_p, c_double_p]),
     ("nnsdp_make_intervals", C.c_int, [C.c_int32, c_int32_p, c_double_p, c_double_p, c_double_p] + [c_double_p] * 8),

@@ -241,15 +241,17 @@ def findCircle(net, x1min, x1max, beta: int, opts: M.AdmmSdpOptions):
     return M.runQuery(q, opts)
 
 
-def findReach2Dpoly(net, x1min, x1max, beta: int, opts: M.AdmmSdpOptions, num_hplanes: int = 6, batched: bool = True):
+def findReach2Dpoly(net, x1min, x1max, beta: int, opts: M.AdmmSdpOptions, num_hplanes: int = 6, batched: bool = True,
+                    share_setup: bool = False):
     """NnSdp.findReach2Dpoly (src/NnSdp.jl:73-95): one reach-hyperplane SDP per direction.  The directions share the
     network and the interval pre-processing and are independent SDPs of identical shape: solved in lockstep through
-    the batch handle (`batched=False`: one after the other, as the reference does)."""
+    the batch handle (`batched=False`: one after the other, as the reference does).  share_setup=True (batched only): the
+    directions differ in the hyperplane normal only, so they are created as one solver family - one operator, one M^-1."""
     qc_input = M.QcInputBox(x1min=x1min, x1max=x1max)
     qc_activs = makeQcActivs(net, x1min, x1max, beta)
     normals = [np.array([np.cos(2 * np.pi * i / num_hplanes), np.sin(2 * np.pi * i / num_hplanes)]) for i in range(num_hplanes)]
     queries = [M.ReachQuery(ffnet=net, qc_input=qc_input, qc_reach=M.QcReachHplane(normal=nrm), qc_activs=qc_activs) for nrm in normals]
-    solns = M.runQueries(queries, opts) if batched and len(queries) > 1 else [M.runQuery(q, opts) for q in queries]
+    solns = M.runQueries(queries, opts, share_setup=share_setup) if batched and len(queries) > 1 else [M.runQuery(q, opts) for q in queries]
     return [(nrm, s.objective_value) for nrm, s in zip(normals, solns)], solns
 
 

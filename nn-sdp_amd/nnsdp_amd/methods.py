@@ -408,13 +408,35 @@ solveQuery = runQuery   # NnSdp.solveQuery (src/NnSdp.jl:25-29)
 class Solver:
     """Handle form (nnsdp_solver_*): lets a caller time exactly K iterations (bench.py)."""
 
-    def __init__(self, query, opts: AdmmSdpOptions):
+    def __init__(self, query, opts: AdmmSdpOptions, _parent: "Optional[Solver]" = None):
         self.lib = _lib.load()
         self.query = query
         self.cp = _CProblem(query)
-        self.o = opts.to_c()
         self.h = C.c_void_p()
-        _lib.check(self.lib.nnsdp_solver_create(C.byref(self.cp.p), C.byref(self.o), C.byref(self.h)))
+        if _parent is None:
+            self.o = opts.to_c()
+            _lib.check(self.lib.nnsdp_solver_create(C.byref(self.cp.p), C.byref(self.o), C.byref(self.h)))
+        else:
+            self.o = _parent.o
+            _lib.check(self.lib.nnsdp_solver_create_sibling(_parent.h, C.byref(self.cp.p), C.byref(self.h)))
+
+    def sibling(self, query) -> "Solver":
+        """A solver for `query` that shares this one's set-up (operator, tables, M^-1) by reference count: `query` may differ from
+        this solver's in the output QC (normal / S / yc, invP) and the last affine layer only (same_family); options are this
+        solver's.  Either may be closed first.  NnsdpError (code -1, naming the field) when the query does not belong."""
+        return Solver(query, None, _parent=self)
+
+    def apply_minv_multi(self, Q):
+        """(M^-1 Q, kernel milliseconds) for Q of shape (nrhs, ngamma) through the fused multi-vector kernel a family uses inside a
+        batch (dense M^-1 only; test entry)."""
+        Q = np.atleast_2d(_f64(Q))
+        if Q.shape[1] != self.cp.ngamma:
+            raise ValueError("Q must have one column per multiplier")
+        out = np.zeros_like(Q)
+        ms = C.c_double()
+        _lib.check(self.lib.nnsdp_solver_apply_minv_multi(self.h, int(Q.shape[0]), Q.ctypes.data_as(_lib.c_double_p),
+                                                          out.ctypes.data_as(_lib.c_double_p), C.byref(ms)))
+        return out, ms.value
 
     def iterate(self, iters: int, time_eig: bool = False) -> float:
         ms = C.c_double(0.0)
@@ -482,7 +504,9 @@ class Solver:
         return out
 
     def info(self, what: int) -> float:
-        """nnsdp_solver_info: 0 hipGraph launches, 1 RCCL all-reduce capturable into a hipGraph, 2 sharded, 3 iterations, 4 blocks, 5 largest block, 6 hipIpc transport (2 = fine-grained exchange buffers)"""
+        """nnsdp_solver_info: 0 hipGraph launches, 1 RCCL all-reduce capturable into a hipGraph, 2 sharded, 3 iterations, 4 blocks, 5 largest block, 6 hipIpc transport (2 = fine-grained exchange buffers),
+        7 family id (0: shares nothing; equal for the members of one family), 8 device bytes this handle owns alone, 9 device bytes it
+        shares with other members of its family"""
         v = C.c_double()
         _lib.check(self.lib.nnsdp_solver_info(self.h, int(what), C.byref(v)))
         return v.value
@@ -547,11 +571,29 @@ class SolverBatch:
         optl = list(opts) if isinstance(opts, (list, tuple)) else [opts] * len(queries)
         if len(optl) != len(queries):
             raise ValueError("one options object per query (or a single one for all)")
-        self.solvers = [Solver(q, o) for q, o in zip(queries, optl)]
+        self._own = True
+        self._open([Solver(q, o) for q, o in zip(queries, optl)])
+
+    def _open(self, solvers) -> None:
+        self.solvers = list(solvers)
         self.lib = _lib.load()
         self.h = C.c_void_p()
         hs = (C.c_void_p * len(self.solvers))(*[s.h for s in self.solvers])
         _lib.check(self.lib.nnsdp_batch_create(hs, len(self.solvers), C.byref(self.h)))
+
+    @classmethod
+    def from_solvers(cls, solvers, own: bool = False) -> "SolverBatch":
+        """a batch over existing Solver objects (e.g. some members of a family); own=False: close() leaves them open"""
+        sb = cls.__new__(cls)
+        sb._own = own
+        sb._open(solvers)
+        return sb
+
+    def batch_info(self, what: int) -> float:
+        """nnsdp_batch_info: 0 members still active, 1 fused family groups in the current launch tables, 2 members they cover"""
+        v = C.c_double()
+        _lib.check(self.lib.nnsdp_batch_info(self.h, int(what), C.byref(v)))
+        return v.value
 
     def _resync(self) -> None:
         _lib.check(self.lib.nnsdp_batch_resync(self.h))
@@ -600,8 +642,9 @@ class SolverBatch:
         if self.h:
             self.lib.nnsdp_batch_destroy(self.h)
             self.h = C.c_void_p()
-        for s in self.solvers:
-            s.close()
+        if getattr(self, "_own", True):
+            for s in getattr(self, "solvers", []):
+                s.close()
 
     def __del__(self):
         try:
@@ -610,9 +653,92 @@ class SolverBatch:
             pass
 
 
-def runQueries(queries, opts) -> List[QuerySolution]:
-    """runQuery for several independent queries at once (batch handle); results in the order of the queries."""
-    sb = SolverBatch(queries, opts)
+def _out_qc(query):
+    return query.qc_reach if isinstance(query, ReachQuery) else query.qc_safety
+
+
+def same_family(q0, q1) -> bool:
+    """Can q0 and q1 share one solver set-up (Solver.sibling)?  True when they differ in the output data only - normal / S / yc,
+    invP and the last affine layer, which enter the constant term z0 and nothing else: same kind of query and of output QC (circle
+    and ellipsoid count as one kind), same
+    network up to the last layer, input box, intervals, sector bounds, beta and activation.  Host only: needs no GPU."""
+    def kind(q):      # (circle and ellipsoid: the same gout generator, hence one kind; the hyperplane's differs)
+        t = type(_out_qc(q))
+        return QcReachCircle if t is QcReachEllipsoid else t
+    if type(q0) is not type(q1) or kind(q0) is not kind(q1):
+        return False
+    n0, n1 = q0.ffnet, q1.ffnet
+    if n0.xdims != n1.xdims or _activ_code(n0.activ) != _activ_code(n1.activ):
+        return False
+    if not all(np.array_equal(a, b) for a, b in zip(n0.Ms[:-1], n1.Ms[:-1])):
+        return False
+    if not (np.array_equal(q0.qc_input.x1min, q1.qc_input.x1min) and np.array_equal(q0.qc_input.x1max, q1.qc_input.x1max)):
+        return False
+    for cls, names in ((QcActivBounded, ("acymin", "acymax")), (QcActivSector, ("smin", "smax", "beta", "acxdim"))):
+        a = [q for q in q0.qc_activs if isinstance(q, cls)]
+        b = [q for q in q1.qc_activs if isinstance(q, cls)]
+        if len(a) != 1 or len(b) != 1:
+            return False
+        if not all(np.array_equal(getattr(a[0], n), getattr(b[0], n)) for n in names):
+            return False
+        if cls is QcActivSector and _activ_code(a[0].activ) != _activ_code(b[0].activ):
+            return False
+    return True
+
+
+class SolverFamily(SolverBatch):
+    """A SolverBatch whose solvers share ONE set-up: the first is created normally, the others as its siblings (Solver.sibling), so
+    the operator, the tables and M^-1 exist once on the device and the batch applies a dense M^-1 to all members in one pass over
+    the matrix.  Every query must satisfy same_family with the first; the library raises NnsdpError otherwise."""
+
+    def __init__(self, queries, opts: AdmmSdpOptions):
+        queries = list(queries)
+        if not queries:
+            raise ValueError("a family needs at least one query")
+        self._own = True
+        solvers = [Solver(queries[0], opts)]
+        try:
+            for q in queries[1:]:
+                solvers.append(solvers[0].sibling(q))
+            self._open(solvers)
+        except Exception:
+            for s in solvers:
+                s.close()
+            raise
+
+
+def _shared_solvers(queries, optl) -> List[Solver]:
+    """one Solver per query; queries that form a family (same_family, identical options) share the set-up of its first member"""
+    solvers: List[Optional[Solver]] = [None] * len(queries)
+    heads: List[int] = []
+    try:
+        for i, (q, o) in enumerate(zip(queries, optl)):
+            head = next((h for h in heads if bytes(optl[h].to_c()) == bytes(o.to_c()) and same_family(queries[h], q)), None)
+            if head is None:
+                heads.append(i)
+                solvers[i] = Solver(q, o)
+            else:
+                solvers[i] = solvers[head].sibling(q)
+    except Exception:
+        for s in solvers:
+            if s is not None:
+                s.close()
+        raise
+    return solvers
+
+
+def runQueries(queries, opts, share_setup: bool = False) -> List[QuerySolution]:
+    """runQuery for several independent queries at once (batch handle); results in the order of the queries.
+    share_setup=True: queries that differ in the output QC only (same_family) are created as one solver family - one set-up and one
+    M^-1 for all of them; the others run beside them in the same batch."""
+    if share_setup:
+        queries = list(queries)
+        optl = list(opts) if isinstance(opts, (list, tuple)) else [opts] * len(queries)
+        if len(optl) != len(queries):
+            raise ValueError("one options object per query (or a single one for all)")
+        sb = SolverBatch.from_solvers(_shared_solvers(queries, optl), own=True)
+    else:
+        sb = SolverBatch(queries, opts)
     try:
         return sb.run()
     finally:

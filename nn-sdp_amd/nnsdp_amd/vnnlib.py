@@ -294,11 +294,13 @@ def safetyFromReach(soln: M.QuerySolution, h: float, h0: float = 0.0) -> M.Query
 
 def verifyAcasSpec(net: M.FeedFwdNet, spec, beta: int, opts: M.AdmmSdpOptions,
                    solve: Callable[[Any, M.AdmmSdpOptions], M.QuerySolution] = None, log: Callable[[str], None] = None,
-                   batch_clause: bool = False, via_reach: bool = False):
+                   batch_clause: bool = False, via_reach: bool = False, share_setup: bool = False):
     """Goes through the conjunction; a clause holds as soon as one of its sub-queries is certified, the spec fails as
     soon as a clause has none (experiments/acas.jl:87-137).  -> (solutions tried, number of queries, status).
     batch_clause: the sub-queries of a clause are independent SDPs on one network - solve them in lockstep through the
     batch handle (runQueries) instead of one after the other; every literal of a tried clause then counts as run.
+    share_setup (with batch_clause): the literals of a clause differ in the safety set - in the reach form: in the normal and the
+    shifted output bias - only, so they are created as one solver family (one set-up, one M^-1).
     via_reach: True = decide every literal through the equivalent reach-hyperplane query (reachForm / safetyFromReach);
     "auto" = first give the feasibility form 500 iterations per literal (failed attempts are not recorded).  The
     feasibility form 'min sum(gamma)' of the reference needs an interior-point solver to FAIL quickly; the reach form
@@ -326,7 +328,7 @@ def verifyAcasSpec(net: M.FeedFwdNet, spec, beta: int, opts: M.AdmmSdpOptions,
                 continue
         forms = [reachForm(q) for q in clause] if via_reach else [(q, None, None) for q in clause]
         if batch_clause and len(clause) > 1:
-            got = M.runQueries([f[0] for f in forms], opts)
+            got = M.runQueries([f[0] for f in forms], opts, share_setup=share_setup)
             got = [safetyFromReach(s, f[1], f[2]) if via_reach else s for s, f in zip(got, forms)]
             solns.extend(got)
             holds = any(isSolutionGood(s) for s in got)
@@ -356,12 +358,12 @@ QUERY_COLUMNS = ["acas", "spec", "qnum", "num_queries", "time", "status", "eigma
 
 
 def verifyPairs(pairs: Sequence[Tuple[str, M.FeedFwdNet, str, Any]], beta: int, opts: M.AdmmSdpOptions, saveto: str = None,
-                solve=None, log=None, batch_clause: bool = False, via_reach: bool = False):
+                solve=None, log=None, batch_clause: bool = False, via_reach: bool = False, share_setup: bool = False):
     """pairs: (network name, network, spec name, spec path or text).  Writes the reference's two tables
     (experiments/acas.jl:146-185): `saveto` and `saveto + "-qdf.csv"`, re-saved after every pair."""
     rows, qrows = [], []
     for name, net, sname, spec in pairs:
-        solns, nq, status = verifyAcasSpec(net, spec, beta, opts, solve=solve, log=log, batch_clause=batch_clause, via_reach=via_reach)
+        solns, nq, status = verifyAcasSpec(net, spec, beta, opts, solve=solve, log=log, batch_clause=batch_clause, via_reach=via_reach, share_setup=share_setup)
         good = [s for s in solns if isSolutionGood(s)]
         avg = sum(s.total_time for s in good) / len(good) if good else float("inf")
         rows.append([name, sname, status, nq, len(solns), avg, sum(s.total_time for s in solns)])
