@@ -189,6 +189,12 @@ int nnsdp_solver_create(const nnsdp_problem* p, const nnsdp_options* o, nnsdp_so
  * tables, the row and column class lists, the block lists, and M^-1 (dense, or the structured factors).  Any member, the parent
  * included, may be destroyed first.  Inside a batch handle the members of a family whose M^-1 is dense are served by ONE pass over
  * the matrix per 16 members (always, also a member alone in its batch: the stage's bits do not depend on who else is there);
+ * members of a family whose M^-1 is structured are served by the four stages of the structured form ONCE per 8 members (four
+ * launches for all such groups of the batch; a lane loads each piece of the shared factors once and uses it for every member), with
+ * every member's result bit-identical to its own single-solver stage - so a member alone in its batch simply keeps the
+ * single-solver launches (as does a family of which ONE chunk slice or separator vector exceeds a CU's LDS: a chunk above 8 192
+ * multipliers, a separator above 20 480).  NNSDP_FAMILY_STRUCT=0 (diagnostic, read once) keeps
+ * them for every member.
  * nnsdp_solver_iterate / _run on a member outside a batch use the single-solver stage like any solver. */
 int nnsdp_solver_create_sibling(nnsdp_solver* parent, const nnsdp_problem* p, nnsdp_solver** out);
 /* run `iters` ADMM iterations (no convergence test); eig_ms (may be NULL) receives the HIP-event
@@ -214,6 +220,10 @@ int nnsdp_solver_apply_minv(nnsdp_solver* s, const double* q, double* out, int32
  * (-1 for a handle whose M^-1 is structured).  Vector j of a call equals a one-vector call on the same vector bit for bit.
  * kernel_ms (may be NULL) receives the HIP-event time of the launch. */
 int nnsdp_solver_apply_minv_multi(nnsdp_solver* s, int32_t nrhs, const double* Q, double* out, double* kernel_ms);
+/* the same for a handle whose M^-1 is structured: runs the fused structured stages of the solver families on the handle's factors, 8
+ * vectors per pass, all passes in the same four launches (-1 with a message for a handle whose M^-1 is dense).  Vector j equals nnsdp_solver_apply_minv on the same vector bit for bit, whatever nrhs and j.
+ * kernel_ms (may be NULL) receives the HIP-event time of the four launches. */
+int nnsdp_solver_apply_minv_structured_multi(nnsdp_solver* s, int32_t nrhs, const double* Q, double* out, double* kernel_ms);
 /* test / diagnostic entry: the multiplier block of the solver's fixed-point variable nu (solver coordinates and scaling), one
  * entry per multiplier of the problem (dropped multipliers 0).  In clique-sharded mode this block is replicated; the two-rank
  * test compares it bit for bit between ranks. */
@@ -222,7 +232,9 @@ int nnsdp_solver_raw_multipliers(nnsdp_solver* s, double* out);
  * 2 clique-sharded mode on, 3 iterations done, 4 PSD blocks, 5 largest block, 6 the hipIpc transport (0 off, 1 on with ordinary device
  * memory behind the exchange buffers, 2 on with fine-grained device memory - the default), 7 family id (0 for a solver that shares
  * nothing, otherwise equal for all members of a family and distinct between the families of a process), 8 bytes of device memory this
- * handle owns exclusively, 9 bytes it shares with other members of its family (buffers with more than one holder) */
+ * handle owns exclusively, 9 bytes it shares with other members of its family (buffers with more than one holder), 10 chunks of the
+ * structured M^-1 plan (0: dense), 11 how many of them start at an odd multiplier or an odd separator column (these take the
+ * scalar-load paths of the structured stages) */
 int nnsdp_solver_info(nnsdp_solver* s, int32_t what, double* out);
 /* iterate until converged / limits; fills r like nnsdp_solve */
 int nnsdp_solver_run(nnsdp_solver* s, nnsdp_result* r);
@@ -245,7 +257,8 @@ int nnsdp_batch_destroy(nnsdp_batch* b);
 /* re-establish lockstep after members of the batch were advanced individually (nnsdp_solver_residuals / _iterate / _advance):
  * the next batched iteration is a cold one for every member and the launch tables are rebuilt */
 int nnsdp_batch_resync(nnsdp_batch* b);
-/* diagnostic: what = 0 members still active, 1 fused family groups in the current launch tables, 2 members covered by them */
+/* diagnostic: what = 0 members still active, 1 fused family groups with a dense M^-1 in the current launch tables, 2 members covered
+ * by them, 3 fused family groups with a structured M^-1, 4 members covered by those */
 int nnsdp_batch_info(nnsdp_batch* b, int32_t what, double* out);
 /* result of a solver that stopped with `status` (as returned by nnsdp_batch_run): certificate polish, gamma, Z */
 int nnsdp_solver_finish_status(nnsdp_solver* s, int32_t status, nnsdp_result* r);

@@ -741,7 +741,8 @@ struct nnsdp_solver {
     minv_structured = o.minv_structured;
     if (!minv_structured) Minv.share(o.Minv);
     else {
-      mplan = o.mplan; m_nslots = o.m_nslots;
+      mplan = o.mplan; m_nslots = o.m_nslots; m_ntiles3 = o.m_ntiles3; m_ntiles_sep = o.m_ntiles_sep;
+      m_tiles.share(o.m_tiles);
       m_clo.share(o.m_clo); m_chi.share(o.m_chi); m_w0.share(o.m_w0); m_w1.share(o.m_w1); m_hslot0.share(o.m_hslot0);
       m_chunk_of.share(o.m_chunk_of); m_sep_of.share(o.m_sep_of); m_sep_gen.share(o.m_sep_gen); m_slot_chunk.share(o.m_slot_chunk);
       m_slotA.share(o.m_slotA); m_slotB.share(o.m_slotB); m_poff.share(o.m_poff); m_hoff.share(o.m_hoff);
@@ -762,7 +763,7 @@ struct nnsdp_solver {
     NNSDP_B(Vg) NNSDP_B(x) NNSDP_B(g) NNSDP_B(p) NNSDP_B(qv) NNSDP_B(ww) NNSDP_B(Minv) NNSDP_B(scal) NNSDP_B(acc) NNSDP_B(gs) NNSDP_B(accp)
     NNSDP_B(m_clo) NNSDP_B(m_chi) NNSDP_B(m_w0) NNSDP_B(m_w1) NNSDP_B(m_hslot0) NNSDP_B(m_chunk_of) NNSDP_B(m_sep_of) NNSDP_B(m_sep_gen)
     NNSDP_B(m_slot_chunk) NNSDP_B(m_slotA) NNSDP_B(m_slotB) NNSDP_B(m_poff) NNSDP_B(m_hoff) NNSDP_B(m_P) NNSDP_B(m_H) NNSDP_B(m_HT) NNSDP_B(m_Sc)
-    NNSDP_B(m_v) NNSDP_B(m_kap) NNSDP_B(m_t) NNSDP_B(m_rpart) NNSDP_B(m_rvec) NNSDP_B(m_xS) NNSDP_B(m_coef) NNSDP_B(m_dpart) NNSDP_B(symv_part)
+    NNSDP_B(m_v) NNSDP_B(m_kap) NNSDP_B(m_t) NNSDP_B(m_rpart) NNSDP_B(m_rvec) NNSDP_B(m_xS) NNSDP_B(m_coef) NNSDP_B(m_dpart) NNSDP_B(m_tiles) NNSDP_B(symv_part)
     NNSDP_B(split.B) NNSDP_B(split.ack) NNSDP_B(split.seen) NNSDP_B(split.xcc) NNSDP_B(split.err)
 #undef NNSDP_B
   }
@@ -882,6 +883,12 @@ struct nnsdp_solver {
     m_v.alloc((size_t)ng * std::max(Q.r, 1)); m_kap.alloc(64);
     m_v.zero(); m_kap.zero();
     m_nslots = nslots;
+    {      // row tiles of the multi-vector stages (minv.hpp): the stage-3 tiles (chunk rows, separators) come first
+      const std::vector<int4> tiles = minv_tiles(Q, hslot0);
+      m_ntiles3 = m_ntiles_sep = 0;
+      for (const int4& t : tiles) { if (t.x == kTileP || t.x == kTileSep) ++m_ntiles3; if (t.x == kTileSep) ++m_ntiles_sep; }
+      m_tiles.upload(tiles);
+    }
     bind_minv_dev(0);
     // low-rank part: v = T^-1 U (the structured apply with r = 0), kap = (diag(1/d) + U'v)^-1 on the host (r x r, r <= 8)
     if (Q.r > 0) {
@@ -919,7 +926,9 @@ struct nnsdp_solver {
 
   // scratch of one SDP's applications of the structured M^-1 and the device view of the (possibly shared) factors; r = rank of the
   // low-rank term in use
-  int m_nslots = 0;
+  int m_nslots = 0, m_ntiles3 = 0, m_ntiles_sep = 0;
+  DBuf<int4> m_tiles;
+  MinvMultiLds m_lds;                   // what the multi-vector stages put in LDS for these factors; !ok: ONE vector does not fit, single form only
   void bind_minv_dev(int r) {
     const MinvPlan& Q = mplan;
     const int ng = S.ng, nS = Q.nS, ldS = Q.ldS;
@@ -931,6 +940,9 @@ struct nnsdp_solver {
     mdev.poff = m_poff.p; mdev.hoff = m_hoff.p; mdev.chunk_of = m_chunk_of.p; mdev.sep_of = m_sep_of.p; mdev.sep_gen = m_sep_gen.p;
     mdev.slot_chunk = m_slot_chunk.p; mdev.slotA = m_slotA.p; mdev.slotB = m_slotB.p;
     mdev.Pinv = m_P.p; mdev.H = m_H.p; mdev.HT = m_HT.p; mdev.Scinv = m_Sc.p; mdev.v = m_v.p; mdev.kap = m_kap.p;
+    mdev.tiles = m_tiles.p; mdev.ntiles = (int)m_tiles.n; mdev.ntiles3 = m_ntiles3; mdev.ntiles_sep = m_ntiles_sep;
+    mdev.q = nullptr; mdev.out = nullptr;      // (set where a work table is built: structured_work)
+    m_lds = minv_multi_lds(Q);
     mdev.t = m_t.p; mdev.rpart = m_rpart.p; mdev.rvec = m_rvec.p; mdev.xS = m_xS.p; mdev.coef = m_coef.p; mdev.dpart = m_dpart.p;
   }
 
@@ -941,6 +953,13 @@ struct nnsdp_solver {
     hipLaunchKernelGGL(k_minv_resid, dim3(cdiv(mdev.nS, kThreads) + 1), dim3(kThreads), 0, s_, mdev, q);
     hipLaunchKernelGGL(k_minv_schur, dim3(cdiv((long long)mdev.nS * 64, kThreads)), dim3(kThreads), 0, s_, mdev);
     hipLaunchKernelGGL(k_minv_stage3, dim3(cdiv((long long)ng * 64, kThreads)), dim3(kThreads), 0, s_, mdev, out);
+  }
+
+  // this solver's row of a multi-vector work table: its own work buffers, out = M^-1 q
+  MinvWork structured_work(const double* q, double* out) const {
+    MinvWork w = mdev;
+    w.q = q; w.out = out;
+    return w;
   }
 
   // ww = M^-1 qv on stream s_ (dense GEMV or the structured form)
@@ -1835,6 +1854,15 @@ struct nnsdp_batch {
   DBuf<int> d_fmem;
   DBuf<FusedPass> d_fpass;
   int n_sym = 0, n_fgroups = 0, n_fmembers = 0, n_fpass = 0, gx_fused = 0;
+  // members of a solver family with a structured inverse: the four stages of minv.hpp once per kMinvWidth members of a group
+  // (k_minv_*_multi) instead of four launches per member.  A group of one keeps its member's own launches (equal bits); so does a
+  // group whose factors are too large to stage in LDS, and every group under NNSDP_FAMILY_STRUCT=0 (diagnostic).
+  DBuf<MinvFactors> d_sfac;
+  DBuf<MinvWork> d_swork;
+  DBuf<MinvPass> d_spass;
+  MinvMultiGrid sgrid;
+  int n_sgroups = 0, n_smembers = 0, n_spass = 0;
+  std::vector<nnsdp_solver*> struct_single;      // structured members that take their own four launches, in batch order
   int nblocks = 0, nmax = 0;
   bool any_structured = false, any_big = false;
   ProjPlan plan;
@@ -1873,6 +1901,7 @@ struct nnsdp_batch {
     if (gexec) { (void)hipGraphExecDestroy(gexec); gexec = nullptr; }
     if (graph) { (void)hipGraphDestroy(graph); graph = nullptr; }
     n_sym = n_fgroups = n_fmembers = n_fpass = gx_fused = 0;
+    n_sgroups = n_smembers = n_spass = 0; sgrid = MinvMultiGrid(); struct_single.clear();
     if (act.empty()) return;
     std::vector<IterArgs> it;
     std::vector<ProjArgs> pw, pc;
@@ -1881,6 +1910,8 @@ struct nnsdp_batch {
     any_structured = false; any_big = false;
     std::vector<IterArgs> it_sym;
     std::vector<std::pair<int, std::vector<int>>> fam;      // family id -> its dense members here, in batch order
+    std::vector<std::pair<int, std::vector<int>>> sfam;     // family id -> its structured members here, in batch order
+    static const bool fuse_struct = [] { const char* e = std::getenv("NNSDP_FAMILY_STRUCT"); return !(e && std::atoi(e) == 0); }();   // diagnostic: 0 keeps the per-member launches
     for (size_t b = 0; b < act.size(); ++b) {
       nnsdp_solver* s = act[b];
       any_structured = any_structured || s->minv_structured;
@@ -1888,6 +1919,11 @@ struct nnsdp_batch {
       if (fused) {
         auto f = std::find_if(fam.begin(), fam.end(), [&](const std::pair<int, std::vector<int>>& x) { return x.first == s->family; });
         if (f == fam.end()) { fam.emplace_back(s->family, std::vector<int>()); f = fam.end() - 1; }
+        f->second.push_back((int)b);
+      }
+      if (s->minv_structured && s->family != 0 && s->m_lds.ok && fuse_struct) {
+        auto f = std::find_if(sfam.begin(), sfam.end(), [&](const std::pair<int, std::vector<int>>& x) { return x.first == s->family; });
+        if (f == sfam.end()) { sfam.emplace_back(s->family, std::vector<int>()); f = sfam.end() - 1; }
         f->second.push_back((int)b);
       }
       HIPCHK(hipStreamSynchronize(s->st));
@@ -1953,6 +1989,27 @@ struct nnsdp_batch {
       }
     HIPCHK(proj_allow_big_lds(plan));
     d_it.upload(it); d_pw.upload(pw); d_pc.upload(pc); d_map.upload(map);
+    {
+      std::vector<MinvFactors> sfac;
+      std::vector<MinvWork> swork;
+      std::vector<MinvPass> spass;
+      std::vector<char> in_group(act.size(), 0);
+      for (auto& f : sfam) {
+        if (f.second.size() < 2) continue;      // a group of one: the member's own launches
+        nnsdp_solver* head = act[f.second[0]];
+        sgrid.add(head->mdev, head->m_lds, (int)std::min<size_t>(kMinvWidth, f.second.size()));
+        for (size_t o = 0; o < f.second.size(); o += kMinvWidth) {
+          const int cnt = (int)std::min<size_t>(kMinvWidth, f.second.size() - o);
+          spass.push_back(MinvPass{(int)sfac.size(), (int)swork.size(), cnt});
+          for (int i = 0; i < cnt; ++i) { nnsdp_solver* s = act[f.second[o + i]]; swork.push_back(s->structured_work(s->qv.p, s->ww.p)); in_group[f.second[o + i]] = 1; }
+        }
+        sfac.push_back(head->mdev);
+        ++n_sgroups;
+      }
+      for (size_t b = 0; b < act.size(); ++b) if (act[b]->minv_structured && !in_group[b]) struct_single.push_back(act[b]);
+      n_smembers = (int)swork.size(); n_spass = (int)spass.size();
+      if (n_spass) { d_sfac.upload(sfac); d_swork.upload(swork); d_spass.upload(spass); HIPCHK(minv_multi_allow_lds()); }
+    }
     if (!fam.empty()) {
       std::vector<int> fmem;
       std::vector<FusedPass> fpass;
@@ -1969,6 +2026,12 @@ struct nnsdp_batch {
     }
   }
 
+  // the structured members: four launches for all fused groups together, then the members outside a group
+  void enqueue_structured() {
+    if (n_spass > 0) launch_minv_multi(sgrid, d_sfac.p, d_swork.p, d_spass.p, n_spass, st);
+    for (nnsdp_solver* s : struct_single) s->enqueue_minv(st);
+  }
+
   void enqueue_iteration(bool warm) {
     const int B = (int)act.size();
     if (nblocks > 0) launch_proj_batched(plan, warm ? d_pw.p : d_pc.p, d_map.p, nblocks, st);
@@ -1980,14 +2043,14 @@ struct nnsdp_batch {
       // the batch holds family members: one pass per group over the common inverse; structured members and solvers of no family
       // take the stage they take without families around (d_it_sym: the dense ones among them)
       hipLaunchKernelGGL(k_minv_family, dim3(gx_fused, n_fpass), dim3(kThreads), 0, st, d_it.p, d_fmem.p, d_fpass.p);
-      if (any_structured) { for (nnsdp_solver* s : act) if (s->minv_structured || s->family == 0) s->enqueue_minv(st); }
+      if (any_structured) { enqueue_structured(); for (nnsdp_solver* s : act) if (!s->minv_structured && s->family == 0) s->enqueue_minv(st); }
       else if (n_sym > 0 && full_gemv) hipLaunchKernelGGL(k_gemv_sym_b, dim3(gx_gemv, n_sym), dim3(kThreads), 0, st, d_it_sym.p);
       else if (n_sym > 0) {
         hipLaunchKernelGGL(k_symv_tiles_b, dim3(gx_tiles, n_sym), dim3(kThreads), 0, st, d_it_sym.p);
         hipLaunchKernelGGL(k_symv_reduce_b, dim3(gx_nb, n_sym), dim3(64), 0, st, d_it_sym.p);
       }
     }
-    else if (any_structured) { for (nnsdp_solver* s : act) s->enqueue_minv(st); }     // large multiplier counts: each SDP's structured M^-1
+    else if (any_structured) { enqueue_structured(); for (nnsdp_solver* s : act) if (!s->minv_structured) s->enqueue_minv(st); }     // large multiplier counts: each SDP's structured M^-1
     else if (full_gemv) hipLaunchKernelGGL(k_gemv_sym_b, dim3(gx_gemv, B), dim3(kThreads), 0, st, d_it.p);
     else {
       hipLaunchKernelGGL(k_symv_tiles_b, dim3(gx_tiles, B), dim3(kThreads), 0, st, d_it.p);
@@ -2244,6 +2307,63 @@ int nnsdp_solver_apply_minv_multi(nnsdp_solver* s, int32_t nrhs, const double* Q
   API_END
 }
 
+int nnsdp_solver_apply_minv_structured_multi(nnsdp_solver* s, int32_t nrhs, const double* Q, double* out, double* kernel_ms) {
+  API_BEGIN
+  if (!s || !Q || !out) throw std::invalid_argument("null argument");
+  if (nrhs < 1) throw std::invalid_argument("nrhs must be >= 1");
+  if (!s->minv_structured) throw std::invalid_argument("the fused structured stages need a structured M^-1 (this handle's is dense)");
+  auto even = [](size_t v) { return (v + 1) & ~(size_t)1; };      // (16-byte aligned pieces: the stages load vectors in pairs)
+  const int ng = s->S.ng, full = s->P.ng;
+  const size_t eg = even(ng), eS = even(std::max(s->mplan.ldS, 2)), esl = even(std::max(s->m_nslots, 1));
+  // every vector gets work buffers of its own, as the members of a family have
+  const size_t per = 3 * eg + esl + 2 * eS + 8 + 8 * kMinvParts;
+  DBuf<double> buf;
+  buf.alloc(per * nrhs); buf.zero();
+  std::vector<double> qh(per * nrhs, 0.0);
+  for (int j = 0; j < nrhs; ++j)
+    for (int g = 0; g < ng; ++g) qh[per * j + g] = Q[(size_t)j * full + s->S.keep[g]];
+  HIPCHK(hipMemcpy(buf.p, qh.data(), qh.size() * sizeof(double), hipMemcpyHostToDevice));
+  std::vector<MinvWork> wk(nrhs);
+  std::vector<MinvPass> ps;
+  for (int j = 0; j < nrhs; ++j) {
+    double* b = buf.p + per * j;
+    wk[j].q = b; wk[j].out = b + eg; wk[j].t = b + 2 * eg; b += 3 * eg;
+    wk[j].rpart = b; b += esl;
+    wk[j].rvec = b; wk[j].xS = b + eS; b += 2 * eS;
+    wk[j].coef = b; wk[j].dpart = b + 8;
+    if (j % kMinvWidth == 0) ps.push_back(MinvPass{0, j, std::min<int>(kMinvWidth, nrhs - j)});
+  }
+  struct Events {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    ~Events() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
+  } ev;
+  HIPCHK(hipEventCreate(&ev.e0)); HIPCHK(hipEventCreate(&ev.e1));
+  DBuf<MinvFactors> dfac; DBuf<MinvWork> dwk; DBuf<MinvPass> dps;
+  if (s->m_lds.ok) {
+    std::vector<MinvFactors> fc(1, s->mdev);
+    dfac.upload(fc); dwk.upload(wk); dps.upload(ps);
+    MinvMultiGrid G;
+    G.add(s->mdev, s->m_lds, std::min<int>(kMinvWidth, nrhs));
+    HIPCHK(minv_multi_allow_lds());
+    HIPCHK(hipEventRecord(ev.e0, s->st));
+    launch_minv_multi(G, dfac.p, dwk.p, dps.p, (int)ps.size(), s->st);
+  } else {      // one vector of these factors does not fit in LDS: the single form per vector (the same bits)
+    HIPCHK(hipEventRecord(ev.e0, s->st));
+    for (int j = 0; j < nrhs; ++j) s->apply_structured_minv(wk[j].q, wk[j].out, s->st);
+  }
+  HIPCHK(hipEventRecord(ev.e1, s->st));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(s->st));
+  float ms = 0.f;
+  (void)hipEventElapsedTime(&ms, ev.e0, ev.e1);
+  if (kernel_ms) *kernel_ms = ms;
+  std::vector<double> o = buf.download();
+  for (size_t i = 0; i < (size_t)nrhs * full; ++i) out[i] = 0.0;
+  for (int j = 0; j < nrhs; ++j)
+    for (int g = 0; g < ng; ++g) out[(size_t)j * full + s->S.keep[g]] = o[per * j + eg + g];
+  API_END
+}
+
 int nnsdp_solver_raw_multipliers(nnsdp_solver* s, double* out) {
   API_BEGIN
   if (!s || !out) throw std::invalid_argument("null argument");
@@ -2267,6 +2387,13 @@ int nnsdp_solver_info(nnsdp_solver* s, int32_t what, double* out) {
     case 5: *out = (double)s->nmax; break;
     case 6: *out = s->ipc ? (s->ipc_fine ? 2.0 : 1.0) : 0.0; break;
     case 7: *out = (double)s->family; break;
+    case 10: *out = s->minv_structured ? (double)s->mplan.nchunk : 0.0; break;
+    case 11: {
+      int odd = 0;
+      if (s->minv_structured) for (int j = 0; j < s->mplan.nchunk; ++j) odd += ((s->mplan.clo[j] | s->mplan.w0[j]) & 1);
+      *out = (double)odd;
+      break;
+    }
     case 8: case 9: { size_t own = 0, sh = 0; s->device_bytes(own, sh); *out = (double)(what == 8 ? own : sh); break; }
     default: throw std::invalid_argument("unknown info item");
   }
@@ -2693,6 +2820,8 @@ int nnsdp_batch_info(nnsdp_batch* b, int32_t what, double* out) {
     case 0: *out = (double)b->act.size(); break;
     case 1: *out = (double)b->n_fgroups; break;
     case 2: *out = (double)b->n_fmembers; break;
+    case 3: *out = (double)b->n_sgroups; break;
+    case 4: *out = (double)b->n_smembers; break;
     default: throw std::invalid_argument("unknown info item");
   }
   API_END

@@ -168,7 +168,9 @@ inline MinvBlocks assemble_minv_blocks(const ScaledOperator& S, const MinvPlan& 
 }
 
 // ---------------------------------------------------------------------------------------------- device side
-struct MinvDev {
+// The factor view is what the members of a solver family share; the work buffers are one solver's own (bind_minv_dev).  The
+// single-vector kernels take both as one MinvDev; the multi-vector kernels below take the factors once and a table of MinvWork.
+struct MinvFactors {
   int ng, nchunk, nS, ldS, r, nslots;
   const int *clo, *chi, *w0, *w1, *hslot0;   // per chunk
   const long long *poff, *hoff;              // per chunk
@@ -178,9 +180,16 @@ struct MinvDev {
   const int* slot_chunk;                     // per H column slot: its chunk (slot = hslot0[j] + c)
   const int *slotA, *slotB;                  // per separator column: its slots in the left / right chunk
   const double *Pinv, *H, *HT, *Scinv, *v, *kap;   // v: ng x r, kap: r x r
+  const int4* tiles;                         // row tiles of the multi-vector kernels (MinvTile), stage-3 tiles first
+  int ntiles, ntiles3, ntiles_sep;           // all tiles; the prefix stage 3 takes; the separator tiles in front (stage 1 skips them)
+};
+struct MinvWork {
   double *t, *rpart, *rvec, *xS, *coef;      // work: t[ng], rpart[nslots], rvec[ldS], xS[nS], coef[8]
   double* dpart;                             // [8][kMinvParts] partial sums of v_a'q (stage 1), added in slot order (stage 2a)
+  const double* q;                           // multi-vector kernels only: this member's right-hand side and result
+  double* out;
 };
+struct MinvDev : MinvFactors, MinvWork {};
 static constexpr int kMinvParts = 32;
 
 // dot product of two 16-byte aligned vectors of length n by one wave (the pattern of k_gemv_sym: 16-byte loads, two chains)
@@ -300,6 +309,302 @@ __global__ void k_minv_transpose(int n, int w, int ldn, int ldw, const double* _
   if (idx >= (long long)n * w) return;
   const int i = (int)(idx % n), c = (int)(idx / n);
   HT[(size_t)i * ldw + c] = H[(size_t)c * ldn + i];
+}
+
+
+// ---------------------------------------------------------------------------------------------- several right-hand sides
+// The four stages for up to kMinvWidth vectors that share one set of factors (the members of a solver family in a batch handle,
+// or the rows of nnsdp_solver_apply_minv_structured_multi): a lane loads each piece of a matrix row ONCE and uses it for every
+// member.  Per member the arithmetic is the single form's, chain by chain (wave_dot2's two loops and tail, the scalar paths for an
+// odd clo / w0, the kMinvParts partial dots in slot order, the low-rank subtraction by one thread), so a member's result is
+// bit-identical to k_minv_stage1 .. k_minv_stage3 on the same vector, whatever its slot and however many members share the pass.
+// A workgroup owns a tile of rows of ONE chunk (MinvTile, built on the host) and stages that chunk's slice of every member's
+// vector in LDS once; blockIdx.y selects the pass (MinvPass), so the groups of several families share a launch.
+static constexpr int kMinvWidth = 8;            // members per pass: 8 x 4 chains of accumulators = 64 VGPRs, 8 x 8 KB of LDS per chunk slice
+static constexpr int kMinvMultiThreads = 512;   // 8 waves
+static constexpr int kMinvTileRows = 16;        // rows per tile in stages 1 and 3 (two per wave): 128 KB of matrix per 64 KB staged
+static constexpr int kMinvSchurRows = 8;        // rows per workgroup in the Schur stage (whole vectors r staged: up to 160 KB at a time)
+static constexpr int kMinvLdsSmall = 64 * 1024, kMinvLdsBig = 160 * 1024;
+enum MinvTileKind { kTileP = 0, kTileH = 1, kTileParts = 2, kTileSep = 3 };
+// int4 tile = {kind, chunk, first, count}: kTileP rows `first ..` (generator ids) of chunk's P_j, kTileH slots `first ..` of its H_j,
+// kTileParts partial low-rank dots `first ..`, kTileSep generators `first ..` of a separator (stage 3 copies x_S)
+struct MinvPass { int fac, first, count; };     // factor view, first member in the work table, members (<= kMinvWidth)
+
+// order: separator tiles, chunk-row tiles (stage 3 takes these two kinds: a prefix), H-slot tiles, partial-dot tiles (stage 1 takes the
+// last three kinds: a suffix)
+inline std::vector<int4> minv_tiles(const MinvPlan& P, const std::vector<int>& hslot0) {
+  std::vector<int4> t;
+  for (int j = 0; j + 1 < P.nchunk; ++j)
+    for (int g = P.slo[j]; g < P.shi[j]; g += kMinvMultiThreads) t.push_back(make_int4(kTileSep, -1, g, std::min(kMinvMultiThreads, P.shi[j] - g)));
+  for (int j = 0; j < P.nchunk; ++j)
+    for (int g = P.clo[j]; g < P.chi[j]; g += kMinvTileRows) t.push_back(make_int4(kTileP, j, g, std::min(kMinvTileRows, P.chi[j] - g)));
+  for (int j = 0; j < P.nchunk; ++j) {
+    const int w = P.w1[j] - P.w0[j];
+    for (int c = 0; c < w; c += kMinvTileRows) t.push_back(make_int4(kTileH, j, hslot0[j] + c, std::min(kMinvTileRows, w - c)));
+  }
+  for (int p = 0; p < kMinvParts; p += kMinvMultiThreads / 64) t.push_back(make_int4(kTileParts, -1, p, std::min(kMinvMultiThreads / 64, kMinvParts - p)));
+  return t;
+}
+
+// copy of n doubles into LDS by the workgroup: 16-byte loads where src is 16-byte aligned (aligned != 0), the odd tail by one thread
+__device__ __forceinline__ void minv_stage_vec(double* dst, const double* __restrict__ src, int n, bool aligned) {
+  if (aligned) {
+    for (int i = threadIdx.x; i < (n >> 1); i += kMinvMultiThreads) reinterpret_cast<double2*>(dst)[i] = reinterpret_cast<const double2*>(src)[i];
+    if ((n & 1) && threadIdx.x == 0) dst[n - 1] = src[n - 1];
+  } else {
+    for (int i = threadIdx.x; i < n; i += kMinvMultiThreads) dst[i] = src[i];
+  }
+}
+
+// res[m] = a'b_m for the members m < cnt, b_m = b + m * ldb (LDS).  MODE 0: wave_dot2; 1: the four-chain scalar path of stage 1;
+// 2: the one-chain scalar path of stage 3
+template <int W, int MODE>
+__device__ __forceinline__ void wave_dot_multi(const double* __restrict__ a, const double* b, int ldb, int n, int lane, int cnt, double (&res)[W]) {
+  double s[W][4];
+#pragma unroll
+  for (int m = 0; m < W; ++m) s[m][0] = s[m][1] = s[m][2] = s[m][3] = 0.0;
+  if (MODE == 0) {
+    int j = lane * 2;
+    for (; j + 129 < n; j += 256) {
+      const double2 a0 = *reinterpret_cast<const double2*>(a + j), a1 = *reinterpret_cast<const double2*>(a + j + 128);
+#pragma unroll
+      for (int m = 0; m < W; ++m)
+        if (m < cnt) {
+          const double2 b0 = *reinterpret_cast<const double2*>(b + m * ldb + j), b1 = *reinterpret_cast<const double2*>(b + m * ldb + j + 128);
+          s[m][0] += a0.x * b0.x; s[m][1] += a0.y * b0.y; s[m][2] += a1.x * b1.x; s[m][3] += a1.y * b1.y;
+        }
+    }
+    for (; j + 1 < n; j += 128) {
+      const double2 a0 = *reinterpret_cast<const double2*>(a + j);
+#pragma unroll
+      for (int m = 0; m < W; ++m)
+        if (m < cnt) {
+          const double2 b0 = *reinterpret_cast<const double2*>(b + m * ldb + j);
+          s[m][0] += a0.x * b0.x; s[m][1] += a0.y * b0.y;
+        }
+    }
+    if (j < n) {
+      const double av = a[j];
+#pragma unroll
+      for (int m = 0; m < W; ++m) if (m < cnt) s[m][0] += av * b[m * ldb + j];
+    }
+  } else if (MODE == 1) {
+    int i = lane;
+    for (; i + 192 < n; i += 256) {
+      const double a0 = a[i], a1 = a[i + 64], a2 = a[i + 128], a3 = a[i + 192];
+#pragma unroll
+      for (int m = 0; m < W; ++m)
+        if (m < cnt) {
+          const double* bm = b + m * ldb + i;
+          s[m][0] += a0 * bm[0]; s[m][1] += a1 * bm[64]; s[m][2] += a2 * bm[128]; s[m][3] += a3 * bm[192];
+        }
+    }
+    for (; i < n; i += 64) {
+      const double a0 = a[i];
+#pragma unroll
+      for (int m = 0; m < W; ++m) if (m < cnt) s[m][0] += a0 * b[m * ldb + i];
+    }
+  } else {
+    for (int c = lane; c < n; c += 64) {
+      const double a0 = a[c];
+#pragma unroll
+      for (int m = 0; m < W; ++m) if (m < cnt) s[m][0] += a0 * b[m * ldb + c];
+    }
+  }
+#pragma unroll
+  for (int m = 0; m < W; ++m)
+    if (m < cnt) res[m] = MODE == 2 ? wave_sum(s[m][0]) : wave_sum((s[m][0] + s[m][1]) + (s[m][2] + s[m][3]));
+}
+
+// LDS: the kernels get `cap` doubles of dynamic LDS and stage as many members' slices at a time as fit (all of a pass where
+// cnt * ld <= cap; otherwise the members go through in sub-passes over the same rows - the matrix rows are then read once per
+// sub-pass, from L2 - so no chunk, coupling or separator has to fit W times).  A member's arithmetic does not see the split.
+
+// stage 1 for the members of a pass: t = P_j q_Ij, rpart = H_j' q_Ij, dpart = partial v'q
+template <int W>
+__global__ __launch_bounds__(kMinvMultiThreads) void k_minv_stage1_multi(const MinvFactors* __restrict__ fac, const MinvWork* __restrict__ work,
+                                                                         const MinvPass* __restrict__ pass, int cap) {
+  extern __shared__ __align__(16) double minv_lds[];
+  const MinvPass ps = pass[blockIdx.y];
+  const MinvFactors& m = fac[ps.fac];
+  if ((int)blockIdx.x >= m.ntiles - m.ntiles_sep) return;
+  const int4 tile = m.tiles[m.ntiles_sep + blockIdx.x];
+  const int cnt = min(ps.count, W), wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  if (tile.x == kTileParts) {
+    if (wave >= tile.w) return;
+    const MinvWork* wk = work + ps.first;
+    const int part = tile.z + wave;
+    const int per = (m.ng + kMinvParts - 1) / kMinvParts, i0 = part * per, i1 = min(i0 + per, m.ng);
+    for (int mm = 0; mm < cnt; ++mm) {
+      const double* __restrict__ q = wk[mm].q;
+      for (int a = 0; a < m.r; ++a) {
+        double s = 0.0;
+        for (int i = i0 + lane; i < i1; i += 64) s += m.v[(size_t)a * m.ng + i] * q[i];
+        s = wave_sum(s);
+        if (lane == 0) wk[mm].dpart[a * kMinvParts + part] = s;
+      }
+    }
+    return;
+  }
+  const int j = tile.y, lo = m.clo[j], n = m.chi[j] - lo, ldn = (n + 1) & ~1;
+  const double* base = tile.x == kTileP ? m.Pinv + m.poff[j] + (size_t)(tile.z - lo) * ldn : m.H + m.hoff[j] + (size_t)(tile.z - m.hslot0[j]) * ldn;
+  const int mps = max(min(cap / ldn, cnt), 1);
+  for (int m0 = 0; m0 < cnt; m0 += mps) {
+    const MinvWork* wk = work + ps.first + m0;
+    const int mc = min(mps, cnt - m0);
+    if (m0) __syncthreads();
+    for (int mm = 0; mm < mc; ++mm) minv_stage_vec(minv_lds + mm * ldn, wk[mm].q + lo, n, (lo & 1) == 0);
+    __syncthreads();
+    for (int rr = wave; rr < tile.w; rr += kMinvMultiThreads / 64) {
+      double res[W];
+      if ((lo & 1) == 0) wave_dot_multi<W, 0>(base + (size_t)rr * ldn, minv_lds, ldn, n, lane, mc, res);
+      else wave_dot_multi<W, 1>(base + (size_t)rr * ldn, minv_lds, ldn, n, lane, mc, res);
+      if (lane == 0) {
+#pragma unroll
+        for (int mm = 0; mm < W; ++mm)
+          if (mm < mc) (tile.x == kTileP ? wk[mm].t : wk[mm].rpart)[tile.z + rr] = res[mm];
+      }
+    }
+  }
+}
+
+// stage 2a for the members of a pass (k_minv_resid per member)
+__global__ __launch_bounds__(kThreads) void k_minv_resid_multi(const MinvFactors* __restrict__ fac, const MinvWork* __restrict__ work,
+                                                               const MinvPass* __restrict__ pass) {
+  const MinvPass ps = pass[blockIdx.y];
+  const MinvFactors& m = fac[ps.fac];
+  const MinvWork* wk = work + ps.first;
+  const int nb = (m.nS + kThreads - 1) / kThreads;
+  if ((int)blockIdx.x > nb) return;
+  if ((int)blockIdx.x == nb) {
+    if ((int)threadIdx.x < ps.count) {
+      const MinvWork& w = wk[threadIdx.x];
+      double d[8];
+      for (int a = 0; a < m.r; ++a) { double s = 0.0; for (int p = 0; p < kMinvParts; ++p) s += w.dpart[a * kMinvParts + p]; d[a] = s; }
+      for (int a = 0; a < m.r; ++a) { double s = 0.0; for (int b = 0; b < m.r; ++b) s += m.kap[a * m.r + b] * d[b]; w.coef[a] = s; }
+    }
+    return;
+  }
+  const int c = blockIdx.x * kThreads + threadIdx.x;
+  if (c >= m.nS) return;
+  const int g = m.sep_gen[c], sa = m.slotA[c], sb = m.slotB[c];
+  for (int mm = 0; mm < ps.count; ++mm) wk[mm].rvec[c] = wk[mm].q[g] - wk[mm].rpart[sa] - wk[mm].rpart[sb];
+}
+
+// stage 2b for the members of a pass: xS = Sc^-1 r, the members' r staged in LDS
+template <int W>
+__global__ __launch_bounds__(kMinvMultiThreads) void k_minv_schur_multi(const MinvFactors* __restrict__ fac, const MinvWork* __restrict__ work,
+                                                                        const MinvPass* __restrict__ pass, int cap) {
+  extern __shared__ __align__(16) double minv_lds[];
+  const MinvPass ps = pass[blockIdx.y];
+  const MinvFactors& m = fac[ps.fac];
+  const int row0 = blockIdx.x * kMinvSchurRows;
+  if (row0 >= m.nS) return;
+  const int cnt = min(ps.count, W), wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int mps = max(min(cap / m.ldS, cnt), 1);
+  for (int m0 = 0; m0 < cnt; m0 += mps) {
+    const MinvWork* wk = work + ps.first + m0;
+    const int mc = min(mps, cnt - m0);
+    if (m0) __syncthreads();
+    for (int mm = 0; mm < mc; ++mm) minv_stage_vec(minv_lds + mm * m.ldS, wk[mm].rvec, m.nS, true);
+    __syncthreads();
+    for (int rr = wave; rr < kMinvSchurRows && row0 + rr < m.nS; rr += kMinvMultiThreads / 64) {
+      double res[W];
+      wave_dot_multi<W, 0>(m.Scinv + (size_t)(row0 + rr) * m.ldS, minv_lds, m.ldS, m.nS, lane, mc, res);
+      if (lane == 0) {
+#pragma unroll
+        for (int mm = 0; mm < W; ++mm) if (mm < mc) wk[mm].xS[row0 + rr] = res[mm];
+      }
+    }
+  }
+}
+
+// stage 3 for the members of a pass: x_Ij = t - H_j x_S with the chunk's slice of the members' x_S in LDS, x_S as is; minus the
+// low-rank term
+template <int W>
+__global__ __launch_bounds__(kMinvMultiThreads) void k_minv_stage3_multi(const MinvFactors* __restrict__ fac, const MinvWork* __restrict__ work,
+                                                                         const MinvPass* __restrict__ pass, int cap) {
+  extern __shared__ __align__(16) double minv_lds[];
+  const MinvPass ps = pass[blockIdx.y];
+  const MinvFactors& m = fac[ps.fac];
+  if ((int)blockIdx.x >= m.ntiles3) return;
+  const int4 tile = m.tiles[blockIdx.x];
+  const int cnt = min(ps.count, W), wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  if (tile.x == kTileSep) {
+    if ((int)threadIdx.x >= tile.w) return;
+    const MinvWork* wk = work + ps.first;
+    const int g = tile.z + threadIdx.x, c = m.sep_of[g];
+    for (int mm = 0; mm < cnt; ++mm) {
+      double x = wk[mm].xS[c];
+      for (int a = 0; a < m.r; ++a) x -= m.v[(size_t)a * m.ng + g] * wk[mm].coef[a];
+      wk[mm].out[g] = x;
+    }
+    return;
+  }
+  const int j = tile.y, lo = m.clo[j], w0 = m.w0[j], wj = m.w1[j] - w0, ldw = (wj + 1) & ~1;
+  const double* base = m.HT + m.hoff[j] + (size_t)(tile.z - lo) * ldw;
+  const int mps = max(min(cap / max(ldw, 2), cnt), 1);
+  for (int m0 = 0; m0 < cnt; m0 += mps) {
+    const MinvWork* wk = work + ps.first + m0;
+    const int mc = min(mps, cnt - m0);
+    if (m0) __syncthreads();
+    for (int mm = 0; mm < mc; ++mm) minv_stage_vec(minv_lds + mm * ldw, wk[mm].xS + w0, wj, (w0 & 1) == 0);
+    __syncthreads();
+    for (int rr = wave; rr < tile.w; rr += kMinvMultiThreads / 64) {
+      double res[W];
+      if ((w0 & 1) == 0) wave_dot_multi<W, 0>(base + (size_t)rr * ldw, minv_lds, ldw, wj, lane, mc, res);
+      else wave_dot_multi<W, 2>(base + (size_t)rr * ldw, minv_lds, ldw, wj, lane, mc, res);
+      if (lane == 0) {
+        const int g = tile.z + rr;
+#pragma unroll
+        for (int mm = 0; mm < W; ++mm)
+          if (mm < mc) {
+            double x = wk[mm].t[g] - res[mm];
+            for (int a = 0; a < m.r; ++a) x -= m.v[(size_t)a * m.ng + g] * wk[mm].coef[a];
+            wk[mm].out[g] = x;
+          }
+      }
+    }
+  }
+}
+
+// leading dimensions of the vectors each stage puts in LDS; ok = false only where ONE vector does not fit (a chunk or a coupling
+// above 8 192, a separator above 20 480: a Schur inverse of 3.3 GB) - the caller then keeps the single form per member (equal bits)
+struct MinvMultiLds { int ldn = 0, ldS = 0, ldw = 0; bool ok = false; };
+inline MinvMultiLds minv_multi_lds(const MinvPlan& P) {
+  MinvMultiLds L;
+  if (!P.ok) return L;
+  for (int j = 0; j < P.nchunk; ++j) {
+    L.ldn = std::max(L.ldn, (P.chi[j] - P.clo[j] + 1) & ~1);
+    L.ldw = std::max(L.ldw, (P.w1[j] - P.w0[j] + 1) & ~1);
+  }
+  L.ldw = std::max(L.ldw, 2);
+  L.ldS = std::max(P.ldS, 2);
+  L.ok = (size_t)L.ldn * 8 <= (size_t)kMinvLdsSmall && (size_t)L.ldw * 8 <= (size_t)kMinvLdsBig && (size_t)L.ldS * 8 <= (size_t)kMinvLdsBig;
+  return L;
+}
+
+// the four launches for `npass` passes (device tables): the largest grid any of the groups needs and the LDS of each stage - what
+// the widest pass of a group wants, capped (stage 1 at 64 KB so that two workgroups share a CU, the others at the CU's 160 KB)
+struct MinvMultiGrid {
+  int tiles1 = 0, tiles3 = 0, resid = 0, schur = 0, cap1 = 0, cap_schur = 0, cap3 = 0;      // caps in doubles
+  void add(const MinvFactors& f, const MinvMultiLds& L, int widest) {
+    tiles1 = std::max(tiles1, f.ntiles - f.ntiles_sep); tiles3 = std::max(tiles3, f.ntiles3);
+    resid = std::max(resid, (f.nS + kThreads - 1) / kThreads + 1); schur = std::max(schur, (f.nS + kMinvSchurRows - 1) / kMinvSchurRows);
+    auto want = [&](int ld, int limit) { return std::max(ld, std::min(widest * ld, limit / 8 / ld * ld)); };
+    cap1 = std::max(cap1, want(L.ldn, kMinvLdsSmall)); cap_schur = std::max(cap_schur, want(L.ldS, kMinvLdsBig)); cap3 = std::max(cap3, want(L.ldw, kMinvLdsBig));
+  }
+};
+inline hipError_t minv_multi_allow_lds() {
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_minv_schur_multi<kMinvWidth>), hipFuncAttributeMaxDynamicSharedMemorySize, kMinvLdsBig);
+  if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_minv_stage3_multi<kMinvWidth>), hipFuncAttributeMaxDynamicSharedMemorySize, kMinvLdsBig);
+  return e;
+}
+inline void launch_minv_multi(const MinvMultiGrid& G, const MinvFactors* fac, const MinvWork* work, const MinvPass* pass, int npass, hipStream_t st) {
+  hipLaunchKernelGGL(k_minv_stage1_multi<kMinvWidth>, dim3(G.tiles1, npass), dim3(kMinvMultiThreads), (size_t)G.cap1 * 8, st, fac, work, pass, G.cap1);
+  hipLaunchKernelGGL(k_minv_resid_multi, dim3(G.resid, npass), dim3(kThreads), 0, st, fac, work, pass);
+  hipLaunchKernelGGL(k_minv_schur_multi<kMinvWidth>, dim3(std::max(G.schur, 1), npass), dim3(kMinvMultiThreads), (size_t)G.cap_schur * 8, st, fac, work, pass, G.cap_schur);
+  hipLaunchKernelGGL(k_minv_stage3_multi<kMinvWidth>, dim3(G.tiles3, npass), dim3(kMinvMultiThreads), (size_t)G.cap3 * 8, st, fac, work, pass, G.cap3);
 }
 
 }  // namespace nnsdp

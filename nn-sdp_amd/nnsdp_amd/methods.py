@@ -438,6 +438,18 @@ class Solver:
                                                           out.ctypes.data_as(_lib.c_double_p), C.byref(ms)))
         return out, ms.value
 
+    def apply_minv_structured_multi(self, Q):
+        """(M^-1 Q, kernel milliseconds) for Q of shape (nrhs, ngamma) through the fused structured stages a family with a structured
+        M^-1 uses inside a batch (structured M^-1 only; test entry).  Row j equals apply_minv on the same vector bit for bit."""
+        Q = np.atleast_2d(_f64(Q))
+        if Q.shape[1] != self.cp.ngamma:
+            raise ValueError("Q must have one column per multiplier")
+        out = np.zeros_like(Q)
+        ms = C.c_double()
+        _lib.check(self.lib.nnsdp_solver_apply_minv_structured_multi(self.h, int(Q.shape[0]), Q.ctypes.data_as(_lib.c_double_p),
+                                                                     out.ctypes.data_as(_lib.c_double_p), C.byref(ms)))
+        return out, ms.value
+
     def iterate(self, iters: int, time_eig: bool = False) -> float:
         ms = C.c_double(0.0)
         _lib.check(self.lib.nnsdp_solver_iterate(self.h, int(iters), C.byref(ms) if time_eig else None))
@@ -590,7 +602,8 @@ class SolverBatch:
         return sb
 
     def batch_info(self, what: int) -> float:
-        """nnsdp_batch_info: 0 members still active, 1 fused family groups in the current launch tables, 2 members they cover"""
+        """nnsdp_batch_info: 0 members still active, 1 fused family groups with a dense M^-1 in the current launch tables, 2 members
+        they cover, 3 fused family groups with a structured M^-1, 4 members those cover"""
         v = C.c_double()
         _lib.check(self.lib.nnsdp_batch_info(self.h, int(what), C.byref(v)))
         return v.value
@@ -688,8 +701,10 @@ def same_family(q0, q1) -> bool:
 
 class SolverFamily(SolverBatch):
     """A SolverBatch whose solvers share ONE set-up: the first is created normally, the others as its siblings (Solver.sibling), so
-    the operator, the tables and M^-1 exist once on the device and the batch applies a dense M^-1 to all members in one pass over
-    the matrix.  Every query must satisfy same_family with the first; the library raises NnsdpError otherwise."""
+    the operator, the tables and M^-1 exist once on the device and the batch applies it to all members in one pass over the shared
+    operands: a dense M^-1 in one launch per 16 members, a structured one (large multiplier counts) in its four stages per 8
+    members, each member's result bit-identical to what it computes alone.  Every query must satisfy same_family with the first;
+    the library raises NnsdpError otherwise."""
 
     def __init__(self, queries, opts: AdmmSdpOptions):
         queries = list(queries)
@@ -730,7 +745,8 @@ def _shared_solvers(queries, optl) -> List[Solver]:
 def runQueries(queries, opts, share_setup: bool = False) -> List[QuerySolution]:
     """runQuery for several independent queries at once (batch handle); results in the order of the queries.
     share_setup=True: queries that differ in the output QC only (same_family) are created as one solver family - one set-up and one
-    M^-1 for all of them; the others run beside them in the same batch."""
+    M^-1 for all of them, applied to all members in one pass over it per iteration (dense or structured); the others run beside
+    them in the same batch."""
     if share_setup:
         queries = list(queries)
         optl = list(opts) if isinstance(opts, (list, tuple)) else [opts] * len(queries)
