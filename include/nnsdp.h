@@ -40,7 +40,7 @@
 extern "C" {
 #endif
 
-#define NNSDP_VERSION 200 /* 0.2.0 */
+#define NNSDP_VERSION 210 /* 0.2.1 */
 
 /* query_kind: Methods.SafetyQuery / Methods.ReachQuery (src/Methods/Methods.jl:22-43) */
 enum { NNSDP_QUERY_SAFETY = 0, NNSDP_QUERY_REACH = 1 };
@@ -56,7 +56,11 @@ enum { NNSDP_DECOMP_DENSE = 0, NNSDP_DECOMP_SINGLE = 1, NNSDP_DECOMP_DOUBLE = 2,
 enum { NNSDP_ACTIV_RELU = 0, NNSDP_ACTIV_TANH = 1 };
 /* termination status; strings as consumed by experiments/acas.jl:77 via nnsdp_status_string() */
 enum { NNSDP_STATUS_OPTIMAL = 0, NNSDP_STATUS_ITERATION_LIMIT = 1, NNSDP_STATUS_TIME_LIMIT = 2,
-       NNSDP_STATUS_SLOW_PROGRESS = 3, NNSDP_STATUS_NUMERICAL_ERROR = 4 };
+       NNSDP_STATUS_SLOW_PROGRESS = 3, NNSDP_STATUS_NUMERICAL_ERROR = 4,
+       NNSDP_STATUS_TARGET_CERTIFIED = 5   /* nnsdp_solver_set_target: a rigorous bound met the target (the certificate is the result) */,
+       NNSDP_STATUS_TARGET_UNREACHABLE = 6 /* ... : the estimates of the optimum exclude the target; an "unknown", not a proof */ };
+/* target modes of nnsdp_solver_set_target */
+enum { NNSDP_TARGET_OFF = 0, NNSDP_TARGET_OBJECTIVE = 1 /* reach: objective <= target */, NNSDP_TARGET_FEASIBLE = 2 /* safety: any certificate */ };
 
 /*
  * The numeric content of a Methods.Query: FeedFwdNet (src/MyNeuralNetwork/MyNeuralNetwork.jl:12-27),
@@ -234,12 +238,39 @@ int nnsdp_solver_raw_multipliers(nnsdp_solver* s, double* out);
  * nothing, otherwise equal for all members of a family and distinct between the families of a process), 8 bytes of device memory this
  * handle owns exclusively, 9 bytes it shares with other members of its family (buffers with more than one holder), 10 chunks of the
  * structured M^-1 plan (0: dense), 11 how many of them start at an odd multiplier or an odd separator column (these take the
- * scalar-load paths of the structured stages) */
+ * scalar-load paths of the structured stages), 12 sparse-bound evaluations so far (nnsdp_solver_certified_bound and the target rule),
+ * 13 whether the pattern has a sparse-bound plan (nnsdp_cert_plan's `supported`; asking builds the plan) */
 int nnsdp_solver_info(nnsdp_solver* s, int32_t what, double* out);
 /* iterate until converged / limits; fills r like nnsdp_solve */
 int nnsdp_solver_run(nnsdp_solver* s, nnsdp_result* r);
 int nnsdp_solver_finish(nnsdp_solver* s, nnsdp_result* r);
 int nnsdp_solver_destroy(nnsdp_solver* s);
+
+/* Decide a target instead of converging (default off; before or between runs; every family / batch member carries its own).
+ * Every ADMM iterate can be made exactly feasible - gamma >= 0, Z(gamma) NSD - by the two exact moves of the certificate polish (a
+ * diagonal shift, then gout from the Schur complement of the affine index), and its objective is then a rigorous upper bound of the
+ * optimum.  The moves are evaluated WITHOUT dense linear algebra: Z lives on the clique pattern, whose stored order is a perfect
+ * elimination order, so 16 shift candidates at a time are factored side by side by a multifrontal Cholesky of -Z with every front in
+ * LDS (nnsdp_cert_plan, nnsdp_sparse_nsd), twice per evaluation; as in the dense polish a candidate must have Z_xx <= -1e-9 I in the
+ * solver's coordinates.
+ *   mode NNSDP_TARGET_OBJECTIVE (reach queries; `target` in the units of nnsdp_result.objective): at every check iteration whose ADMM
+ *     primal estimate is <= target the bound is evaluated, and the solve stops with NNSDP_STATUS_TARGET_CERTIFIED as soon as it is
+ *     <= target.  It stops with NNSDP_STATUS_TARGET_UNREACHABLE once both residuals are <= 1e-3 and
+ *     min(pobj, dobj) - target > 3.8 x max(pres, dres) x max(|pobj|, |dobj|)  (twice the smallest factor that is safe on every traced
+ *     check point).  UNREACHABLE rests on estimates: it is an "unknown", never a proof that the target fails, and
+ *     the rule can only ever produce such an unknown - a TARGET_CERTIFIED is always backed by the exactly feasible point returned.
+ *   mode NNSDP_TARGET_FEASIBLE (safety queries: any certificate): the bound is evaluated at every check iteration and the solve stops
+ *     with NNSDP_STATUS_TARGET_CERTIFIED at the first feasible candidate.
+ * nnsdp_solver_finish / _finish_status then return exactly that point, checked by the dense eigmax like any other result.  A pattern
+ * whose largest front exceeds 128 has no sparse route: the rule then uses the dense polish on the schedule of cert_tol.  -1 for a
+ * clique-sharded solver, and for NNSDP_TARGET_OBJECTIVE on a safety query. */
+int nnsdp_solver_set_target(nnsdp_solver* s, int32_t mode, double target);
+/* The rigorous bound of the CURRENT iterate (any query kind; reach: objective = gout): *certified = 1 and the exactly feasible
+ * multipliers in gamma (ngamma doubles, reference coordinates, may be NULL; multipliers of coordinates the normalisation removed are
+ * set "large": 1e8 x the largest other one), or *certified = 0 when no candidate passed.  *ms receives the wall-clock time of the call.
+ * Deterministic; the iteration state is not touched (the iterates that follow are bit-identical to those of a solver that never
+ * asked).  A pattern without a sparse route answers through the dense polish. */
+int nnsdp_solver_certified_bound(nnsdp_solver* s, double* objective, double* gamma, int32_t* certified, double* ms);
 
 /* Batch handle (no reference analogue): several independent SDPs - the beta sweep of experiments/scale.jl:28, the
  * hyperplane directions of NnSdp.findReach2Dpoly (src/NnSdp.jl:73-95), the sub-queries of an ACAS clause
@@ -345,6 +376,23 @@ int nnsdp_comm_unique_id(char* id128);
  * block_n[n_blocks] (block dimensions after the normalisation) and start[nranks+1] (rank r owns blocks start[r] .. start[r+1]-1). */
 int nnsdp_shard_plan(const nnsdp_problem* p, const nnsdp_options* o, int32_t nranks, int32_t* n_blocks, int32_t* block_n,
                      int32_t* start);
+/* Host-only (no GPU): the plan of the sparse NSD check for (problem, options) - symbolic elimination of the solver's clique pattern
+ * (reduced coordinates, stored order, the affine index a = n - 1 last and never eliminated; a is a row of every front).  n: reduced
+ * dimension; supernodes are the column ranges col_start[s] .. col_start[s+1]-1 (col_start[n_super] = n - 1); rows row_idx[row_ptr[s] ..
+ * row_ptr[s+1]-1] lie below supernode s's diagonal block (ascending, fill included, the last one is a); the parent of s is the supernode
+ * of its first row (none when that row is a: the plan may be a forest); max_front: the largest columns + rows; fill: entries of the
+ * factor's structure outside the pattern; supported: max_front <= 128.  Two-pass: any of the three arrays may be NULL; row_idx needs
+ * row_ptr[n_super] <= n_super x max_front entries. */
+int nnsdp_cert_plan(const nnsdp_problem* p, const nnsdp_options* o, int32_t* n, int32_t* n_super, int32_t* max_front, int64_t* fill,
+                    int32_t* supported, int32_t* col_start, int32_t* row_ptr, int32_t* row_idx);
+/* Test / diagnostic entry of the sparse NSD check on dense input: `mats` holds `batch` symmetric n x n column-major matrices on the
+ * clique pattern (ptr / idx as nnsdp_make_cliques returns them; index n - 1 is the affine index a).  Candidate b is negative
+ * semidefinite exactly when ok[b] = 1 - every pivot of the Cholesky of -M_xx exceeded 1e-13 x the largest diagonal entry of its
+ * supernode's columns as assembled - and schur[b] = M_aa - m_xa' M_xx^-1 m_xa <= 0.  min_pivot[b]: the smallest pivot met; for a
+ * candidate with ok[b] = 0, schur[b] holds the first failing column instead.  A candidate's bits do not depend on the batch size or on
+ * its position.  -1: a non-zero entry outside the pattern; -2 (before any launch): a front above 128.  kernel_ms: HIP-event time. */
+int nnsdp_sparse_nsd(int32_t n, int32_t n_cliques, const int32_t* ptr, const int32_t* idx, int32_t batch, const double* mats, int32_t* ok,
+                     double* min_pivot, double* schur, double* kernel_ms);
 int nnsdp_solver_set_comm(nnsdp_solver* s, int32_t nranks, int32_t rank, const char* id128);
 /* The same sharded mode over the CALLER's collective instead of RCCL (MPI.Allreduce! from the Julia side; gloo in the
  * two-process GPU test): fn(user, buf, count) replaces the HOST buffer buf[count] by its element-wise sum over all ranks and

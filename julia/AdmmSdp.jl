@@ -33,6 +33,9 @@ struct AutoDecomp <: DecompMode end      # PathDecomp when the query allows it, 
   interval_guard::Float64 = 5e-5
   minv_mode::Int = 0
   proj_refine::Int = 1
+  # decide a target instead of converging (nnsdp_solver_set_target; not fields of nnsdp_options: set on the handle after create)
+  target::Union{Nothing,Float64} = nothing   # units of objective_value; reach queries
+  target_mode::Int = -1                      # -1: 1 (objective <= target) when a target is given, else 0 (off); 2: any certificate (safety)
 end
 
 # field order and types must match include/nnsdp.h
@@ -99,8 +102,25 @@ function runQuery(query::Query, opts::AdmmSdpOptions)
     prob = CProblem(ffnet.K, pointer(xdims), pointer(M), pointer(x1min), pointer(x1max), pointer(acymin), pointer(acymax),
                     pointer(smin), pointer(smax), Int32(qs.β), qkind, okind, p(normal), p(yc), p(invP), p(S),
                     ffnet.activ isa TanhActiv ? Int32(1) : Int32(0))
-    rc = ccall((:nnsdp_solve, LIBNNSDP), Cint, (Ref{CProblem}, Ref{COptions}, Ref{CResult}), prob, copts, res)
-    rc == 0 || error("nnsdp_solve failed ($rc): " * unsafe_string(ccall((:nnsdp_last_error, LIBNNSDP), Cstring, ())))
+    tmode = opts.target_mode >= 0 ? opts.target_mode : (opts.target === nothing ? 0 : 1)
+    if tmode == 0
+      rc = ccall((:nnsdp_solve, LIBNNSDP), Cint, (Ref{CProblem}, Ref{COptions}, Ref{CResult}), prob, copts, res)
+      rc == 0 || error("nnsdp_solve failed ($rc): " * unsafe_string(ccall((:nnsdp_last_error, LIBNNSDP), Cstring, ())))
+    else
+      # a target lives on the handle: create, set the target, run (status "TARGET_CERTIFIED" / "TARGET_UNREACHABLE"), destroy
+      h = Ref{Ptr{Cvoid}}(C_NULL)
+      lasterr() = unsafe_string(ccall((:nnsdp_last_error, LIBNNSDP), Cstring, ()))
+      rc = ccall((:nnsdp_solver_create, LIBNNSDP), Cint, (Ref{CProblem}, Ref{COptions}, Ref{Ptr{Cvoid}}), prob, copts, h)
+      rc == 0 || error("nnsdp_solver_create failed ($rc): " * lasterr())
+      try
+        rc = ccall((:nnsdp_solver_set_target, LIBNNSDP), Cint, (Ptr{Cvoid}, Int32, Float64), h[], Int32(tmode), something(opts.target, 0.0))
+        rc == 0 || error("nnsdp_solver_set_target failed ($rc): " * lasterr())
+        rc = ccall((:nnsdp_solver_run, LIBNNSDP), Cint, (Ptr{Cvoid}, Ref{CResult}), h[], res)
+        rc == 0 || error("nnsdp_solver_run failed ($rc): " * lasterr())
+      finally
+        ccall((:nnsdp_solver_destroy, LIBNNSDP), Cint, (Ptr{Cvoid},), h[])
+      end
+    end
   end
   values = Dict{Symbol,Any}(:γin => gin, :γac1 => gac1, :γac2 => gac2, :Z => Z)
   if query isa ReachQuery; values[:γout] = gout end

@@ -20,6 +20,7 @@
 #include "kernels.hip"
 #include "refine_pipe.hpp"
 #include "setup.hpp"
+#include "cert_plan.hpp"
 #include "minv.hpp"
 #include "intervals.hpp"
 #include "forward.hpp"
@@ -340,6 +341,54 @@ static std::vector<int> shard_ranges(const std::vector<int>& cn, int nr) {
   for (int r = parts; r <= nr; ++r) start[r] = ncl;     // more ranks than blocks: the surplus ranks own nothing
   return start;
 }
+
+// the pattern a solver for (problem, options) works on: its reduced cliques, NNSDP_DECOMP_AUTO resolved by the solver's own rule.  Host only.
+static Pattern solver_pattern(const ProblemCopy& P, const Congruence& C, int mode) {
+  if (mode == NNSDP_DECOMP_AUTO) {
+    mode = NNSDP_DECOMP_PATH;
+    try {
+      Pattern ptp = build_pattern(C.nred, reduced_cliques(P, C, mode));
+      (void)OperatorBuilder(P, C, ptp).build();
+    } catch (const std::runtime_error&) { mode = NNSDP_DECOMP_DOUBLE; }
+  }
+  return build_pattern(C.nred, reduced_cliques(P, C, mode));
+}
+
+// Device half of the sparse NSD check (cert_plan.hpp / cert_chol.hpp): the plan's tables, the per-candidate scratch and results.
+struct CertDev {
+  CertPlan pl;
+  DBuf<int> col_start, row_ptr, rel, child_ptr, child_idx, roots, gat_ptr, gat_pos, gat_ent, ok, fail;
+  DBuf<long long> upd_off;
+  DBuf<double> scratch, minp, schur;
+  int cap = 0;
+  static constexpr double kPivotFloor = 1e-13;
+  void upload(CertPlan&& plan) {
+    pl = std::move(plan);
+    if (!pl.supported) throw std::invalid_argument("sparse NSD check: largest front " + std::to_string(pl.max_front) + " exceeds " + std::to_string(kCertFrontMax));
+    col_start.upload(pl.col_start); row_ptr.upload(pl.row_ptr); rel.upload(pl.rel); child_ptr.upload(pl.child_ptr);
+    child_idx.upload(pl.child_idx); roots.upload(pl.roots); gat_ptr.upload(pl.gat_ptr); gat_pos.upload(pl.gat_pos);
+    gat_ent.upload(pl.gat_ent); upd_off.upload(pl.upd_off);
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(nnsdp::k_cert_chol), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64));
+  }
+  void reserve(int batch) {
+    if (batch <= cap) return;
+    scratch.alloc((size_t)batch * pl.scratch); ok.alloc(batch); fail.alloc(batch); minp.alloc(batch); schur.alloc(batch);
+    cap = batch;
+  }
+  // factor -Z of `batch` candidates whose NE-vectors lie zstride apart; results stay on the device until fetched
+  void launch(const double* z, long long zstride, int batch, hipStream_t st, double diag_margin = 0.0) {
+    reserve(batch);
+    nnsdp::CertArgs a{};
+    a.n_super = pl.n_super; a.e_aa = pl.e_aa; a.n_roots = (int)pl.roots.size();
+    a.col_start = col_start.p; a.row_ptr = row_ptr.p; a.rel = rel.p; a.child_ptr = child_ptr.p; a.child_idx = child_idx.p;
+    a.roots = roots.p; a.gat_ptr = gat_ptr.p; a.gat_pos = gat_pos.p; a.gat_ent = gat_ent.p; a.upd_off = upd_off.p;
+    a.z = z; a.zstride = zstride; a.scratch = scratch.p; a.sstride = pl.scratch; a.pivot_floor = kPivotFloor; a.diag_margin = diag_margin;
+    a.ld = nnsdp::cert_ld(pl.max_front);
+    a.ok = ok.p; a.fail_col = fail.p; a.min_pivot = minp.p; a.schur = schur.p;
+    hipLaunchKernelGGL(nnsdp::k_cert_chol, dim3(batch), dim3(nnsdp::kCertThreads), nnsdp::cert_lds_bytes(pl.max_front), st, a);
+    HIPCHK(hipGetLastError());
+  }
+};
 
 struct nnsdp_solver {
   nnsdp_options opt;
@@ -974,6 +1023,7 @@ struct nnsdp_solver {
     if (iters_done != 0) throw std::invalid_argument("set_comm must be called before the first iteration");
     if (family != 0) throw std::invalid_argument("a member of a solver family cannot be clique-sharded (its M^-1 is shared)");
     if (sharded) throw std::invalid_argument("the solver already has a communicator");
+    if (target_mode != NNSDP_TARGET_OFF) throw std::invalid_argument("a solver with a target cannot be clique-sharded");
     if (fn) { ar_fn = fn; ar_user = user; }
     else {
       Rccl& R = Rccl::get();
@@ -1433,6 +1483,18 @@ struct nnsdp_solver {
       for (int i = 0; i < S.ng; ++i) o += S.c[i] * gp[i];
       std::fprintf(stderr, "[nnsdp] it %6lld t %.2f polished rho %.8g (ok %d shift %.2e) admm %.8g dobj %.8g pres %.1e dres %.1e polish_ms %.0f\n", iters_done,
                    now_s() - t0, o / (S.zscale * S.cscale), (int)ok, polish_shift, last_pobj, last_dobj, last_pres, last_dres, 1e3 * (now_s() - tp));
+      if (cert_ready()) {      // the sparse route at the same iterate (tools/decision_timing.py reads both lines)
+        tp = now_s();
+        const SparseBound sb = sparse_bound();
+        std::fprintf(stderr, "[nnsdp] it %6lld sparse rho %.10g (ok %d shift %.2e) dense %.10g sparse_ms %.3f\n", iters_done, sb.objective, (int)sb.certified,
+                     sb.delta, o / (S.zscale * S.cscale), 1e3 * (now_s() - tp));
+      }
+    }
+    // a target is decided at EVERY check iteration, the one on which the residual test would end the solve included: a solve that
+    // converges at its first check (a hyperplane direction whose optimum is gout = 0) still answers the question it was asked
+    if (!advance_only && target_mode != NNSDP_TARGET_OFF) {
+      const int ts = target_check();
+      if (ts >= 0) return ts;
     }
     if (!advance_only && last_pres <= opt.eps_rel && last_dres <= opt.eps_rel) return NNSDP_STATUS_OPTIMAL;
     // optional early stop on the CERTIFIED objective: the polished point is exactly feasible, so once it
@@ -1559,32 +1621,45 @@ struct nnsdp_solver {
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(st));
   }
-  bool polish(std::vector<double>& gsh) {
+  // The two exact moves' tables: shift_gen[i] / dcoef[i] - the kept multiplier whose generator is a pure negative diagonal on the reduced
+  // coordinate i and its (negative) coefficient there; jout / aout - gout and its coefficient on (a, a) (reach queries; -1 otherwise).
+  // false: some coordinate has no such multiplier.
+  bool shift_direction(std::vector<int>& shift_gen, std::vector<double>& dcoef, int& jout, double& aout) const {
     int n = pat.n, nx = n - 1;
     if (nx < 1) return false;
     // kept-generator index of the diagonal-shift multiplier of each reduced coordinate, and of gout
     std::vector<int> inv(P.ng, -1);
     for (int i = 0; i < S.ng; ++i) inv[S.keep[i]] = i;
-    std::vector<int> shift_gen(nx, -1);
+    shift_gen.assign(nx, -1);
     for (int i = 0; i < P.Zdim - 1; ++i) {
       int ri = C.newpos[i];
       if (ri < 0 || ri >= nx) continue;
       int full = i < P.nin ? i : P.nin + P.nout + (i - P.nin);
       shift_gen[ri] = inv[full];
     }
-    auto entry = [&](int e, int g) -> double {   // A_s[e, g]
-      for (int q = S.csr_ptr[e]; q < S.csr_ptr[e + 1]; ++q) if (S.csr_col[q] == g) return S.csr_val[q];
-      return 0.0;
-    };
-    std::vector<double> dcoef(nx, 0.0);
+    dcoef.assign(nx, 0.0);
     for (int i = 0; i < nx; ++i) {
       if (shift_gen[i] < 0) return false;
-      dcoef[i] = entry(pat.pos(i, i), shift_gen[i]);
+      dcoef[i] = op_entry(pat.pos(i, i), shift_gen[i]);
       if (!(dcoef[i] < 0.0)) return false;
     }
-    int jout = P.nout ? inv[P.nin] : -1;
-    double aout = jout >= 0 ? entry(pat.pos(nx, nx), jout) : 0.0;
+    jout = P.nout ? inv[P.nin] : -1;
+    aout = jout >= 0 ? op_entry(pat.pos(nx, nx), jout) : 0.0;
     if (P.nout && !(aout < 0.0)) return false;
+    return true;
+  }
+  double op_entry(int e, int g) const {   // A_s[e, g]
+    for (int q = S.csr_ptr[e]; q < S.csr_ptr[e + 1]; ++q) if (S.csr_col[q] == g) return S.csr_val[q];
+    return 0.0;
+  }
+  bool polish(std::vector<double>& gsh) {
+    int n = pat.n, nx = n - 1;
+    std::vector<int> shift_gen;
+    std::vector<double> dcoef;
+    int jout = -1;
+    double aout = 0.0;
+    if (!shift_direction(shift_gen, dcoef, jout, aout)) return false;
+    auto entry = [&](int e, int g) { return op_entry(e, g); };
     DBuf<double> Zt, W, Dv, Ev;
     DBuf<rocblas_int> info;
     info.alloc(1); Dv.alloc(nx); Ev.alloc(nx); W.alloc((size_t)nx * nx);
@@ -1655,6 +1730,212 @@ struct nnsdp_solver {
     double need = (Zh[(size_t)nx * n + nx] + q) / (-aout);
     gsh[jout] = std::max(0.0, need * (1.0 + 1e-12) + 1e-300);
     return true;
+  }
+
+  // ---- sparse certified bound ---------------------------------------------------------------
+  // The same two exact moves as polish(), evaluated through the sparse Cholesky of -Z on the clique pattern (cert_plan.hpp,
+  // cert_chol.hpp) instead of dense dsyevd / dpotrf: gout = 0, kSbCand candidates gamma + delta_b s along the diagonal-shift direction
+  // s_i = 1 / (-dcoef_i) - delta = 0 and a geometric grid over twelve decades below `top` - become kSbCand NE-vectors in one launch
+  // and are factored side by side in one launch.  top = (Gershgorin bound of Z_xx)+ + margin + |z_xa| / sqrt(kappa) brackets the
+  // minimiser of polish()'s f(delta) = Z_aa + kappa delta + z_xa' (-Z_xx + delta I)^-1 z_xa: the first two terms make Z_xx <= -margin
+  // for certain, and f' >= 0 from |z_xa| / sqrt(kappa) past that point on.  As in polish() a candidate must have Z_xx <= -margin I
+  // (margin = 1e-9: the kernel factors -Z_xx - margin I, so its Schur complement errs on the safe side); it is then exactly feasible
+  // once gout takes that Schur complement (a safety query has no gout: the Schur complement itself must be negative), the one with
+  // the smallest objective is kept, and a second round of candidates between its neighbours refines it.  Deterministic (fixed grids,
+  // fixed-order kernels), no host library, and nothing of the iteration state is touched (gs and the buffers below are scratch).
+  static constexpr int kSbCand = 16;
+  int target_mode = NNSDP_TARGET_OFF;
+  double target = 0.0;
+  long long sparse_calls = 0;
+  int cert_state = 0;                  // 0: plan not built yet, 1: ready, -1: unsupported (front above kCertFrontMax, or no shift direction)
+  std::unique_ptr<CertDev> cert;
+  std::vector<int> sb_shift_gen;
+  std::vector<double> sb_dcoef;
+  int sb_jout = -1;
+  double sb_aout = 0.0, sb_kappa = 0.0;   // kappa: what a unit shift adds to Z_aa
+  static constexpr double kSbMargin = 1e-9;       // polish()'s margin on Z_xx
+  DBuf<double> sb_g, sb_z;
+  struct SparseBound {
+    bool certified = false;
+    double objective = 0.0, delta = 0.0;       // objective in the units of nnsdp_result.objective
+    std::vector<double> gsh;                    // the multipliers (solver coordinates), gout included
+  };
+  bool cert_ready() {
+    if (cert_state == 0) {
+      cert_state = -1;
+      if (const char* e = std::getenv("NNSDP_SPARSE_BOUND")) if (std::atoi(e) == 0) return false;      // (diagnostic: the dense route everywhere)
+      CertPlan pl = make_cert_plan(pat);
+      if (pl.supported && pl.n_super > 0 && shift_direction(sb_shift_gen, sb_dcoef, sb_jout, sb_aout)) {
+        sb_kappa = 0.0;
+        for (int i = 0; i < pat.n - 1; ++i) sb_kappa += op_entry(pat.pos(pat.n - 1, pat.n - 1), sb_shift_gen[i]) / (-sb_dcoef[i]);
+        cert.reset(new CertDev());
+        cert->upload(std::move(pl));
+        sb_g.alloc((size_t)kSbCand * S.ng);
+        sb_z.alloc((size_t)kSbCand * S.NE);
+        cert->reserve(kSbCand);
+        cert_state = 1;
+      }
+    }
+    return cert_state == 1;
+  }
+  SparseBound sparse_bound() {
+    SparseBound R;
+    if (!cert_ready()) return R;
+    ++sparse_calls;
+    const int ng = S.ng, nx = pat.n - 1, NE = S.NE, B = kSbCand;
+    hipLaunchKernelGGL(k_extract_gamma, dim3(cdiv(ng, 256)), dim3(256), 0, st, ng, nu.p, d_sigma(), d_kappa(), gs.p);
+    HIPCHK(hipStreamSynchronize(st));
+    std::vector<double> g0 = gs.download();
+    if (sb_jout >= 0) g0[sb_jout] = 0.0;
+    // Z(gamma) itself, for the Gershgorin bound of its x-block (the upper end of the shift grid) and the scale of the margin
+    HIPCHK(hipMemcpyAsync(sb_g.p, g0.data(), (size_t)ng * sizeof(double), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_apply_A, dim3(cdiv((long long)NE * 16, kThreads)), dim3(kThreads), 0, st, NE, D.csr_ptr.p, D.csr_col.p, D.csr_val.p,
+                       sb_g.p, D.z0.p, sb_z.p);
+    HIPCHK(hipGetLastError());
+    std::vector<double> zv(NE);
+    HIPCHK(hipMemcpyAsync(zv.data(), sb_z.p, (size_t)NE * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    std::vector<double> dg(nx, 0.0), off(nx, 0.0);
+    double zxa2 = 0.0;
+    for (int e = 0; e < NE; ++e) {
+      const int i = pat.erow[e], j = pat.ecol[e];
+      if (i >= nx) { if (j < nx) zxa2 += 0.5 * zv[e] * zv[e]; continue; }
+      if (i == j) dg[i] = zv[e];
+      else { const double v = std::fabs(zv[e]) * M_SQRT1_2; off[i] += v; off[j] += v; }
+    }
+    double gersh = -1e300, scale = 0.0;
+    for (int i = 0; i < nx; ++i) { gersh = std::max(gersh, dg[i] + off[i]); scale = std::max(scale, std::fabs(dg[i]) + off[i]); }
+    if (!(scale > 0.0) || !(scale < 1e300)) return R;
+    const double top = std::max(gersh, 0.0) * (1.0 + 1e-9) + kSbMargin + (sb_kappa > 0.0 ? std::sqrt(zxa2 / sb_kappa) : 1e-3 * scale), margin = 1e-12 * scale;
+    std::vector<double> G((size_t)B * ng), obj(B);
+    std::vector<int> okv(B);
+    std::vector<double> sch(B);
+    // one round: candidates at the shifts dl[0 .. B-1]; returns the best feasible one (-1: none)
+    auto round = [&](const std::vector<double>& dl) {
+      for (int b = 0; b < B; ++b) {
+        double* gb = &G[(size_t)b * ng];
+        std::copy(g0.begin(), g0.end(), gb);
+        if (dl[b] > 0.0) for (int i = 0; i < nx; ++i) gb[sb_shift_gen[i]] += dl[b] / (-sb_dcoef[i]);
+      }
+      HIPCHK(hipMemcpyAsync(sb_g.p, G.data(), G.size() * sizeof(double), hipMemcpyHostToDevice, st));
+      hipLaunchKernelGGL(k_apply_A_multi, dim3(cdiv((long long)NE * 16, kThreads), B), dim3(kThreads), 0, st, NE, D.csr_ptr.p, D.csr_col.p,
+                         D.csr_val.p, sb_g.p, (long long)ng, D.z0.p, sb_z.p, (long long)NE);
+      HIPCHK(hipGetLastError());
+      cert->launch(sb_z.p, NE, B, st, kSbMargin);
+      HIPCHK(hipMemcpyAsync(okv.data(), cert->ok.p, B * sizeof(int), hipMemcpyDeviceToHost, st));
+      HIPCHK(hipMemcpyAsync(sch.data(), cert->schur.p, B * sizeof(double), hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
+      int best = -1;
+      for (int b = 0; b < B; ++b) {
+        obj[b] = 1e300;
+        if (!okv[b] || !(sch[b] == sch[b])) continue;
+        double* gb = &G[(size_t)b * ng];
+        if (sb_jout >= 0) gb[sb_jout] = std::max(0.0, sch[b] / (-sb_aout) * (1.0 + 1e-12) + 1e-300);
+        else if (!(sch[b] <= -margin)) continue;
+        double o = 0.0;
+        for (int i = 0; i < ng; ++i) o += S.c[i] * gb[i];
+        obj[b] = o;
+        if (best < 0 || o < obj[best]) best = b;
+      }
+      return best;
+    };
+    auto keep = [&](int b, const std::vector<double>& dl) {
+      const double o = obj[b] / (S.zscale * S.cscale);
+      if (R.certified && !(o < R.objective)) return;
+      R.certified = true; R.objective = o; R.delta = dl[b];
+      R.gsh.assign(G.begin() + (size_t)b * ng, G.begin() + (size_t)(b + 1) * ng);
+    };
+    std::vector<double> dl(B, 0.0);
+    const double ratio = std::pow(1e12, 1.0 / (B - 2));
+    for (int b = B - 1; b >= 1; --b) dl[b] = b == B - 1 ? top : dl[b + 1] / ratio;
+    const int b1 = round(dl);
+    if (b1 < 0) return R;
+    keep(b1, dl);
+    // second round: between the neighbours of the best
+    const double hi = b1 < B - 1 ? dl[b1 + 1] : dl[b1];
+    const double lo = b1 > 0 && dl[b1 - 1] > 0.0 ? dl[b1 - 1] : 1e-6 * hi;
+    std::vector<double> d2(B);
+    for (int b = 0; b < B; ++b) d2[b] = lo * std::pow(hi / lo, (b + 1.0) / (B + 1.0));
+    const int b2 = round(d2);
+    if (b2 >= 0) keep(b2, d2);
+    return R;
+  }
+  // the target rule of post_check: 5 / 6 to stop with, -1 to go on (target_mode != OFF)
+  static constexpr double kTargetUnreachM = 3.8;   // twice the smallest m that is safe on every traced check point
+  int target_check() {
+    const bool reach = target_mode == NNSDP_TARGET_OBJECTIVE;
+    if (!reach || last_pobj <= target) {
+      bool have = false;
+      double o = 0.0, sh = 0.0;
+      std::vector<double> gp;
+      if (cert_ready()) {
+        SparseBound sb = sparse_bound();
+        have = sb.certified; o = sb.objective; sh = sb.delta; gp = std::move(sb.gsh);
+      } else if (iters_done >= next_cert && std::max(last_pres, last_dres) <= 1e-3) {
+        // no sparse route for this pattern: the dense polish, on the schedule of the cert_tol rule
+        next_cert = std::max<long long>(iters_done + 100, iters_done * 11 / 10);
+        hipLaunchKernelGGL(k_extract_gamma, dim3(cdiv(S.ng, 256)), dim3(256), 0, st, S.ng, nu.p, d_sigma(), d_kappa(), gs.p);
+        HIPCHK(hipStreamSynchronize(st));
+        gp = gs.download();
+        have = polish(gp) && (P.nout != 0);     // (a safety query's dense polish does not look at the row of a: no certificate from it)
+        sh = polish_shift;
+        if (have) {
+          for (int i = 0; i < S.ng; ++i) o += S.c[i] * gp[i];
+          o /= (S.zscale * S.cscale);
+        }
+      }
+      if (have && (!reach || o <= target)) {
+        if (opt.verbose) std::fprintf(stderr, "[nnsdp] it %6lld target certified: bound %.8g target %.8g\n", iters_done, o, target);
+        cert_gp = std::move(gp); cert_shift = sh; cert_iter = iters_done;      // finish() checks exactly this point
+        return NNSDP_STATUS_TARGET_CERTIFIED;
+      }
+    }
+    if (reach && std::max(last_pres, last_dres) <= 1e-3 &&
+        std::min(last_pobj, last_dobj) - target > kTargetUnreachM * std::max(last_pres, last_dres) * std::max(std::fabs(last_pobj), std::fabs(last_dobj)))
+      return NNSDP_STATUS_TARGET_UNREACHABLE;
+    return -1;
+  }
+  void set_target(int mode, double tg) {
+    if (mode < NNSDP_TARGET_OFF || mode > NNSDP_TARGET_FEASIBLE) throw std::invalid_argument("unrecognized target mode");
+    if (sharded) throw std::invalid_argument("a clique-sharded solver takes no target");
+    if (mode == NNSDP_TARGET_OBJECTIVE && !P.nout) throw std::invalid_argument("NNSDP_TARGET_OBJECTIVE needs a reach query (a safety query takes NNSDP_TARGET_FEASIBLE)");
+    if (mode == NNSDP_TARGET_OBJECTIVE && !(tg == tg)) throw std::invalid_argument("the target is NaN");
+    target_mode = mode; target = tg;
+  }
+  // rigorous bound of the current iterate on request: the sparse route, or the dense polish where the pattern has none
+  void certified_bound(double* objective, double* gamma, int32_t* certified, double* ms) {
+    const double t_in = now_s();
+    bool have = false;
+    double o = 0.0;
+    std::vector<double> gp;
+    if (cert_ready()) {
+      SparseBound sb = sparse_bound();
+      have = sb.certified; o = sb.objective; gp = std::move(sb.gsh);
+    } else {
+      hipLaunchKernelGGL(k_extract_gamma, dim3(cdiv(S.ng, 256)), dim3(256), 0, st, S.ng, nu.p, d_sigma(), d_kappa(), gs.p);
+      HIPCHK(hipStreamSynchronize(st));
+      gp = gs.download();
+      have = polish(gp) && (P.nout != 0);
+      if (have) {
+        for (int i = 0; i < S.ng; ++i) o += S.c[i] * gp[i];
+        o /= (S.zscale * S.cscale);
+      }
+    }
+    if (ms) *ms = 1e3 * (now_s() - t_in);
+    if (certified) *certified = have ? 1 : 0;
+    if (objective) *objective = have ? o : std::nan("");
+    if (gamma) {
+      std::fill(gamma, gamma + P.ng, 0.0);
+      if (have) {
+        double gscale = 1.0;
+        for (int i = 0; i < S.ng; ++i) { gamma[S.keep[i]] = gp[i] * S.ecol[i] / S.zscale; gscale = std::max(gscale, gamma[S.keep[i]]); }
+        // coordinates removed by the normalisation: their box multipliers are cost-free and exact in the limit of infinity
+        if (opt.normalize && P.query_kind == NNSDP_QUERY_REACH) {
+          for (int i = 0; i < P.nin; ++i) if (C.newpos[i] < 0) gamma[i] = 1e8 * gscale;
+          for (int t = 0; t < P.acdim; ++t) if (C.newpos[P.nin + t] < 0) gamma[P.nin + P.nout + t] = 1e8 * gscale;
+        }
+      }
+    }
   }
 
   // The certificate (gamma, eigmax) is computed ONCE: in clique-sharded mode by rank 0 alone, whose result travels to every
@@ -2140,6 +2421,8 @@ const char* nnsdp_status_string(int32_t s) {
     case NNSDP_STATUS_TIME_LIMIT: return "TIME_LIMIT";
     case NNSDP_STATUS_SLOW_PROGRESS: return "SLOW_PROGRESS";
     case NNSDP_STATUS_NUMERICAL_ERROR: return "NUMERICAL_ERROR";
+    case NNSDP_STATUS_TARGET_CERTIFIED: return "TARGET_CERTIFIED";
+    case NNSDP_STATUS_TARGET_UNREACHABLE: return "TARGET_UNREACHABLE";
     default: return "UNKNOWN";
   }
 }
@@ -2394,6 +2677,8 @@ int nnsdp_solver_info(nnsdp_solver* s, int32_t what, double* out) {
       *out = (double)odd;
       break;
     }
+    case 12: *out = (double)s->sparse_calls; break;
+    case 13: *out = s->cert_ready() ? 1.0 : 0.0; break;
     case 8: case 9: { size_t own = 0, sh = 0; s->device_bytes(own, sh); *out = (double)(what == 8 ? own : sh); break; }
     default: throw std::invalid_argument("unknown info item");
   }
@@ -2419,7 +2704,7 @@ int nnsdp_solver_finish(nnsdp_solver* s, nnsdp_result* r) {
 int nnsdp_solver_finish_status(nnsdp_solver* s, int32_t status, nnsdp_result* r) {
   API_BEGIN
   if (!s || !r) throw std::invalid_argument("null argument");
-  if (status < NNSDP_STATUS_OPTIMAL || status > NNSDP_STATUS_NUMERICAL_ERROR) throw std::invalid_argument("unrecognized status");
+  if (status < NNSDP_STATUS_OPTIMAL || status > NNSDP_STATUS_TARGET_UNREACHABLE) throw std::invalid_argument("unrecognized status");
   s->finish(r, status);
   API_END
 }
@@ -2876,6 +3161,101 @@ int nnsdp_shard_plan(const nnsdp_problem* p, const nnsdp_options* o, int32_t nra
     for (size_t k = 0; k < cl.size(); ++k) cn[k] = (int)cl[k].size();
     if (block_n) for (size_t k = 0; k < cn.size(); ++k) block_n[k] = cn[k];
     if (start) { auto st = shard_ranges(cn, nranks); for (int r = 0; r <= nranks; ++r) start[r] = st[r]; }
+  }
+  API_END
+}
+
+int nnsdp_solver_set_target(nnsdp_solver* s, int32_t mode, double target) {
+  API_BEGIN
+  if (!s) throw std::invalid_argument("null solver");
+  s->set_target(mode, target);
+  API_END
+}
+
+int nnsdp_solver_certified_bound(nnsdp_solver* s, double* objective, double* gamma, int32_t* certified, double* ms) {
+  API_BEGIN
+  if (!s) throw std::invalid_argument("null solver");
+  if (s->sharded) throw std::invalid_argument("a clique-sharded solver has no sparse bound");
+  s->certified_bound(objective, gamma, certified, ms);
+  API_END
+}
+
+int nnsdp_cert_plan(const nnsdp_problem* p, const nnsdp_options* o, int32_t* n, int32_t* n_super, int32_t* max_front, int64_t* fill,
+                    int32_t* supported, int32_t* col_start, int32_t* row_ptr, int32_t* row_idx) {
+  API_BEGIN
+  if (!p || !o) throw std::invalid_argument("null argument");
+  if (o->decomp_mode < NNSDP_DECOMP_DENSE || o->decomp_mode > NNSDP_DECOMP_AUTO) throw std::invalid_argument("unrecognized decomp_mode");
+  ProblemCopy P;
+  P.load(p);
+  Congruence C = make_congruence(P, o->normalize != 0, o->interval_guard);
+  const CertPlan pl = make_cert_plan(solver_pattern(P, C, o->decomp_mode));
+  if (n) *n = pl.n;
+  if (n_super) *n_super = pl.n_super;
+  if (max_front) *max_front = pl.max_front;
+  if (fill) *fill = pl.fill;
+  if (supported) *supported = pl.supported ? 1 : 0;
+  if (col_start) std::copy(pl.col_start.begin(), pl.col_start.end(), col_start);
+  if (row_ptr) std::copy(pl.row_ptr.begin(), pl.row_ptr.end(), row_ptr);
+  if (row_idx) std::copy(pl.row_idx.begin(), pl.row_idx.end(), row_idx);
+  API_END
+}
+
+int nnsdp_sparse_nsd(int32_t n, int32_t n_cliques, const int32_t* ptr, const int32_t* idx, int32_t batch, const double* mats, int32_t* ok,
+                     double* min_pivot, double* schur, double* kernel_ms) {
+  API_BEGIN
+  if (n < 1 || n_cliques < 1 || !ptr || !idx) throw std::invalid_argument("null / empty pattern");
+  if (batch < 0) throw std::invalid_argument("batch must be >= 0");
+  if (batch == 0) return 0;
+  if (!mats || !ok) throw std::invalid_argument("null argument");
+  std::vector<std::vector<int>> cl(n_cliques);
+  for (int k = 0; k < n_cliques; ++k) {
+    if (ptr[k + 1] < ptr[k]) throw std::invalid_argument("clique pointers must be nondecreasing");
+    for (int q = ptr[k]; q < ptr[k + 1]; ++q) {
+      if (idx[q] < 0 || idx[q] >= n) throw std::invalid_argument("clique index out of range");
+      cl[k].push_back(idx[q]);
+    }
+  }
+  const Pattern pat = build_pattern(n, cl);
+  if (pat.pos(n - 1, n - 1) < 0) throw std::invalid_argument("the affine index n - 1 must lie in some clique");
+  const size_t nn = (size_t)n * n;
+  std::vector<double> z((size_t)batch * pat.NE);
+  for (int b = 0; b < batch; ++b) {
+    const double* M = mats + b * nn;
+    for (int j = 0; j < n; ++j)
+      for (int i = 0; i < n; ++i) {
+        const int e = pat.pos(i, j);
+        if (e < 0) {
+          if (M[(size_t)j * n + i] != 0.0) throw std::invalid_argument("matrix " + std::to_string(b) + " has a non-zero entry outside the clique pattern");
+        } else if (i >= j) z[(size_t)b * pat.NE + e] = i == j ? M[(size_t)j * n + i] : M[(size_t)j * n + i] * M_SQRT2;
+      }
+  }
+  CertPlan pl = make_cert_plan(pat);
+  if (!pl.supported) {
+    g_err = "sparse NSD check: largest front " + std::to_string(pl.max_front) + " exceeds " + std::to_string(kCertFrontMax);
+    return -2;
+  }
+  require_gpu();
+  CertDev cd;
+  cd.upload(std::move(pl));
+  DBuf<double> dz;
+  dz.upload(z);
+  hipEvent_t e0, e1;
+  HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
+  cd.reserve(batch);
+  HIPCHK(hipEventRecord(e0, nullptr));
+  cd.launch(dz.p, pat.NE, batch, nullptr);
+  HIPCHK(hipEventRecord(e1, nullptr));
+  HIPCHK(hipDeviceSynchronize());
+  float ms = 0;
+  HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+  if (kernel_ms) *kernel_ms = ms;
+  HIPCHK(hipMemcpy(ok, cd.ok.p, batch * sizeof(int), hipMemcpyDeviceToHost));
+  if (min_pivot) HIPCHK(hipMemcpy(min_pivot, cd.minp.p, batch * sizeof(double), hipMemcpyDeviceToHost));
+  if (schur) HIPCHK(hipMemcpy(schur, cd.schur.p, batch * sizeof(double), hipMemcpyDeviceToHost));
+  if (schur) {      // a candidate that failed has no Schur complement: its slot reports the first failing column instead
+    const std::vector<int> fc = cd.fail.download();
+    for (int b = 0; b < batch; ++b) if (!ok[b]) schur[b] = (double)fc[b];
   }
   API_END
 }

@@ -3186,3 +3186,5 @@ __global__ __launch_bounds__(kThreads) void k_apply_At(int ng, const int* __rest
 }
 
 }  // namespace nnsdp
+
+#include "cert_chol.hpp"

@@ -4,7 +4,8 @@ from .methods import (  # noqa: F401
     FeedFwdNet, QcInputBox, QcSafety, QcReachHplane, QcReachCircle, QcReachEllipsoid,
     QcActivBounded, QcActivSector, SafetyQuery, ReachQuery, AdmmSdpOptions, QuerySolution,
     SingleDecomp, DoubleDecomp, DoubleRelaxDecomp, PathDecomp, AutoDecomp, DenseCone, Solver, SolverBatch, SolverFamily, same_family,
-    runQuery, runQueries, solveQuery, makeZ, adjoint, makeCliques, project_psd_batched, project_psd_warm, comm_unique_id, shardPlan,
+    runQuery, runQueries, solveQuery, makeZ, adjoint, makeCliques, project_psd_batched, project_psd_warm, comm_unique_id, shardPlan, certPlan, sparse_nsd,
+    TARGET_OFF, TARGET_OBJECTIVE, TARGET_FEASIBLE,
 )
 from .frontend import (  # noqa: F401
     read_nnet, evalFeedFwdNet, evalFeedFwdNetBatch, sampleTrajs, randomNetwork, makeIntervalsInfo, makeQcActivs, approxEllipsoid,

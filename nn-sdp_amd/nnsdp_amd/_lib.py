@@ -100,6 +100,10 @@ SYMBOLS = [
     ("nnsdp_project_psd_warm_state", C.c_int, [C.c_int32, c_int32_p, c_double_p, c_double_p, C.c_double, C.c_int32, c_double_p, c_int32_p, c_double_p, c_int32_p]),
     ("nnsdp_comm_unique_id", C.c_int, [C.c_char_p]),
     ("nnsdp_shard_plan", C.c_int, [C.POINTER(Problem), C.POINTER(Options), C.c_int32, c_int32_p, c_int32_p, c_int32_p]),
+    ("nnsdp_solver_set_target", C.c_int, [C.c_void_p, C.c_int32, C.c_double]),
+    ("nnsdp_solver_certified_bound", C.c_int, [C.c_void_p, c_double_p, c_double_p, c_int32_p, c_double_p]),
+    ("nnsdp_cert_plan", C.c_int, [C.POINTER(Problem), C.POINTER(Options), c_int32_p, c_int32_p, c_int32_p, C.POINTER(C.c_int64), c_int32_p, c_int32_p, c_int32_p, c_int32_p]),
+    ("nnsdp_sparse_nsd", C.c_int, [C.c_int32, C.c_int32, c_int32_p, c_int32_p, C.c_int32, c_double_p, c_int32_p, c_double_p, c_double_p, c_double_p]),
     ("nnsdp_solver_set_comm", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_char_p]),
     ("nnsdp_solver_set_comm_callback", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, ALLREDUCE_FN, C.c_void_p]),
     ("nnsdp_solver_set_comm_ipc", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, ALLREDUCE_FN, C.c_void_p]),

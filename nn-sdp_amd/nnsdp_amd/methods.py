@@ -27,6 +27,7 @@ import numpy as np
 from . import _lib
 
 QUERY_SAFETY, QUERY_REACH = 0, 1
+TARGET_OFF, TARGET_OBJECTIVE, TARGET_FEASIBLE = 0, 1, 2      # nnsdp_solver_set_target modes
 ACTIV_RELU, ACTIV_TANH = 0, 1
 
 
@@ -233,6 +234,17 @@ class AdmmSdpOptions:
     interval_guard: float = 5e-5   # relative floor on neuron interval half-widths inside the solver (see include/nnsdp.h)
     minv_mode: int = 0             # 0 auto, 1 dense M^-1, 2 structured M^-1 (block-banded by layer + low rank; see include/nnsdp.h)
     proj_refine: int = 1           # GEMM-only refinement of the persistent eigenbasis in front of the Jacobi sweeps: 0 off, 1, 2 (see include/nnsdp.h)
+    # decide a target instead of converging (nnsdp_solver_set_target; not part of the C struct: applied to the handle after create).
+    # target: units of objective_value; target_mode None = TARGET_OBJECTIVE when a target is given, else off; TARGET_FEASIBLE needs none
+    target: Optional[float] = None
+    target_mode: Optional[int] = None
+
+    def target_setting(self):
+        """(mode, target) as handed to nnsdp_solver_set_target"""
+        mode = self.target_mode if self.target_mode is not None else (TARGET_OBJECTIVE if self.target is not None else TARGET_OFF)
+        if int(mode) == TARGET_OBJECTIVE and self.target is None:
+            raise ValueError("target_mode = TARGET_OBJECTIVE needs a target")
+        return int(mode), float(self.target if self.target is not None else 0.0)
 
     def to_c(self) -> _lib.Options:
         o = _lib.Options()
@@ -371,7 +383,7 @@ def _solution(cp: _CProblem, r, bufs) -> QuerySolution:
                    n_cliques=r.n_cliques, max_clique=r.max_clique,
                    eig_flops_per_iter=r.eig_flops_per_iter, eig_bytes_per_iter=r.eig_bytes_per_iter,
                    avg_sweeps=r.avg_sweeps, objective_admm=r.objective_admm, polish_shift=r.polish_shift,
-                   refine_blocks=[int(v) for v in r.refine_blocks])
+                   refine_blocks=[int(v) for v in r.refine_blocks], sparse_bound_calls=0)
     return QuerySolution(objective_value=r.objective, values=values,
                          termination_status=lib.nnsdp_status_string(r.status).decode(),
                          total_time=r.t_total, setup_time=r.t_setup, solve_time=r.t_solve, summary=summary)
@@ -391,14 +403,21 @@ def _apply_obj_func(query, soln: QuerySolution) -> QuerySolution:
 def runQuery(query, opts: AdmmSdpOptions) -> QuerySolution:
     """Methods.runQuery(query, opts) with opts::AdmmSdpOptions (src/Methods/Methods.jl:91-131)."""
     lib = _lib.load()
-    cp = _CProblem(query)
-    o = opts.to_c()
-    r, bufs = _alloc_result(cp)
-    _lib.check(lib.nnsdp_solve(C.byref(cp.p), C.byref(o), C.byref(r)))
-    soln = _apply_obj_func(query, _solution(cp, r, bufs))
+    if opts.target_setting()[0] != TARGET_OFF:       # a target lives on the handle: create, set, run
+        sv = Solver(query, opts)
+        try:
+            soln = sv.run()
+        finally:
+            sv.close()
+    else:
+        cp = _CProblem(query)
+        o = opts.to_c()
+        r, bufs = _alloc_result(cp)
+        _lib.check(lib.nnsdp_solve(C.byref(cp.p), C.byref(o), C.byref(r)))
+        soln = _apply_obj_func(query, _solution(cp, r, bufs))
     if opts.verbose:
         print(f"setup: {soln.setup_time:.3f} \tsolve: {soln.solve_time:.3f} \ttotal: {soln.total_time:.3f} \t"
-              f"obj: {soln.objective_value:.5f} ({soln.termination_status}) \tλmax: {r.lambda_max:.7f}")
+              f"obj: {soln.objective_value:.5f} ({soln.termination_status}) \tλmax: {soln.summary['lambda_max']:.7f}")
     return soln
 
 
@@ -419,6 +438,25 @@ class Solver:
         else:
             self.o = _parent.o
             _lib.check(self.lib.nnsdp_solver_create_sibling(_parent.h, C.byref(self.cp.p), C.byref(self.h)))
+        if opts is not None and opts.target_setting()[0] != TARGET_OFF:
+            self.set_target(*opts.target_setting())
+
+    def set_target(self, mode: int, target: float = 0.0) -> None:
+        """nnsdp_solver_set_target: TARGET_OBJECTIVE (reach: stop once a rigorous bound <= target is certified, or once the estimates
+        exclude it), TARGET_FEASIBLE (safety: stop at the first certificate), TARGET_OFF.  Before or between runs."""
+        _lib.check(self.lib.nnsdp_solver_set_target(self.h, int(mode), float(target)))
+
+    def certified_bound(self):
+        """(objective, gamma, certified, milliseconds): the rigorous bound of the current iterate through the sparse Cholesky of -Z
+        (gamma >= 0 exactly feasible, reference coordinates).  Does not touch the iteration state."""
+        obj, ok, ms = C.c_double(), C.c_int32(), C.c_double()
+        g = np.zeros(self.cp.ngamma)
+        _lib.check(self.lib.nnsdp_solver_certified_bound(self.h, C.byref(obj), g.ctypes.data_as(_lib.c_double_p), C.byref(ok), C.byref(ms)))
+        return obj.value, g, bool(ok.value), ms.value
+
+    def cert_plan(self):
+        """certPlan of this solver's (query, options)"""
+        return _cert_plan(self.cp, self.o)
 
     def sibling(self, query) -> "Solver":
         """A solver for `query` that shares this one's set-up (operator, tables, M^-1) by reference count: `query` may differ from
@@ -528,15 +566,20 @@ class Solver:
         _lib.check(self.lib.nnsdp_solver_residuals(self.h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
         return a.value, b.value, c.value, d.value
 
+    def _soln(self, r, bufs) -> QuerySolution:
+        soln = _apply_obj_func(self.query, _solution(self.cp, r, bufs))
+        soln.summary["sparse_bound_calls"] = int(self.info(12))
+        return soln
+
     def run(self) -> QuerySolution:
         r, bufs = _alloc_result(self.cp)
         _lib.check(self.lib.nnsdp_solver_run(self.h, C.byref(r)))
-        return _apply_obj_func(self.query, _solution(self.cp, r, bufs))
+        return self._soln(r, bufs)
 
     def finish(self) -> QuerySolution:
         r, bufs = _alloc_result(self.cp)
         _lib.check(self.lib.nnsdp_solver_finish(self.h, C.byref(r)))
-        return _apply_obj_func(self.query, _solution(self.cp, r, bufs))
+        return self._soln(r, bufs)
 
     def close(self):
         if self.h:
@@ -563,6 +606,49 @@ def shardPlan(query, opts: AdmmSdpOptions, nranks: int):
     _lib.check(lib.nnsdp_shard_plan(C.byref(cp.p), C.byref(o), int(nranks), C.byref(n), bn.ctypes.data_as(_lib.c_int32_p),
                                     st.ctypes.data_as(_lib.c_int32_p)))
     return bn.tolist(), st.tolist()
+
+
+def _cert_plan(cp: "_CProblem", o) -> Dict[str, Any]:
+    lib = _lib.load()
+    n, ns, mf, sup, fill = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64()
+    head = (C.byref(cp.p), C.byref(o), C.byref(n), C.byref(ns), C.byref(mf), C.byref(fill), C.byref(sup))
+    _lib.check(lib.nnsdp_cert_plan(*head, None, None, None))
+    cs = np.zeros(ns.value + 1, dtype=np.int32)
+    rp = np.zeros(ns.value + 1, dtype=np.int32)
+    _lib.check(lib.nnsdp_cert_plan(*head, cs.ctypes.data_as(_lib.c_int32_p), rp.ctypes.data_as(_lib.c_int32_p), None))
+    ri = np.zeros(max(int(rp[-1]), 1), dtype=np.int32)
+    _lib.check(lib.nnsdp_cert_plan(*head, None, None, ri.ctypes.data_as(_lib.c_int32_p)))
+    rows = [ri[rp[s]:rp[s + 1]].tolist() for s in range(ns.value)]
+    return dict(n=n.value, n_super=ns.value, max_front=mf.value, fill=int(fill.value), supported=bool(sup.value),
+                col_start=cs.tolist(), rows=rows)
+
+
+def certPlan(query, opts: AdmmSdpOptions) -> Dict[str, Any]:
+    """nnsdp_cert_plan: the plan of the sparse NSD check for (query, options) - n (reduced dimension), n_super, col_start (supernode s
+    = columns col_start[s] .. col_start[s+1]-1; the affine index n-1 is no supernode), rows (per supernode: the rows below its diagonal
+    block, fill included, the affine index last), max_front, fill, supported (max_front <= 128).  Host only: needs no GPU."""
+    return _cert_plan(_CProblem(query), opts.to_c())
+
+
+def sparse_nsd(n: int, cliques, mats):
+    """nnsdp_sparse_nsd (test / diagnostic entry): the sparse NSD check of dense symmetric n x n matrices on the clique pattern
+    `cliques` (index n-1 = affine index) -> (ok, min_pivot, schur, kernel milliseconds); schur[b] of a failed candidate holds its
+    first failing column.  NnsdpError with code -1 for an entry outside the pattern, -2 for a front above 128."""
+    lib = _lib.load()
+    mats = np.ascontiguousarray(np.stack([np.asarray(m, dtype=np.float64).T for m in mats]))     # (column-major per matrix)
+    B = mats.shape[0]
+    if mats.shape[1:] != (n, n):
+        raise ValueError("every matrix must be n x n")
+    ptr = np.zeros(len(cliques) + 1, dtype=np.int32)
+    ptr[1:] = np.cumsum([len(c) for c in cliques])
+    idx = np.asarray([i for c in cliques for i in c], dtype=np.int32)
+    ok = np.zeros(B, dtype=np.int32)
+    mp, sc = np.zeros(B), np.zeros(B)
+    ms = C.c_double()
+    _lib.check(lib.nnsdp_sparse_nsd(int(n), len(cliques), ptr.ctypes.data_as(_lib.c_int32_p), idx.ctypes.data_as(_lib.c_int32_p), B,
+                                    mats.ctypes.data_as(_lib.c_double_p), ok.ctypes.data_as(_lib.c_int32_p),
+                                    mp.ctypes.data_as(_lib.c_double_p), sc.ctypes.data_as(_lib.c_double_p), C.byref(ms)))
+    return ok, mp, sc, ms.value
 
 
 def comm_unique_id() -> bytes:
@@ -639,7 +725,7 @@ class SolverBatch:
         for s, code in zip(self.solvers, st):
             r, bufs = _alloc_result(s.cp)
             _lib.check(self.lib.nnsdp_solver_finish_status(s.h, int(code), C.byref(r)))
-            out.append(_apply_obj_func(s.query, _solution(s.cp, r, bufs)))
+            out.append(s._soln(r, bufs))
         return out
 
     def residuals(self):
@@ -706,15 +792,23 @@ class SolverFamily(SolverBatch):
     members, each member's result bit-identical to what it computes alone.  Every query must satisfy same_family with the first;
     the library raises NnsdpError otherwise."""
 
-    def __init__(self, queries, opts: AdmmSdpOptions):
+    def __init__(self, queries, opts: AdmmSdpOptions, targets=None):
         queries = list(queries)
         if not queries:
             raise ValueError("a family needs at least one query")
+        if targets is not None and len(targets) != len(queries):
+            raise ValueError("one target (or None) per query")
         self._own = True
         solvers = [Solver(queries[0], opts)]
         try:
             for q in queries[1:]:
                 solvers.append(solvers[0].sibling(q))
+            # every member carries its own target: the options' one, or `targets` (None entries: no target for that member)
+            for i, sv in enumerate(solvers):
+                if targets is not None:
+                    sv.set_target(TARGET_OFF if targets[i] is None else TARGET_OBJECTIVE, 0.0 if targets[i] is None else targets[i])
+                elif i > 0 and opts.target_setting()[0] != TARGET_OFF:
+                    sv.set_target(*opts.target_setting())
             self._open(solvers)
         except Exception:
             for s in solvers:
@@ -734,6 +828,8 @@ def _shared_solvers(queries, optl) -> List[Solver]:
                 solvers[i] = Solver(q, o)
             else:
                 solvers[i] = solvers[head].sibling(q)
+                if o.target_setting()[0] != TARGET_OFF:
+                    solvers[i].set_target(*o.target_setting())
     except Exception:
         for s in solvers:
             if s is not None:

@@ -294,7 +294,7 @@ def safetyFromReach(soln: M.QuerySolution, h: float, h0: float = 0.0) -> M.Query
 
 def verifyAcasSpec(net: M.FeedFwdNet, spec, beta: int, opts: M.AdmmSdpOptions,
                    solve: Callable[[Any, M.AdmmSdpOptions], M.QuerySolution] = None, log: Callable[[str], None] = None,
-                   batch_clause: bool = False, via_reach: bool = False, share_setup: bool = False):
+                   batch_clause: bool = False, via_reach: bool = False, share_setup: bool = False, decide_early: bool = False):
     """Goes through the conjunction; a clause holds as soon as one of its sub-queries is certified, the spec fails as
     soon as a clause has none (experiments/acas.jl:87-137).  -> (solutions tried, number of queries, status).
     batch_clause: the sub-queries of a clause are independent SDPs on one network - solve them in lockstep through the
@@ -304,7 +304,11 @@ def verifyAcasSpec(net: M.FeedFwdNet, spec, beta: int, opts: M.AdmmSdpOptions,
     via_reach: True = decide every literal through the equivalent reach-hyperplane query (reachForm / safetyFromReach);
     "auto" = first give the feasibility form 500 iterations per literal (failed attempts are not recorded).  The
     feasibility form 'min sum(gamma)' of the reference needs an interior-point solver to FAIL quickly; the reach form
-    ends in bounded time either way and reports the margin."""
+    ends in bounded time either way and reports the margin.
+    decide_early: a literal needs a decision, not the tightest bound - every literal's solve gets a target (nnsdp_solver_set_target)
+    and stops as soon as a rigorous certificate decides it: in the reach form the target is the offset h - h0 (TARGET_CERTIFIED once
+    a feasible point with bound <= h - h0 exists, TARGET_UNREACHABLE once the estimates exclude it), in the feasibility form the
+    first certificate (TARGET_FEASIBLE).  The certificate is checked as always (safetyFromReach / isSolutionGood), whatever the status."""
     solve = solve or M.solveQuery
     cnf = loadReluQueriesCnf(net, spec, beta)
     num_queries = sum(len(c) for c in cnf)
@@ -327,8 +331,14 @@ def verifyAcasSpec(net: M.FeedFwdNet, spec, beta: int, opts: M.AdmmSdpOptions,
             if holds:
                 continue
         forms = [reachForm(q) for q in clause] if via_reach else [(q, None, None) for q in clause]
+        if not decide_early:
+            lopts = [opts] * len(forms)
+        elif via_reach:
+            lopts = [dataclasses.replace(opts, target=f[1] - f[2], target_mode=M.TARGET_OBJECTIVE) for f in forms]
+        else:
+            lopts = [dataclasses.replace(opts, target=None, target_mode=M.TARGET_FEASIBLE)] * len(forms)
         if batch_clause and len(clause) > 1:
-            got = M.runQueries([f[0] for f in forms], opts, share_setup=share_setup)
+            got = M.runQueries([f[0] for f in forms], lopts if decide_early else opts, share_setup=share_setup)
             got = [safetyFromReach(s, f[1], f[2]) if via_reach else s for s, f in zip(got, forms)]
             solns.extend(got)
             holds = any(isSolutionGood(s) for s in got)
@@ -336,7 +346,7 @@ def verifyAcasSpec(net: M.FeedFwdNet, spec, beta: int, opts: M.AdmmSdpOptions,
                 log(f"conj {ci + 1}/{len(cnf)}: {len(clause)} subqueries in one batch, certified: {[isSolutionGood(s) for s in got]}")
         else:
             for qi, (q, h, h0) in enumerate(forms):
-                s = solve(q, opts)
+                s = solve(q, lopts[qi])
                 if via_reach:
                     s = safetyFromReach(s, h, h0)
                 solns.append(s)
