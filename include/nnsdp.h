@@ -335,6 +335,20 @@ int nnsdp_make_intervals_activ(int32_t K, const int32_t* xdims, const double* M,
 int nnsdp_eval_network(int32_t K, const int32_t* xdims, const double* M, int32_t activ, int64_t N, const double* X, double* Y,
                        double* kernel_ms);
 
+/* CROWN-sliced bounds (the algorithm of nnsdp_make_intervals) for nbox input boxes of ONE network in one launch, fp64: the
+ * screening stage of input splitting (nnsdp_amd/split.py), one workgroup per box, the A W_j products of the backward passes on
+ * fp64 MFMA (csrc/crown_batch.hpp).  The host routine keeps float32 for parity with the reference; this one has no reference
+ * counterpart and keeps every quantity in double, so the two agree to float32 level only.
+ * x1min / x1max: xdims[0] x nbox column-major.  Outputs (HOST pointers, any may be NULL), column-major, one column per box:
+ * acymin/acymax/acxmin/acxmax [acdim x nbox], ymin/ymax [xdims[K] x nbox].  ReLU only; every width (xdims[0..K]) <= 64.
+ * -1 with a message otherwise (Tanh, a wider layer, x1min > x1max, NaN or an infinite bound); nbox = 0 returns 0.  The argument
+ * checks need no GPU.
+ * kernel_ms (may be NULL): HIP-event time of the launch. */
+int nnsdp_make_intervals_batch(int32_t K, const int32_t* xdims, const double* M, int32_t activ, int32_t nbox,
+                               const double* x1min, const double* x1max,
+                               double* acymin, double* acymax, double* acxmin, double* acxmax,
+                               double* ymin, double* ymax, double* kernel_ms);
+
 /* Batched projection onto the PSD cone, the hot kernel (replaces the cone handling inside MOSEK;
  * reference of the arithmetic: LinearAlgebra.eigen on Symmetric).  mats: `batch` symmetric
  * matrices back to back, matrix b is n[b] x n[b] column-major.  Matrices up to 160 go through the LDS-resident Jacobi kernel

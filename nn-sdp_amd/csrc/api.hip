@@ -24,6 +24,7 @@
 #include "minv.hpp"
 #include "intervals.hpp"
 #include "forward.hpp"
+#include "crown_batch.hpp"
 
 namespace nnsdp {
 
@@ -2870,6 +2871,68 @@ int nnsdp_eval_network(int32_t K, const int32_t* xdims, const double* M, int32_t
   HIPCHK(hipEventElapsedTime(&ms, ev.e0, ev.e1));
   if (kernel_ms) *kernel_ms = ms;
   HIPCHK(hipMemcpy(Y, dY.p, (size_t)xd[K] * N * sizeof(double), hipMemcpyDeviceToHost));
+  API_END
+}
+
+int nnsdp_make_intervals_batch(int32_t K, const int32_t* xdims, const double* M, int32_t activ, int32_t nbox,
+                               const double* x1min, const double* x1max,
+                               double* acymin, double* acymax, double* acxmin, double* acxmax,
+                               double* ymin, double* ymax, double* kernel_ms) {
+  API_BEGIN
+  if (K < 2 || !xdims || !M) throw std::invalid_argument("null / empty network (K >= 2 layers are needed)");
+  if (activ == NNSDP_ACTIV_TANH) throw std::invalid_argument("Tanh networks are not supported by the batched intervals: use nnsdp_make_intervals_activ per box");
+  if (activ != NNSDP_ACTIV_RELU) throw std::invalid_argument("unknown activation");
+  std::vector<int> xd(xdims, xdims + K + 1), acoff(K, 0);
+  std::vector<long long> moff(K + 1, 0);
+  for (int k = 0; k <= K; ++k) {
+    if (xd[k] < 1) throw std::invalid_argument("layer widths must be >= 1");
+    if (xd[k] > nnsdp::kCbW)
+      throw std::invalid_argument("layer width " + std::to_string(xd[k]) + " is above 64, the widest layer of the batched intervals");
+  }
+  for (int k = 0; k < K; ++k) {
+    moff[k + 1] = moff[k] + (long long)xd[k + 1] * (xd[k] + 1);
+    if (k > 0) acoff[k] = acoff[k - 1] + xd[k];
+  }
+  const int acdim = acoff[K - 1], n0 = xd[0], ny = xd[K];
+  if (nbox < 0) throw std::invalid_argument("nbox must be >= 0");
+  if (nbox == 0) return 0;
+  if (!x1min || !x1max) throw std::invalid_argument("null argument");
+  for (long long b = 0; b < nbox; ++b)
+    for (int i = 0; i < n0; ++i)
+      if (!std::isfinite(x1min[b * n0 + i]) || !std::isfinite(x1max[b * n0 + i]) || !(x1min[b * n0 + i] <= x1max[b * n0 + i]))
+        throw std::invalid_argument("box " + std::to_string(b) + ": x1min must be <= x1max and both finite (no NaN, no infinity)");
+  require_gpu();
+  DBuf<int> dxd, dao; DBuf<long long> dmo; DBuf<double> dM, dlo, dhi, dscr, dout;
+  dxd.upload(xd); dao.upload(acoff); dmo.upload(moff);
+  const size_t nb = (size_t)nbox, na = nb * acdim, ny_all = nb * ny;
+  dM.alloc(moff[K]); dlo.alloc(nb * n0); dhi.alloc(nb * n0); dscr.alloc(2 * na); dout.alloc(4 * na + 2 * ny_all);
+  HIPCHK(hipMemcpy(dM.p, M, moff[K] * sizeof(double), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dlo.p, x1min, nb * n0 * sizeof(double), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dhi.p, x1max, nb * n0 * sizeof(double), hipMemcpyHostToDevice));
+  nnsdp::CrownArgs a;
+  a.K = K; a.xdims = dxd.p; a.moff = dmo.p; a.acoff = dao.p; a.M = dM.p; a.lo = dlo.p; a.hi = dhi.p; a.scratch = dscr.p;
+  a.acymin = dout.p; a.acymax = dout.p + na; a.acxmin = dout.p + 2 * na; a.acxmax = dout.p + 3 * na;
+  a.ymin = dout.p + 4 * na; a.ymax = a.ymin + ny_all; a.acdim = acdim;
+  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&nnsdp::k_crown_batch), hipFuncAttributeMaxDynamicSharedMemorySize,
+                             (int)nnsdp::kCbLdsBytes));
+  struct Events {   // destroyed on every path out of this function, HIPCHK throws
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    ~Events() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
+  } ev;
+  HIPCHK(hipEventCreate(&ev.e0)); HIPCHK(hipEventCreate(&ev.e1));
+  HIPCHK(hipEventRecord(ev.e0, nullptr));
+  hipLaunchKernelGGL(nnsdp::k_crown_batch, dim3((unsigned)nbox), dim3(256), nnsdp::kCbLdsBytes, nullptr, a);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(ev.e1, nullptr));
+  HIPCHK(hipEventSynchronize(ev.e1));
+  float ms = 0;
+  HIPCHK(hipEventElapsedTime(&ms, ev.e0, ev.e1));
+  if (kernel_ms) *kernel_ms = ms;
+  double* host[6] = {acymin, acymax, acxmin, acxmax, ymin, ymax};
+  const double* dev[6] = {a.acymin, a.acymax, a.acxmin, a.acxmax, a.ymin, a.ymax};
+  for (int o = 0; o < 6; ++o)
+    if (host[o] && (o < 4 ? na : ny_all))
+      HIPCHK(hipMemcpy(host[o], dev[o], (o < 4 ? na : ny_all) * sizeof(double), hipMemcpyDeviceToHost));
   API_END
 }
 

@@ -1,0 +1,222 @@
+// CROWN-sliced interval bounds of many input boxes of one ReLU network in one launch (nnsdp_make_intervals_batch): the
+// screening stage of input splitting (nnsdp_amd/split.py).  The recurrences are those of make_intervals / crown_backward in
+// intervals.hpp, every quantity in fp64 (the host routine keeps float32 for parity with the reference's torch path).
+//
+// One workgroup of 256 threads per box, so a box's bits depend neither on nbox nor on its position.  The coefficient
+// matrices lA, uA of a backward pass (at most 64 x 64) live in LDS, one copy each, stored [column t][row i] with the
+// 16-row tiles of odd columns swapped (cb_idx), so the MFMA operand read - lanes 0..15 column t, lanes 16..31 column
+// t + 1, 16 consecutive rows each - touches 64 different banks.  Per layer j of a pass:
+//   1. the relaxation of layer j from its pre-activation bounds (global scratch, written by an earlier pass of this workgroup),
+//   2. thread (matrix, row) scales its row by the sign-split slopes and accumulates its two bias terms, t ascending,
+//   3. A <- A W_j on v_mfma_f64_16x16x4_f64: wave w owns the output columns 16 w .. 16 w + 15 of both matrices (8 tiles), W_j
+//      is read from global memory / L2 in chunks of kCbChunk k-steps, the tiles stay in registers across a barrier and are
+//      written back over A.
+// Then thread (matrix, row) concretises its row over the box.  No atomics; 68 KB of LDS (69 632 B), two workgroups per CU.
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace nnsdp {
+
+struct CrownArgs {
+  int K;                    // affine layers (>= 2)
+  const int* xdims;         // K + 1 widths, each <= 64
+  const long long* moff;    // offset of M_k = [W_k b_k] (xdims[k+1] x (xdims[k] + 1), column-major) in M
+  const int* acoff;         // K entries: acoff[j] = xdims[1] + ... + xdims[j], where the outputs of affine layer j start; acoff[K-1] = acdim
+  const double* M;
+  const double* lo;         // xdims[0] x nbox, column-major
+  const double* hi;
+  double* scratch;          // 2 acdim per box: CROWN pre-activation bounds (lower, then upper)
+  double *acymin, *acymax, *acxmin, *acxmax;   // acdim x nbox
+  double *ymin, *ymax;      // xdims[K] x nbox
+  int acdim;
+};
+
+static constexpr int kCbW = 64;        // widest layer
+static constexpr int kCbChunk = 8;     // k-steps whose weight operands are in flight together
+static constexpr size_t kCbLdsBytes = (2 * kCbW * kCbW + 8 * kCbW) * sizeof(double);
+
+__device__ __forceinline__ int cb_idx(int t, int i) { return t * kCbW + (i ^ ((t & 1) << 4)); }
+
+// One backward pass for box `box`.  head_identity == 0: bounds of W_{k-1} relu(... ) + b_{k-1}, i.e. the pre-activation of hidden
+// layer k (k < K, raw, to the scratch) or the network output (k == K, post-fixed, to ymin / ymax).  head_identity == 1: the
+// post-activation of hidden layer k through an identity head (post-fixed, to acymin / acymax).
+__device__ void crown_pass(const CrownArgs& a, double* lds, long long box, int k, int head_identity) {
+  double* A[2] = {lds, lds + kCbW * kCbW};
+  double* v_du = lds + 2 * kCbW * kCbW;
+  double* v_dl = v_du + kCbW;
+  double* v_bu = v_dl + kCbW;
+  double* v_bj = v_bu + kCbW;
+  double* v_c = v_bj + kCbW;      // box centre
+  double* v_r = v_c + kCbW;       // box radius
+  double* v_res = v_r + kCbW;     // 2 x 64: a pass's lower / upper results, for the post-fix
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, lr = lane & 15, lc = lane >> 4;
+  const int mat = tid >> 6, row = tid & 63;      // the (matrix, row) a thread owns in the row passes (threads 0..127)
+  const int nout = a.xdims[k];
+  int d = head_identity ? nout : a.xdims[k - 1];
+  const int jtop = head_identity ? k - 1 : k - 2;
+  double bias = 0.0;
+  {
+    const double* Mh = a.M + a.moff[k - 1];
+    for (int idx = tid; idx < nout * d; idx += 256) {
+      const int t = idx / nout, i = idx - t * nout;
+      const double v = head_identity ? (t == i ? 1.0 : 0.0) : Mh[(size_t)t * nout + i];
+      A[0][cb_idx(t, i)] = v;
+      A[1][cb_idx(t, i)] = v;
+    }
+    if (tid < 128 && row < nout && !head_identity) bias = Mh[(size_t)d * nout + row];
+    if (tid < a.xdims[0]) {
+      const double l = a.lo[(size_t)box * a.xdims[0] + tid], u = a.hi[(size_t)box * a.xdims[0] + tid];
+      v_c[tid] = (u + l) / 2.0;
+      v_r[tid] = (u - l) / 2.0;
+    }
+  }
+  __syncthreads();
+  for (int j = jtop; j >= 0; --j) {
+    const int in = a.xdims[j];
+    const double* Mj = a.M + a.moff[j];       // d x (in + 1), column-major
+    if (tid < d) {
+      const double* pre = a.scratch + (size_t)box * 2 * a.acdim + a.acoff[j];
+      const double l = pre[tid], u = pre[a.acdim + tid];
+      const double lrx = l < 0.0 ? l : 0.0;
+      double ur = u > 0.0 ? u : 0.0;
+      ur = ur > lrx + 1e-8 ? ur : lrx + 1e-8;
+      const double du = ur / (ur - lrx);
+      v_du[tid] = du;
+      v_dl[tid] = du > 0.5 ? 1.0 : 0.0;
+      v_bu[tid] = -lrx * du;
+      v_bj[tid] = Mj[(size_t)in * d + tid];
+    }
+    __syncthreads();
+    if (tid < 128 && row < nout) {
+      double* Am = A[mat];
+      double s = 0.0, tl = 0.0;
+      for (int t = 0; t < d; ++t) {
+        const double x = Am[cb_idx(t, row)];
+        const double xp = x > 0.0 ? x : 0.0, xn = x < 0.0 ? x : 0.0;
+        const double du = v_du[t], dl = v_dl[t];
+        s += (mat ? xp : xn) * v_bu[t];
+        const double y = mat ? xp * du + xn * dl : xp * dl + xn * du;
+        Am[cb_idx(t, row)] = y;
+        tl += y * v_bj[t];
+      }
+      bias += s;
+      bias += tl;
+    }
+    __syncthreads();
+    // A (nout x d) <- A W_j (nout x in): MFMA operand a = A[16 it + lr][4 ks + lc] from LDS, b = W_j[4 ks + lc][16 w + lr] from global
+    const int nit = (nout + 15) >> 4, nqt = (in + 15) >> 4, ks = (d + 3) >> 2;
+    d4_t c[2][4];
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+      for (int it = 0; it < 4; ++it) c[m][it] = d4_t{0.0, 0.0, 0.0, 0.0};
+    const int q = 16 * w + lr;
+    if (w < nqt) {
+      for (int k0 = 0; k0 < ks; k0 += kCbChunk) {
+        double bv[kCbChunk];
+#pragma unroll
+        for (int u = 0; u < kCbChunk; ++u) {
+          const int t = 4 * (k0 + u) + lc;
+          bv[u] = (q < in && t < d) ? Mj[(size_t)q * d + t] : 0.0;
+        }
+#pragma unroll
+        for (int u = 0; u < kCbChunk; ++u) {
+          if (k0 + u < ks) {
+            const int t = 4 * (k0 + u) + lc;
+            const int tc = t < d ? t : 0;      // a column past d multiplies a zero of bv: read a written one, never stale bits
+#pragma unroll
+            for (int it = 0; it < 4; ++it) {
+              if (it < nit) {
+                const int i = 16 * it + lr;
+                const bool ok = t < d && i < nout;
+                const double al = ok ? A[0][cb_idx(tc, i)] : 0.0;
+                const double au = ok ? A[1][cb_idx(tc, i)] : 0.0;
+                c[0][it] = __builtin_amdgcn_mfma_f64_16x16x4f64(al, bv[u], c[0][it], 0, 0, 0);
+                c[1][it] = __builtin_amdgcn_mfma_f64_16x16x4f64(au, bv[u], c[1][it], 0, 0, 0);
+              }
+            }
+          }
+        }
+      }
+    }
+    __syncthreads();
+    if (w < nqt && q < in) {
+#pragma unroll
+      for (int it = 0; it < 4; ++it) {
+        if (it < nit) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int i = 16 * it + lc + 4 * r;
+            if (i < nout) {
+              A[0][cb_idx(q, i)] = c[0][it][r];
+              A[1][cb_idx(q, i)] = c[1][it][r];
+            }
+          }
+        }
+      }
+    }
+    d = in;
+    __syncthreads();
+  }
+  if (tid < 128 && row < nout) {
+    const double* Am = A[mat];
+    double s = 0.0, rr = 0.0;
+    for (int t = 0; t < d; ++t) {
+      const double x = Am[cb_idx(t, row)];
+      s += x * v_c[t];
+      rr += fabs(x) * v_r[t];
+    }
+    v_res[mat * kCbW + row] = mat ? s + rr + bias : s - rr + bias;
+  }
+  __syncthreads();
+  if (tid < nout) {
+    const double l = v_res[tid], u = v_res[kCbW + tid];
+    if (!head_identity && k < a.K) {
+      double* pre = a.scratch + (size_t)box * 2 * a.acdim + a.acoff[k - 1];
+      pre[tid] = l;
+      pre[a.acdim + tid] = u;
+    } else {
+      const double fl = l < u ? l : u, fu = fl > u ? fl : u;     // lb = min(lb, ub), ub = max(lb, ub)
+      if (head_identity) {
+        const size_t o = (size_t)box * a.acdim + a.acoff[k - 1] + tid;
+        a.acymin[o] = fl;
+        a.acymax[o] = fu;
+      } else {
+        const size_t o = (size_t)box * nout + tid;
+        a.ymin[o] = fl;
+        a.ymax[o] = fu;
+      }
+    }
+  }
+  __threadfence_block();
+  __syncthreads();
+}
+
+__global__ __launch_bounds__(256) void k_crown_batch(CrownArgs a) {
+  extern __shared__ double cb_lds[];
+  const long long box = blockIdx.x;
+  for (int k = 1; k <= a.K; ++k) {
+    crown_pass(a, cb_lds, box, k, 0);
+    if (k < a.K) crown_pass(a, cb_lds, box, k, 1);
+  }
+  // one interval step per layer for the pre-activations, from the post-fixed bounds of the layer below
+  const int n0 = a.xdims[0];
+  for (int idx = threadIdx.x; idx < a.acdim; idx += 256) {
+    int k = 0;
+    while (idx >= a.acoff[k + 1]) ++k;                   // affine layer k: acoff[k] <= idx < acoff[k + 1]
+    const int r = a.xdims[k + 1], cdim = a.xdims[k], i = idx - a.acoff[k];
+    const double* Mk = a.M + a.moff[k];
+    const double* xl = k ? a.acymin + (size_t)box * a.acdim + a.acoff[k - 1] : a.lo + (size_t)box * n0;
+    const double* xu = k ? a.acymax + (size_t)box * a.acdim + a.acoff[k - 1] : a.hi + (size_t)box * n0;
+    double sl = Mk[(size_t)cdim * r + i], su = sl;
+    for (int j = 0; j < cdim; ++j) {
+      const double wv = Mk[(size_t)j * r + i];
+      if (wv >= 0) { sl += wv * xl[j]; su += wv * xu[j]; }
+      else { sl += wv * xu[j]; su += wv * xl[j]; }
+    }
+    a.acxmin[(size_t)box * a.acdim + idx] = sl;
+    a.acxmax[(size_t)box * a.acdim + idx] = su;
+  }
+}
+
+}  // namespace nnsdp

@@ -9,12 +9,14 @@ from .methods import (  # noqa: F401
 )
 from .frontend import (  # noqa: F401
     read_nnet, evalFeedFwdNet, evalFeedFwdNetBatch, sampleTrajs, randomNetwork, makeIntervalsInfo, makeQcActivs, approxEllipsoid,
-    findEllipsoid, findCircle, findReach2Dpoly, write_scale_csv, runScale, ellipsoidQuery,
+    findEllipsoid, findCircle, findReach2Dpoly, write_scale_csv, runScale, ellipsoidQuery, makeIntervalsBatch,
 )
 from . import _lib  # noqa: F401
 from . import vnnlib  # noqa: F401
 from .vnnlib import (  # noqa: F401
     read_vnnlib, hplaneS, loadVnnlibCnf, loadReluQueriesCnf, verifyAcasSpec, verifyPairs, isSolutionGood, shardPairs, reachForm, safetyFromReach,
 )
+from . import split  # noqa: F401
+from .split import SplitOptions, SplitResult, Leaf, verifySplit  # noqa: F401
 
 __version__ = "0.2.0"

@@ -183,6 +183,62 @@ def makeQcActivs(net: M.FeedFwdNet, x1min, x1max, beta: int):
             M.QcActivSector(acxdim=len(acymin), beta=int(beta), smin=smin, smax=smax, activ=net.activ)]
 
 
+def _net_arrays(net: M.FeedFwdNet):
+    xd = np.asarray(net.xdims, dtype=np.int32)
+    Mp = np.concatenate([np.asfortranarray(Mk, dtype=np.float64).ravel(order="F") for Mk in net.Ms])
+    return xd, Mp
+
+
+def makeIntervalsBatch(net: M.FeedFwdNet, lo, hi, backend: str = "host", workers: int = 16, return_ms: bool = False):
+    """CROWN-sliced bounds of many input boxes of one network: lo / hi are xdims[0] x nbox, one column per box.
+    -> (acymin, acymax, acxmin, acxmax, ymin, ymax), one column per box.
+    backend="gpu":  nnsdp_make_intervals_batch (csrc/crown_batch.hpp), one launch, fp64; ReLU networks with every width <= 64,
+                    anything else raises (no fall-back to the host).
+    backend="host": nnsdp_make_intervals_activ (csrc/intervals.hpp, float32 arithmetic by design) once per box on a thread pool
+                    of at most 16 workers (ctypes releases the GIL); the only route for Tanh networks and wider layers, and the
+                    default until the kernel has been timed against it (tools/split_timing.py)."""
+    lib = _lib.load()
+    xd, Mp = _net_arrays(net)
+    lo = np.asarray(lo, dtype=np.float64)
+    hi = np.asarray(hi, dtype=np.float64)
+    if lo.ndim != 2 or lo.shape[0] != xd[0] or hi.shape != lo.shape:
+        raise ValueError("lo / hi must be xdims[0] x nbox")
+    nbox = lo.shape[1]
+    acdim, ny = int(xd[1:-1].sum()), int(xd[-1])
+    loc, hic = np.ascontiguousarray(lo.T), np.ascontiguousarray(hi.T)          # column-major xdims[0] x nbox
+    outs = [np.zeros((nbox, acdim)) for _ in range(4)] + [np.zeros((nbox, ny)) for _ in range(2)]
+    dp = _lib.c_double_p
+    ms = C.c_double(0.0)
+    if backend == "gpu":
+        _lib.check(lib.nnsdp_make_intervals_batch(net.K, xd.ctypes.data_as(_lib.c_int32_p), Mp.ctypes.data_as(dp), M._activ_code(net.activ),
+                                                  nbox, loc.ctypes.data_as(dp), hic.ctypes.data_as(dp),
+                                                  *[o.ctypes.data_as(dp) for o in outs], C.byref(ms)))
+    elif backend == "host":
+        activ = M._activ_code(net.activ)
+        xdp, Mpp = xd.ctypes.data_as(_lib.c_int32_p), Mp.ctypes.data_as(dp)
+
+        def one(b):
+            rows = [o[b] for o in outs]
+            return lib.nnsdp_make_intervals_activ(net.K, xdp, Mpp, activ, loc[b].ctypes.data_as(dp), hic[b].ctypes.data_as(dp),
+                                                  rows[0].ctypes.data_as(dp), rows[1].ctypes.data_as(dp), rows[2].ctypes.data_as(dp),
+                                                  rows[3].ctypes.data_as(dp), None, None, rows[4].ctypes.data_as(dp), rows[5].ctypes.data_as(dp))
+
+        nw = max(1, min(int(workers), 16, nbox))
+        if nw == 1:
+            for b in range(nbox):
+                _lib.check(one(b))
+        else:
+            from concurrent.futures import ThreadPoolExecutor
+            with ThreadPoolExecutor(max_workers=nw) as pool:
+                codes = list(pool.map(one, range(nbox)))
+            if any(codes):
+                raise _lib.NnsdpError(next(c for c in codes if c), "nnsdp_make_intervals_activ failed for a box of the batch")
+    else:
+        raise ValueError("backend must be 'gpu' or 'host'")
+    res = tuple(o.T for o in outs)
+    return res + (ms.value,) if return_ms else res
+
+
 # ----------------------------------------------------------------------------- f2: callers of the path
 def evalFeedFwdNetBatch(net: M.FeedFwdNet, X, return_ms: bool = False):
     """the network at the columns of X (xdims[0] x N) on the GPU: nnsdp_eval_network (csrc/forward.hpp, fp64 MFMA, one wave per

@@ -1,0 +1,246 @@
+"""Input splitting: decide a disjunctive clause of hyperplane literals on an input box by bisecting the box.
+
+A relaxation over a whole input box is often too loose to decide a literal, and TARGET_UNREACHABLE / ITERATION_LIMIT are final
+answers of a single solve.  verifySplit works level by level on the frontier of open sub-boxes:
+
+  bound    one makeIntervalsBatch call for the whole frontier (csrc/crown_batch.hpp on the GPU, or the host routine per box);
+           a literal  normal' f(x) <= h  is proved on a box when  sum_j max(n_j ymin_j, n_j ymax_j) <= h
+  refute   the network at the box centres (plus `samples` seeded points per box): a point that violates every literal,
+           confirmed by the fp64 numpy evaluation, is a witness
+  sdp      the boxes closest to a proof get one reach-hyperplane SDP per literal (vnnlib.reachForm) with the target h, decided
+           early, in lockstep batches; the literals of a box form one solver family; the activation QCs come from the bounds of
+           the first step (no second interval pass)
+  split    every box still open is bisected along the coordinate that is widest relative to the root box
+
+The driver is deterministic: no random numbers unless samples > 0, and then seeded from the box index.  With
+sdp_per_level = 0 and crown_backend = "host" it needs no GPU.  The reference has no counterpart (it prints :unsafe for a clause
+it could not certify on the whole box, experiments/acas.jl:87-137).
+"""
+from __future__ import annotations
+
+import dataclasses
+import time
+from dataclasses import dataclass, field
+from typing import Any, Dict, List, Optional, Sequence, Tuple
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from . import frontend as F
+from . import methods as M
+from . import vnnlib as V
+
+
+@dataclass
+class SplitOptions:
+    max_boxes: int = 512          # boxes bounded (visited) before the driver gives up
+    max_depth: int = 24           # bisections of one box before the driver gives up
+    sdp_per_level: int = 26       # open boxes per level that get SDPs (0: bounds only)
+    batch: int = 13               # SDPs advanced in lockstep in one batch handle
+    # makeIntervalsBatch backend and where the refutation points are evaluated: "gpu" (csrc/crown_batch.hpp, fp64) or "host".  "host" is
+    # the default until the kernel has been timed against 16 host workers (tools/split_timing.py)
+    crown_backend: str = "host"
+    samples: int = 0              # extra uniform points per open box in the refutation step, seeded from the box index
+
+
+@dataclass
+class Leaf:
+    lo: np.ndarray
+    hi: np.ndarray
+    depth: int
+    proved_by: Optional[str]      # "crown" | "sdp" | None (open)
+    literal: Optional[int]        # index of the literal that was proved
+    bound: Optional[float]        # the proved literal's upper bound of normal' f on the box (open: the smallest excess literal's cheap bound)
+    soln: Any = None              # the reach-form QuerySolution of an "sdp" leaf
+
+
+@dataclass
+class SplitResult:
+    verdict: str                  # "holds" | "violated" | "unknown"
+    leaves: List[Leaf]
+    witness: Optional[np.ndarray]
+    visited: int
+    sdp_solves: int
+    seconds: Dict[str, float] = field(default_factory=dict)
+
+
+@dataclass
+class _Box:
+    lo: np.ndarray
+    hi: np.ndarray
+    cuts: np.ndarray              # bisections per coordinate: the width is the root's times 2^-cuts, exactly comparable
+    index: int = -1
+
+
+def _violates_all(Y, normals, hs) -> np.ndarray:
+    """columns of Y (outputs) at which every literal normal' y <= h is false"""
+    return np.all(normals @ Y > hs[:, None], axis=0)
+
+
+def _solve_boxes(net, todo, normals, hs, beta: int, opts: M.AdmmSdpOptions, batch: int, seconds: Dict[str, float]):
+    """todo: [(box, intervals of that box)] -> per box the list of (reach solution, h0) of its literals.  Boxes are packed into batch
+    handles of at most `batch` SDPs (a box's literals stay together: they are one solver family)."""
+    lib = _lib.load()
+    out, group, count = [], [], 0
+
+    def flush():
+        nonlocal group, count
+        if not group:
+            return
+        queries, optl, h0s = [], [], []
+        for box, (acymin, acymax, acxmin, acxmax, ymin, ymax) in group:
+            x_intvs, acx, o = [(box.lo, box.hi)], [], 0
+            for k in range(1, net.K):
+                n = net.xdims[k]
+                x_intvs.append((acymin[o:o + n], acymax[o:o + n]))
+                acx.append((acxmin[o:o + n], acxmax[o:o + n]))
+                o += n
+            x_intvs.append((ymin, ymax))
+            qin = M.QcInputBox(x1min=box.lo, x1max=box.hi)
+            qa = F.makeQcActivsIntvs(net, x_intvs, acx, beta)
+            for nrm, h in zip(normals, hs):
+                sq = M.SafetyQuery(ffnet=net, qc_input=qin, qc_safety=M.QcSafety(S=V.hplaneS(nrm, h, net)), qc_activs=qa)
+                rq, hh, h0 = V.reachForm(sq, ybounds=(ymin, ymax))
+                queries.append(rq)
+                h0s.append(h0)
+                optl.append(dataclasses.replace(opts, target=hh - h0, target_mode=M.TARGET_OBJECTIVE))
+        t0 = time.perf_counter()
+        sb = M.SolverBatch.from_solvers(M._shared_solvers(queries, optl), own=True)
+        try:
+            t1 = time.perf_counter()
+            st = (C.c_int32 * len(sb.solvers))()
+            _lib.check(lib.nnsdp_batch_run(sb.h, st))
+            t2 = time.perf_counter()
+            solns = []
+            for s, code in zip(sb.solvers, st):
+                r, bufs = M._alloc_result(s.cp)
+                _lib.check(lib.nnsdp_solver_finish_status(s.h, int(code), C.byref(r)))
+                solns.append(s._soln(r, bufs))
+            t3 = time.perf_counter()
+        finally:
+            sb.close()
+        seconds["setup"] += t1 - t0
+        seconds["solve"] += t2 - t1
+        seconds["finish"] += t3 - t2
+        nl = len(normals)
+        for b in range(len(group)):
+            out.append(list(zip(solns[b * nl:(b + 1) * nl], h0s[b * nl:(b + 1) * nl])))
+        group, count = [], 0
+
+    for item in todo:
+        if group and count + len(normals) > max(1, int(batch)):
+            flush()
+        group.append(item)
+        count += len(normals)
+    flush()
+    return out
+
+
+def verifySplit(net: M.FeedFwdNet, x1min, x1max, literals: Sequence[Tuple[Any, float]], beta: int, opts: M.AdmmSdpOptions,
+                split: SplitOptions = None) -> SplitResult:
+    """Decide the clause  OR_i normal_i' f(x) <= h_i  on the box [x1min, x1max]: "holds" when every leaf of the bisection tree has
+    one literal proved on all of it, "violated" with a witness x at which every literal is false, "unknown" when max_boxes or
+    max_depth ends the search (the open leaves are returned as they are)."""
+    split = split or SplitOptions()
+    if split.crown_backend not in ("gpu", "host"):
+        raise ValueError("crown_backend must be 'gpu' or 'host'")
+    t_start = time.perf_counter()
+    root_lo, root_hi = np.array(x1min, dtype=np.float64), np.array(x1max, dtype=np.float64)
+    n0, ny = net.xdims[0], net.xdims[-1]
+    if root_lo.shape != (n0,) or root_hi.shape != (n0,) or not np.all(root_lo <= root_hi):
+        raise ValueError("x1min / x1max must have xdims[0] entries with x1min <= x1max")
+    if not literals:
+        raise ValueError("a clause needs at least one literal")
+    normals = np.array([np.asarray(nrm, dtype=np.float64) for nrm, _ in literals])
+    hs = np.array([float(h) for _, h in literals])
+    if normals.shape != (len(literals), ny):
+        raise ValueError("every normal must have xdims[K] entries")
+    seconds = {"crown": 0.0, "setup": 0.0, "solve": 0.0, "finish": 0.0, "total": 0.0}
+    leaves: List[Leaf] = []
+    visited = sdp_solves = depth = 0
+    splittable = root_hi > root_lo
+    frontier = [_Box(root_lo, root_hi, np.zeros(n0, dtype=np.int64))]
+
+    def done(verdict, witness=None):
+        seconds["total"] = time.perf_counter() - t_start
+        return SplitResult(verdict, leaves, witness, visited, sdp_solves, seconds)
+
+    while frontier:
+        room = int(split.max_boxes) - visited
+        for box in frontier[max(room, 0):]:        # never bounded: open as they are
+            leaves.append(Leaf(box.lo, box.hi, depth, None, None, None))
+        frontier = frontier[:max(room, 0)]
+        if not frontier:
+            return done("unknown")
+        for box in frontier:
+            box.index = visited
+            visited += 1
+        # 1. bound
+        t0 = time.perf_counter()
+        lo, hi = np.stack([b.lo for b in frontier], axis=1), np.stack([b.hi for b in frontier], axis=1)
+        iv = F.makeIntervalsBatch(net, lo, hi, backend=split.crown_backend)
+        seconds["crown"] += time.perf_counter() - t0
+        ymin, ymax = iv[4], iv[5]
+        cheap = np.stack([np.maximum(nrm[:, None] * ymin, nrm[:, None] * ymax).sum(axis=0) for nrm in normals])   # literal x box
+        excess = cheap - hs[:, None]
+        best = np.argmin(excess, axis=0)
+        open_ids = []
+        for b, box in enumerate(frontier):
+            if excess[best[b], b] <= 0.0:
+                leaves.append(Leaf(box.lo, box.hi, depth, "crown", int(best[b]), float(cheap[best[b], b])))
+            else:
+                open_ids.append(b)
+        # 2. refute
+        if open_ids:
+            pts = [0.5 * (lo[:, open_ids] + hi[:, open_ids])]
+            if split.samples > 0:
+                for b in open_ids:
+                    rng = np.random.default_rng(frontier[b].index)
+                    pts.append(lo[:, [b]] + rng.random((n0, int(split.samples))) * (hi[:, [b]] - lo[:, [b]]))
+            X = np.concatenate(pts, axis=1)
+            Y = F.evalFeedFwdNetBatch(net, X) if split.crown_backend == "gpu" else F.evalFeedFwdNet(net, X)
+            for c in np.flatnonzero(_violates_all(Y, normals, hs)):
+                x = X[:, c].copy()
+                if bool(_violates_all(F.evalFeedFwdNet(net, x)[:, None], normals, hs)[0]):     # confirmed in fp64 on the host
+                    for b in open_ids:
+                        leaves.append(Leaf(frontier[b].lo, frontier[b].hi, depth, None, int(best[b]), float(cheap[best[b], b])))
+                    return done("violated", x)
+        # 3. SDP on the open boxes closest to a proof
+        if open_ids and split.sdp_per_level > 0:
+            order = sorted(open_ids, key=lambda b: (excess[best[b], b], b))[:int(split.sdp_per_level)]
+            todo = [(frontier[b], tuple(a[:, b] for a in iv)) for b in order]
+            got = _solve_boxes(net, todo, normals, hs, beta, opts, split.batch, seconds)
+            sdp_solves += len(order) * len(hs)
+            for b, res in zip(order, got):
+                for li, (s, h0) in enumerate(res):
+                    rho = float(s.objective_value) + h0
+                    if s.termination_status == "TARGET_CERTIFIED" and V.isSolutionGood(s) and rho <= hs[li]:
+                        leaves.append(Leaf(frontier[b].lo, frontier[b].hi, depth, "sdp", li, rho, s))
+                        open_ids.remove(b)
+                        break
+        if not open_ids:
+            break
+        # 5. stop / 4. split
+        if visited >= split.max_boxes or depth >= split.max_depth or not np.any(splittable):
+            for b in open_ids:
+                leaves.append(Leaf(frontier[b].lo, frontier[b].hi, depth, None, int(best[b]), float(cheap[best[b], b])))
+            return done("unknown")
+        nxt = []
+        for b in open_ids:
+            box = frontier[b]
+            j = int(np.argmin(np.where(splittable, box.cuts, np.iinfo(np.int64).max)))     # widest relative to the root, lowest index on ties
+            mid = 0.5 * (box.lo[j] + box.hi[j])
+            cuts = box.cuts.copy()
+            cuts[j] += 1
+            left_hi, right_lo = box.hi.copy(), box.lo.copy()
+            left_hi[j] = mid
+            right_lo[j] = mid
+            nxt.append(_Box(box.lo, left_hi, cuts))
+            nxt.append(_Box(right_lo, box.hi, cuts.copy()))
+        frontier = nxt
+        depth += 1
+    # every box of the last level was proved; boxes that the budget kept from being bounded are open leaves, and one open leaf is
+    # enough for "unknown"
+    return done("holds" if all(lf.proved_by is not None for lf in leaves) else "unknown")

@@ -292,9 +292,21 @@ def safetyFromReach(soln: M.QuerySolution, h: float, h0: float = 0.0) -> M.Query
                            total_time=soln.total_time, setup_time=soln.setup_time, solve_time=soln.solve_time, summary=summ)
 
 
+class SpecStatus(str):
+    """verifyAcasSpec's status when it may split: "safe" | "violated" | "unknown", a str with the witness (or None) and the
+    SplitResult of every clause that went through verifySplit"""
+
+    def __new__(cls, value, witness=None, splits=()):
+        obj = super().__new__(cls, value)
+        obj.witness = witness
+        obj.splits = list(splits)
+        return obj
+
+
 def verifyAcasSpec(net: M.FeedFwdNet, spec, beta: int, opts: M.AdmmSdpOptions,
                    solve: Callable[[Any, M.AdmmSdpOptions], M.QuerySolution] = None, log: Callable[[str], None] = None,
-                   batch_clause: bool = False, via_reach: bool = False, share_setup: bool = False, decide_early: bool = False):
+                   batch_clause: bool = False, via_reach: bool = False, share_setup: bool = False, decide_early: bool = False,
+                   split=None):
     """Goes through the conjunction; a clause holds as soon as one of its sub-queries is certified, the spec fails as
     soon as a clause has none (experiments/acas.jl:87-137).  -> (solutions tried, number of queries, status).
     batch_clause: the sub-queries of a clause are independent SDPs on one network - solve them in lockstep through the
@@ -308,8 +320,13 @@ def verifyAcasSpec(net: M.FeedFwdNet, spec, beta: int, opts: M.AdmmSdpOptions,
     decide_early: a literal needs a decision, not the tightest bound - every literal's solve gets a target (nnsdp_solver_set_target)
     and stops as soon as a rigorous certificate decides it: in the reach form the target is the offset h - h0 (TARGET_CERTIFIED once
     a feasible point with bound <= h - h0 exists, TARGET_UNREACHABLE once the estimates exclude it), in the feasibility form the
-    first certificate (TARGET_FEASIBLE).  The certificate is checked as always (safetyFromReach / isSolutionGood), whatever the status."""
+    first certificate (TARGET_FEASIBLE).  The certificate is checked as always (safetyFromReach / isSolutionGood), whatever the status.
+    split: None = a clause that is not certified on its whole box ends the spec as "unsafe", as the reference does.  A SplitOptions
+    hands such a clause to split.verifySplit (bisection of the input box) first; the spec then ends as "safe", as "violated" (a point of
+    the box inside the clause's unsafe polytope was found) or as "unknown" - a SpecStatus, a str that also carries `witness` and
+    `splits` (the SplitResult of every clause that was split).  The safety certificates of the SDP-proved leaves join the solutions."""
     solve = solve or M.solveQuery
+    splits = []
     cnf = loadReluQueriesCnf(net, spec, beta)
     num_queries = sum(len(c) for c in cnf)
     solns, status = [], "safe"
@@ -357,9 +374,29 @@ def verifyAcasSpec(net: M.FeedFwdNet, spec, beta: int, opts: M.AdmmSdpOptions,
                 if good:
                     holds = True
                     break
+        if not holds and split is not None:
+            from . import split as SP
+            q0 = clause[0]
+            d1, dK = net.xdims[0], net.xdims[-1]
+            lits = [(np.asarray(q.qc_safety.S)[d1:d1 + dK, -1].copy(), -0.5 * float(np.asarray(q.qc_safety.S)[-1, -1])) for q in clause]
+            res = SP.verifySplit(net, q0.qc_input.x1min, q0.qc_input.x1max, lits, beta, opts, split)
+            splits.append(res)
+            solns.extend(safetyFromReach(lf.soln, lits[lf.literal][1], lf.bound - float(lf.soln.objective_value))
+                         for lf in res.leaves if lf.proved_by == "sdp")
+            if log:
+                log(f"conj {ci + 1}/{len(cnf)}: split verdict {res.verdict} after {res.visited} boxes and {res.sdp_solves} SDPs")
+            if res.verdict == "holds":
+                continue
+            # a witness of the split violates  normal' y <= h  with h = -b - eps: it is a counterexample of the spec only inside A y <= b
+            y = F.evalFeedFwdNet(net, res.witness) if res.witness is not None else None
+            inside = y is not None and all(float(nrm @ y) >= h + SPEC_EPS for nrm, h in lits)
+            status = SpecStatus("violated" if inside else "unknown", res.witness if inside else None, splits)
+            break
         if not holds:
             status = "unsafe"
             break
+    if split is not None and isinstance(status, str) and not isinstance(status, SpecStatus):
+        status = SpecStatus(status, None, splits)
     return solns, num_queries, status
 
 

@@ -1,0 +1,81 @@
+#!/usr/bin/env python3
+"""Batched CROWN bounds: the GPU kernel against the host routine, and where one verifySplit spends its time.
+usage: python tools/split_timing.py [case ...]   cases: W10-D5 W40-D20 acas-shape   (default: all)
+Writes profiles/split_timing_<case>.json (or $SPLIT_TIMING_OUT/...).  Per case:
+  crown    nnsdp_make_intervals_batch at nbox = 1, 256, 4096 sub-boxes of the root box: HIP-event time of the launch (median of 7 after 2
+           warm launches) and the wall-clock of the whole call with its copies; beside it the host backend (nnsdp_make_intervals_activ per
+           box) with 1 and 16 workers on the same boxes, wall-clock, one run (the 1-worker run on at most 256 boxes, scaled to nbox)
+  split    one verifySplit of the literal y_0 <= s + 0.25 (c0 - s) (s: sampled maximum, c0: root cheap bound): verdict, visited, SDPs and
+           the `seconds` breakdown crown / setup / solve / finish / total
+Timings are host clocks of whole calls unless marked kernel; the GPU is shared, so expect a few per cent of spread."""
+import json, os, statistics, sys, time
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "nn-sdp_amd")); sys.path.insert(0, os.path.join(ROOT, "tests"))
+import numpy as np
+import helpers, nnsdp_amd as na
+
+
+def case(name):
+    if name in ("W10-D5", "W40-D20"):
+        z = np.load(os.path.join(helpers.GOLDEN, "nets", f"scale-I2-O2-{name}.npz"))
+        xdims = [int(v) for v in z["xdims"]]
+        return na.FeedFwdNet(xdims=xdims, Ms=[np.array(z[f"M{k}"], dtype=np.float64) for k in range(len(xdims) - 1)]), np.full(2, 0.5), np.full(2, 1.5)
+    if name == "acas-shape":
+        return na.randomNetwork([5] + [50] * 6 + [5], seed=1234), np.full(5, 0.25), np.full(5, 0.35)
+    raise SystemExit(f"unknown case {name}")
+
+
+def sub_boxes(lo, hi, nbox, seed=0):
+    rng = np.random.default_rng(seed)
+    hw = (hi - lo)[:, None] / 16.0
+    c = lo[:, None] + hw + rng.random((len(lo), nbox)) * ((hi - lo)[:, None] - 2 * hw)
+    return c - hw, c + hw
+
+
+def crown_rows(net, lo, hi):
+    rows = []
+    for nbox in (1, 256, 4096):
+        blo, bhi = sub_boxes(lo, hi, nbox)
+        ker, wall = [], []
+        for i in range(9):
+            t = time.perf_counter()
+            *_, ms = na.makeIntervalsBatch(net, blo, bhi, backend="gpu", return_ms=True)
+            if i >= 2:
+                ker.append(ms); wall.append(1e3 * (time.perf_counter() - t))
+        n1 = min(nbox, 256)
+        t = time.perf_counter(); na.makeIntervalsBatch(net, blo[:, :n1], bhi[:, :n1], backend="host", workers=1); h1 = 1e3 * (time.perf_counter() - t) * nbox / n1
+        t = time.perf_counter(); na.makeIntervalsBatch(net, blo, bhi, backend="host", workers=16); h16 = 1e3 * (time.perf_counter() - t)
+        rows.append(dict(nbox=nbox, gpu_kernel_ms_median=statistics.median(ker), gpu_kernel_ms_min=min(ker), gpu_kernel_ms_max=max(ker),
+                         gpu_call_ms_median=statistics.median(wall), host_1_worker_ms=h1, host_1_worker_boxes_timed=n1, host_16_workers_ms=h16,
+                         gpu_call_over_host_16=statistics.median(wall) / h16, gpu_kernel_over_host_16=statistics.median(ker) / h16))
+        print(rows[-1], flush=True)
+    return rows
+
+
+def split_row(net, lo, hi):
+    nrm = np.zeros(net.xdims[-1]); nrm[0] = 1.0
+    X = lo[:, None] + np.random.default_rng(0).random((len(lo), 20000)) * (hi - lo)[:, None]
+    s = float((nrm @ na.evalFeedFwdNetBatch(net, X)).max())
+    iv = na.makeIntervalsBatch(net, lo[:, None], hi[:, None], backend="gpu")
+    c0 = float(np.maximum(nrm * iv[4][:, 0], nrm * iv[5][:, 0]).sum())
+    h = s + 0.25 * (c0 - s)
+    opts = na.AdmmSdpOptions(max_iters=4000, eps_rel=1e-5)
+    so = na.SplitOptions(max_boxes=256, sdp_per_level=13, crown_backend="gpu")
+    r = na.verifySplit(net, lo, hi, [(nrm, h)], 0, opts, so)
+    by = [lf.proved_by for lf in r.leaves]
+    row = dict(sampled_max=s, root_cheap_bound=c0, h=h, verdict=r.verdict, visited=r.visited, sdp_solves=r.sdp_solves, leaves=len(r.leaves),
+               by_crown=by.count("crown"), by_sdp=by.count("sdp"), open=by.count(None), max_boxes=so.max_boxes, sdp_per_level=so.sdp_per_level,
+               max_iters=opts.max_iters, seconds=r.seconds)
+    print(row, flush=True)
+    return row
+
+
+if __name__ == "__main__":
+    names = sys.argv[1:] or ["W10-D5", "W40-D20", "acas-shape"]
+    out_dir = os.environ.get("SPLIT_TIMING_OUT", os.path.join(ROOT, "profiles"))
+    os.makedirs(out_dir, exist_ok=True)
+    for name in names:
+        net, lo, hi = case(name)
+        res = dict(case=name, xdims=net.xdims, crown=crown_rows(net, lo, hi), split=split_row(net, lo, hi))
+        with open(os.path.join(out_dir, f"split_timing_{name}.json"), "w") as fh:
+            json.dump(res, fh, indent=1)
