@@ -254,15 +254,40 @@ static double lambda_max_dense(rocblas_handle h, const DBuf<double>& Zd, int n, 
 }
 
 // ---- PSD blocks above 128 (library path: rocSOLVER dsyevd + rocBLAS dgemm, one block at a time) --------------------
-// A = sym(nu_k)
-__global__ void k_big_sym(int n, const double* __restrict__ nu, double* __restrict__ A) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x, j = blockIdx.y;
-  if (i < n) A[(size_t)j * n + i] = 0.5 * (nu[(size_t)j * n + i] + nu[(size_t)i * n + j]);
+// The library eigensolver has no scaling of its own: on a block of entries around 1e-150 dsyevd returned finite eigenvalues that were
+// wrong by more than |A| (tests/test_projection_hard_cases.py, the library launches).  A block whose largest entry lies outside
+// [2^-64, 2^64] is therefore solved as f A with the power of two f that brings the entry into [1, 2) - exact - and the eigenvalues are
+// scaled back; every other block (a solver's normalised blocks) keeps f = 1 and its bits.  scl[0] = f, scl[1] = 1 / f.  One workgroup.
+__global__ __launch_bounds__(1024) void k_big_absmax(long long n2, const double* __restrict__ nu, double* __restrict__ scl) {
+  __shared__ double part[16];
+  double v = 0.0;
+  for (long long i = threadIdx.x; i < n2; i += 1024) v = fmax(v, fabs(nu[i]));
+  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int q = 1; q < 16; ++q) v = fmax(v, part[q]);
+    const int e = (int)((__double_as_longlong(v) >> 52) & 0x7ff) - 1023;      // (-1023: zero or subnormal, 1024: infinity)
+    const bool keep = v == 0.0 || e == 1024 || (e >= -64 && e <= 64);
+    scl[0] = keep ? 1.0 : ldexp(1.0, -e);
+    scl[1] = keep ? 1.0 : ldexp(1.0, e);
+  }
 }
-// T[:, j] = V[:, j] * max(lam_j, 0)
-__global__ void k_big_scale(int n, const double* __restrict__ V, const double* __restrict__ lam, double* __restrict__ T) {
+// A = f sym(nu_k)
+__global__ void k_big_sym(int n, const double* __restrict__ nu, double* __restrict__ A, const double* __restrict__ scl) {
   int i = blockIdx.x * blockDim.x + threadIdx.x, j = blockIdx.y;
-  if (i < n) { double l = lam[j]; T[(size_t)j * n + i] = l > 0.0 ? l * V[(size_t)j * n + i] : 0.0; }
+  const double f = scl[0];
+  if (i < n) A[(size_t)j * n + i] = 0.5 * (f * nu[(size_t)j * n + i] + f * nu[(size_t)i * n + j]);
+}
+// T[:, j] = V[:, j] * max(lam_j, 0) / f
+__global__ void k_big_scale(int n, const double* __restrict__ V, const double* __restrict__ lam, double* __restrict__ T, const double* __restrict__ scl) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x, j = blockIdx.y;
+  if (i < n) { double l = lam[j] * scl[1]; T[(size_t)j * n + i] = l > 0.0 ? l * V[(size_t)j * n + i] : 0.0; }
+}
+// eigenvalues of the block itself: lam / f
+__global__ void k_big_eig(int n, const double* __restrict__ lam, const double* __restrict__ scl, double* __restrict__ out) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = lam[i] * scl[1];
 }
 // nu <- w + kappa (nu - w)   (penalty change, as the LDS kernel does for its blocks)
 __global__ void k_big_rescale(long long n2, const double* __restrict__ w, double* __restrict__ nu, const double* __restrict__ kappa) {
@@ -279,14 +304,16 @@ __global__ void k_sticky_info(const rocblas_int* __restrict__ info, int* __restr
 __global__ void k_fold_flag(const int* __restrict__ flag, double* __restrict__ acc7) { if (*flag != 0) *acc7 += 1024.0; }
 
 // w_k = proj_PSD(sym(nu_k)) for one block of any size through rocSOLVER dsyevd + rocBLAS dgemm, all on the handle's stream
+// (scl: two doubles of device scratch for the block's scale factor, see k_big_absmax)
 static void project_big_block(rocblas_handle h, hipStream_t st, int n, const double* nuk, double* wk, double* A, double* T, double* Dv,
-                              double* Ev, rocblas_int* info, double* eig_out = nullptr) {
-  hipLaunchKernelGGL(k_big_sym, dim3((n + 255) / 256, n), dim3(256), 0, st, n, nuk, A);
+                              double* Ev, rocblas_int* info, double* scl, double* eig_out = nullptr) {
+  hipLaunchKernelGGL(k_big_absmax, dim3(1), dim3(1024), 0, st, (long long)n * n, nuk, scl);
+  hipLaunchKernelGGL(k_big_sym, dim3((n + 255) / 256, n), dim3(256), 0, st, n, nuk, A, scl);
   RBCHK(rocsolver_dsyevd(h, rocblas_evect_original, rocblas_fill_lower, n, A, n, Dv, Ev, info));
-  hipLaunchKernelGGL(k_big_scale, dim3((n + 255) / 256, n), dim3(256), 0, st, n, A, Dv, T);
+  hipLaunchKernelGGL(k_big_scale, dim3((n + 255) / 256, n), dim3(256), 0, st, n, A, Dv, T, scl);
   const double one = 1.0, zero = 0.0;
   RBCHK(rocblas_dgemm(h, rocblas_operation_none, rocblas_operation_transpose, n, n, n, &one, T, n, A, n, &zero, wk, n));
-  if (eig_out) HIPCHK(hipMemcpyAsync(eig_out, Dv, n * sizeof(double), hipMemcpyDeviceToDevice, st));
+  if (eig_out) hipLaunchKernelGGL(k_big_eig, dim3((n + 255) / 256), dim3(256), 0, st, n, Dv, scl, eig_out);
 }
 
 __global__ void k_symmetrize_lower(int n, int ld, double* A) {
@@ -405,7 +432,7 @@ struct nnsdp_solver {
   std::vector<int> small_idx, big_idx;          // blocks for the LDS kernel (n <= 128) / for the library path
   DBuf<int> d_cn_s;
   DBuf<long long> d_coff_s;
-  DBuf<double> big_A, big_T, big_D, big_E;
+  DBuf<double> big_A, big_T, big_D, big_E, big_scl;
   DBuf<rocblas_int> big_info;
   DBuf<int> big_flag;                   // sticky: some library eigensolve of this process reported info != 0 (k_sticky_info)
   int big_flag_host = 0;
@@ -694,7 +721,7 @@ struct nnsdp_solver {
   void setup_member() {
     const int ng = S.ng;
     if (!big_idx.empty()) {
-      big_A.alloc((size_t)nmax * nmax); big_T.alloc((size_t)nmax * nmax); big_D.alloc(nmax); big_E.alloc(nmax);
+      big_A.alloc((size_t)nmax * nmax); big_T.alloc((size_t)nmax * nmax); big_D.alloc(nmax); big_E.alloc(nmax); big_scl.alloc(2);
       big_info.alloc(big_idx.size()); big_info.zero();
       big_flag.alloc(1); big_flag.zero();
     }
@@ -807,7 +834,7 @@ struct nnsdp_solver {
     auto add = [&](size_t b, bool sh) { (sh ? shared_b : own) += b; };
 #define NNSDP_B(x) add((x).bytes(), (x).shared());
     NNSDP_B(D.csr_ptr) NNSDP_B(D.csr_col) NNSDP_B(D.csr_val) NNSDP_B(D.csc_ptr) NNSDP_B(D.csc_row) NNSDP_B(D.csc_val) NNSDP_B(D.z0) NNSDP_B(D.c)
-    NNSDP_B(D.Dinv) NNSDP_B(D.erow) NNSDP_B(D.ecol) NNSDP_B(d_cn_s) NNSDP_B(d_coff_s) NNSDP_B(big_A) NNSDP_B(big_T) NNSDP_B(big_D) NNSDP_B(big_E)
+    NNSDP_B(D.Dinv) NNSDP_B(D.erow) NNSDP_B(D.ecol) NNSDP_B(d_cn_s) NNSDP_B(d_coff_s) NNSDP_B(big_A) NNSDP_B(big_T) NNSDP_B(big_D) NNSDP_B(big_E) NNSDP_B(big_scl)
     NNSDP_B(big_info) NNSDP_B(big_flag) NNSDP_B(d_cn) NNSDP_B(d_sptr) NNSDP_B(d_stats) NNSDP_B(d_long) NNSDP_B(d_rstate) NNSDP_B(d_medrows)
     NNSDP_B(d_medsrc) NNSDP_B(d_colcls) NNSDP_B(d_coff) NNSDP_B(d_soff) NNSDP_B(d_isdiag) NNSDP_B(d_gidx) NNSDP_B(Tg) NNSDP_B(Ug) NNSDP_B(nu) NNSDP_B(w)
     NNSDP_B(Vg) NNSDP_B(x) NNSDP_B(g) NNSDP_B(p) NNSDP_B(qv) NNSDP_B(ww) NNSDP_B(Minv) NNSDP_B(scal) NNSDP_B(acc) NNSDP_B(gs) NNSDP_B(accp)
@@ -1225,7 +1252,7 @@ struct nnsdp_solver {
       const int n = cn[k];
       double* nuk = nu.p + S.ng + coff[k];
       double* wk = w.p + S.ng + coff[k];
-      project_big_block(roc->h, strm, n, nuk, wk, big_A.p, big_T.p, big_D.p, big_E.p, big_info.p + big_slot(k));
+      project_big_block(roc->h, strm, n, nuk, wk, big_A.p, big_T.p, big_D.p, big_E.p, big_info.p + big_slot(k), big_scl.p);
       hipLaunchKernelGGL(k_sticky_info, dim3(1), dim3(1), 0, strm, big_info.p + big_slot(k), big_flag.p);
       hipLaunchKernelGGL(k_big_rescale, dim3(cdiv((long long)n * n, 256)), dim3(256), 0, strm, (long long)n * n, wk, nuk, d_kappa());
     }
@@ -2985,11 +3012,11 @@ int nnsdp_project_psd_batched(int32_t batch, const int32_t* n, const double* mat
       RBCHK(rocblas_set_stream(rh.h, nullptr));
       int nb = 0;
       for (int b : big) nb = std::max(nb, cn[b]);
-      DBuf<double> A, T, Dv, Ev; DBuf<rocblas_int> info;
-      A.alloc((size_t)nb * nb); T.alloc((size_t)nb * nb); Dv.alloc(nb); Ev.alloc(nb); info.alloc(big.size()); info.zero();
+      DBuf<double> A, T, Dv, Ev, scl; DBuf<rocblas_int> info;
+      A.alloc((size_t)nb * nb); T.alloc((size_t)nb * nb); Dv.alloc(nb); Ev.alloc(nb); scl.alloc(2); info.alloc(big.size()); info.zero();
       for (size_t bi = 0; bi < big.size(); ++bi) {
         const int b = big[bi];
-        project_big_block(rh.h, nullptr, cn[b], dnu.p + coff[b], dw.p + coff[b], A.p, T.p, Dv.p, Ev.p, info.p + bi, dE.p + eoff[b]);
+        project_big_block(rh.h, nullptr, cn[b], dnu.p + coff[b], dw.p + coff[b], A.p, T.p, Dv.p, Ev.p, info.p + bi, scl.p, dE.p + eoff[b]);
       }
       HIPCHK(hipDeviceSynchronize());
       for (rocblas_int v : info.download())

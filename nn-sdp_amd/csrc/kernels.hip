@@ -329,7 +329,12 @@ __device__ __forceinline__ void proj_body(const ProjArgs& a, const int k, const 
 #pragma unroll
     for (int m = 0; m < MR; ++m) {
       const int e = min(2 * (tid + NT * m), n2 - 2);
-      if (NT * m < npc) {
+      if (m == 0 && n2 < 2) {
+        // a 1 x 1 block has no 16-byte piece: n2 - 2 = -1 would read the element in FRONT of the block (in front of the allocation
+        // when the block is the first of the launch).  One element, in both halves of the piece (workgroup-uniform branch)
+        ta[0].x = ta[0].y = nuk[0];
+        if (warm) tv[0].x = tv[0].y = vgk[0];
+      } else if (NT * m < npc) {
         ta[m] = *reinterpret_cast<const double2*>(nuk + e);
         if (warm) tv[m] = *reinterpret_cast<const double2*>(vgk + e);
       }
