@@ -327,6 +327,18 @@ int nnsdp_make_intervals_activ(int32_t K, const int32_t* xdims, const double* M,
                                double* acymin, double* acymax, double* acxmin, double* acxmax, double* smin, double* smax,
                                double* ymin, double* ymax);
 
+/* nnsdp_make_intervals_activ plus bounds of nlit literals  normal_i' f(x)  (the split driver's clause, nnsdp_amd/split.py): one more
+ * backward pass whose head is [C W_{K-1} | C b_{K-1}], C the nlit x ny matrix of normals, float32 like the rest of the routine; ReLU
+ * and Tanh, any width.  normals: ny x nlit column-major (one literal's normal after the other), nlit in 0..64.  Outputs (any may be
+ * NULL): lit_smin / lit_smax [nlit] raw bounds of the literals, and the linear upper bound  normal_i' f(x) <= uA[:, i]' x + ub0[i]
+ * on the box, uA [xdims[0] x nlit] column-major; lit_smax = uA' c + |uA|' r + ub0 with the box centre c and radius r.  The other
+ * outputs have the bits of nnsdp_make_intervals_activ.  -1 with a message for nlit outside 0..64, normals NULL with nlit > 0, or a
+ * non-finite normal entry ("literal i").  No GPU needed. */
+int nnsdp_make_intervals_lits(int32_t K, const int32_t* xdims, const double* M, int32_t activ, const double* x1min, const double* x1max,
+                              double* acymin, double* acymax, double* acxmin, double* acxmax, double* smin, double* smax,
+                              double* ymin, double* ymax, int32_t nlit, const double* normals, double* lit_smin, double* lit_smax,
+                              double* uA, double* ub0);
+
 /* Sampled forward pass on the GPU: Y[:, s] = ffnet(X[:, s]) for N points in fp64.  Replaces the
  * N = 1e5 calls of evalFeedFwdNet (src/MyNeuralNetwork/MyNeuralNetwork.jl:40-48) inside Utils.sampleTrajs (src/Utils/qc.jl:40-47),
  * whose outputs shape the ellipsoid of NnSdp.findEllipsoid (approxEllipsoid, src/Utils/qc.jl:50-67).  K, xdims, M as in
@@ -348,6 +360,21 @@ int nnsdp_make_intervals_batch(int32_t K, const int32_t* xdims, const double* M,
                                const double* x1min, const double* x1max,
                                double* acymin, double* acymax, double* acxmin, double* acxmax,
                                double* ymin, double* ymax, double* kernel_ms);
+
+/* nnsdp_make_intervals_batch plus bounds of nlit literals  normal_i' f(x)  per box, from one more backward pass of the same kernel
+ * whose head is H = [C W_{K-1} | C b_{K-1}] (C the nlit x ny matrix of normals; H is computed once on the host in fp64, plain sums
+ * over ascending index).  normals: ny x nlit column-major, nlit in 0..64 (0: exactly nnsdp_make_intervals_batch).  Outputs (HOST
+ * pointers, any may be NULL): smin / smax [nlit x nbox] raw (no min / max post-fix), uA [xdims[0] x nlit x nbox] (coefficient index
+ * fastest, then the literal, then the box) and ub0 [nlit x nbox]:  normal_i' f(x) <= uA' x + ub0  on the box, and
+ * smax = uA' c + |uA|' r + ub0 with the box centre c and radius r.  A literal's bits depend neither on nbox, nor on the box's
+ * position, nor on the other literals of the call; the six interval arrays have the bits of nnsdp_make_intervals_batch.
+ * -1 with a message as nnsdp_make_intervals_batch, and for nlit outside 0..64, normals NULL with nlit > 0, or a non-finite normal
+ * entry ("literal i"); these checks need no GPU. */
+int nnsdp_make_intervals_batch_lits(int32_t K, const int32_t* xdims, const double* M, int32_t activ, int32_t nbox,
+                                    const double* x1min, const double* x1max,
+                                    double* acymin, double* acymax, double* acxmin, double* acxmax,
+                                    double* ymin, double* ymax, int32_t nlit, const double* normals,
+                                    double* smin, double* smax, double* uA, double* ub0, double* kernel_ms);
 
 /* Batched projection onto the PSD cone, the hot kernel (replaces the cone handling inside MOSEK;
  * reference of the arithmetic: LinearAlgebra.eigen on Symmetric).  mats: `batch` symmetric

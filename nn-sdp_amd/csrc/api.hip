@@ -2811,12 +2811,37 @@ int nnsdp_make_cliques(int32_t K, const int32_t* xdims, int32_t beta, int32_t mo
   API_END
 }
 
+// the refusals of the literal arguments, shared by the two _lits entries (xdims[K] must be valid)
+static void check_literals(int32_t ny, int32_t nlit, const double* normals) {
+  if (nlit < 0 || nlit > nnsdp::kCbW) throw std::invalid_argument("nlit must be in 0..64, got " + std::to_string(nlit));
+  if (nlit > 0 && !normals) throw std::invalid_argument("normals is null with nlit > 0");
+  for (int i = 0; i < nlit; ++i)
+    for (int j = 0; j < ny; ++j)
+      if (!std::isfinite(normals[(size_t)i * ny + j]))
+        throw std::invalid_argument("literal " + std::to_string(i) + ": the normal has a non-finite entry (NaN or infinity)");
+}
+
 static int make_intervals_impl(int32_t K, const int32_t* xdims, const double* M, int32_t activ, const double* x1min, const double* x1max,
                          double* acymin, double* acymax, double* acxmin, double* acxmax, double* smin, double* smax,
-                         double* ymin, double* ymax) {
+                         double* ymin, double* ymax, int32_t nlit = 0, const double* normals = nullptr, double* lit_smin = nullptr,
+                         double* lit_smax = nullptr, double* uA = nullptr, double* ub0 = nullptr) {
   API_BEGIN
   if (activ != NNSDP_ACTIV_RELU && activ != NNSDP_ACTIV_TANH) throw std::invalid_argument("unknown activation");
-  nnsdp::IntervalsOut iv = nnsdp::make_intervals(K, xdims, M, x1min, x1max, activ == NNSDP_ACTIV_TANH);
+  nnsdp::LitHead head;
+  if (nlit != 0) {
+    if (K < 2 || !xdims || !M) throw std::invalid_argument("make_intervals: bad arguments");
+    for (int k = 0; k <= K; ++k)
+      if (xdims[k] <= 0) throw std::invalid_argument("make_intervals: layer widths must be positive");
+    check_literals(xdims[K], nlit, normals);
+    head = nnsdp::make_lit_head(K, xdims, M, nlit, normals);
+  }
+  nnsdp::IntervalsOut iv = nnsdp::make_intervals(K, xdims, M, x1min, x1max, activ == NNSDP_ACTIV_TANH, nlit > 0 ? &head : nullptr);
+  for (int i = 0; i < nlit; ++i) {
+    if (lit_smin) lit_smin[i] = iv.smin[i];
+    if (lit_smax) lit_smax[i] = iv.smax[i];
+    if (ub0) ub0[i] = iv.ub0[i];
+  }
+  if (uA && nlit > 0) std::copy(iv.uA.begin(), iv.uA.end(), uA);
   const double eps = 1e-4;   // src/Qc/activ_sector.jl:65
   size_t o = 0;
   for (int k = 1; k < K; ++k)
@@ -2853,6 +2878,14 @@ int nnsdp_make_intervals_activ(int32_t K, const int32_t* xdims, const double* M,
                                double* acymin, double* acymax, double* acxmin, double* acxmax, double* smin, double* smax,
                                double* ymin, double* ymax) {
   return make_intervals_impl(K, xdims, M, activ, x1min, x1max, acymin, acymax, acxmin, acxmax, smin, smax, ymin, ymax);
+}
+
+int nnsdp_make_intervals_lits(int32_t K, const int32_t* xdims, const double* M, int32_t activ, const double* x1min, const double* x1max,
+                              double* acymin, double* acymax, double* acxmin, double* acxmax, double* smin, double* smax,
+                              double* ymin, double* ymax, int32_t nlit, const double* normals, double* lit_smin, double* lit_smax,
+                              double* uA, double* ub0) {
+  return make_intervals_impl(K, xdims, M, activ, x1min, x1max, acymin, acymax, acxmin, acxmax, smin, smax, ymin, ymax, nlit, normals,
+                             lit_smin, lit_smax, uA, ub0);
 }
 
 int nnsdp_eval_network(int32_t K, const int32_t* xdims, const double* M, int32_t activ, int64_t N, const double* X, double* Y,
@@ -2905,6 +2938,15 @@ int nnsdp_make_intervals_batch(int32_t K, const int32_t* xdims, const double* M,
                                const double* x1min, const double* x1max,
                                double* acymin, double* acymax, double* acxmin, double* acxmax,
                                double* ymin, double* ymax, double* kernel_ms) {
+  return nnsdp_make_intervals_batch_lits(K, xdims, M, activ, nbox, x1min, x1max, acymin, acymax, acxmin, acxmax, ymin, ymax, 0, nullptr,
+                                         nullptr, nullptr, nullptr, nullptr, kernel_ms);
+}
+
+int nnsdp_make_intervals_batch_lits(int32_t K, const int32_t* xdims, const double* M, int32_t activ, int32_t nbox,
+                                    const double* x1min, const double* x1max,
+                                    double* acymin, double* acymax, double* acxmin, double* acxmax,
+                                    double* ymin, double* ymax, int32_t nlit, const double* normals,
+                                    double* smin, double* smax, double* uA, double* ub0, double* kernel_ms) {
   API_BEGIN
   if (K < 2 || !xdims || !M) throw std::invalid_argument("null / empty network (K >= 2 layers are needed)");
   if (activ == NNSDP_ACTIV_TANH) throw std::invalid_argument("Tanh networks are not supported by the batched intervals: use nnsdp_make_intervals_activ per box");
@@ -2921,6 +2963,7 @@ int nnsdp_make_intervals_batch(int32_t K, const int32_t* xdims, const double* M,
     if (k > 0) acoff[k] = acoff[k - 1] + xd[k];
   }
   const int acdim = acoff[K - 1], n0 = xd[0], ny = xd[K];
+  check_literals(ny, nlit, normals);
   if (nbox < 0) throw std::invalid_argument("nbox must be >= 0");
   if (nbox == 0) return 0;
   if (!x1min || !x1max) throw std::invalid_argument("null argument");
@@ -2932,14 +2975,22 @@ int nnsdp_make_intervals_batch(int32_t K, const int32_t* xdims, const double* M,
   DBuf<int> dxd, dao; DBuf<long long> dmo; DBuf<double> dM, dlo, dhi, dscr, dout;
   dxd.upload(xd); dao.upload(acoff); dmo.upload(moff);
   const size_t nb = (size_t)nbox, na = nb * acdim, ny_all = nb * ny;
-  dM.alloc(moff[K]); dlo.alloc(nb * n0); dhi.alloc(nb * n0); dscr.alloc(2 * na); dout.alloc(4 * na + 2 * ny_all);
+  // the literal head H sits behind M; the literal outputs behind the six interval arrays: smin, smax, ub0 (nlit each per box), uA
+  const size_t hlen = nlit > 0 ? (size_t)nlit * (xd[K - 1] + 1) : 0, nl_all = nb * (size_t)nlit, nA_all = nl_all * n0;
+  dM.alloc(moff[K] + hlen); dlo.alloc(nb * n0); dhi.alloc(nb * n0); dscr.alloc(2 * na); dout.alloc(4 * na + 2 * ny_all + 3 * nl_all + nA_all);
   HIPCHK(hipMemcpy(dM.p, M, moff[K] * sizeof(double), hipMemcpyHostToDevice));
+  if (nlit > 0) {
+    const nnsdp::LitHead head = nnsdp::make_lit_head(K, xdims, M, nlit, normals);
+    HIPCHK(hipMemcpy(dM.p + moff[K], head.H.data(), hlen * sizeof(double), hipMemcpyHostToDevice));
+  }
   HIPCHK(hipMemcpy(dlo.p, x1min, nb * n0 * sizeof(double), hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(dhi.p, x1max, nb * n0 * sizeof(double), hipMemcpyHostToDevice));
   nnsdp::CrownArgs a;
   a.K = K; a.xdims = dxd.p; a.moff = dmo.p; a.acoff = dao.p; a.M = dM.p; a.lo = dlo.p; a.hi = dhi.p; a.scratch = dscr.p;
   a.acymin = dout.p; a.acymax = dout.p + na; a.acxmin = dout.p + 2 * na; a.acxmax = dout.p + 3 * na;
   a.ymin = dout.p + 4 * na; a.ymax = a.ymin + ny_all; a.acdim = acdim;
+  a.nlit = nlit; a.H = dM.p + moff[K];
+  a.smin = a.ymax + ny_all; a.smax = a.smin + nl_all; a.ub0 = a.smax + nl_all; a.uA = a.ub0 + nl_all;
   HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&nnsdp::k_crown_batch), hipFuncAttributeMaxDynamicSharedMemorySize,
                              (int)nnsdp::kCbLdsBytes));
   struct Events {   // destroyed on every path out of this function, HIPCHK throws
@@ -2960,6 +3011,11 @@ int nnsdp_make_intervals_batch(int32_t K, const int32_t* xdims, const double* M,
   for (int o = 0; o < 6; ++o)
     if (host[o] && (o < 4 ? na : ny_all))
       HIPCHK(hipMemcpy(host[o], dev[o], (o < 4 ? na : ny_all) * sizeof(double), hipMemcpyDeviceToHost));
+  double* lhost[4] = {smin, smax, ub0, uA};
+  const double* ldev[4] = {a.smin, a.smax, a.ub0, a.uA};
+  for (int o = 0; o < 4; ++o)
+    if (lhost[o] && (o < 3 ? nl_all : nA_all))
+      HIPCHK(hipMemcpy(lhost[o], ldev[o], (o < 3 ? nl_all : nA_all) * sizeof(double), hipMemcpyDeviceToHost));
   API_END
 }
 

@@ -12,6 +12,13 @@
 //      is read from global memory / L2 in chunks of kCbChunk k-steps, the tiles stay in registers across a barrier and are
 //      written back over A.
 // Then thread (matrix, row) concretises its row over the box.  No atomics; 68 KB of LDS (69 632 B), two workgroups per CU.
+//
+// Literal pass (nlit > 0, nnsdp_make_intervals_batch_lits): after the K output passes the pre-activation bounds of every hidden
+// layer are in the scratch, so one more pass whose head is H = [C W_{K-1} | C b_{K-1}] (nlit x (xdims[K-1] + 1), one row per literal
+// normal, computed once on the host) bounds  normal' f(x)  directly instead of through the per-output boxes.  It is the same
+// row pass and the same MFMA product with nout = nlit; its results are raw (no post-fix), and the upper bound's linear form
+// uA x + ub0 is written out beside them (smax = uA c + |uA| r + ub0).  Every output element of the product is its own dot product
+// and the row passes are per row, so a literal's bits do not depend on the other literals of the call.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -29,6 +36,12 @@ struct CrownArgs {
   double *acymin, *acymax, *acxmin, *acxmax;   // acdim x nbox
   double *ymin, *ymax;      // xdims[K] x nbox
   int acdim;
+  // literal pass (nlit == 0: none, the pointers below are unused)
+  int nlit;                 // 0 .. 64
+  const double* H;          // nlit x (xdims[K-1] + 1), column-major like an M_k block
+  double *smin, *smax;      // nlit x nbox, raw
+  double* uA;               // xdims[0] x nlit x nbox, coefficient index fastest
+  double* ub0;              // nlit x nbox
 };
 
 static constexpr int kCbW = 64;        // widest layer
@@ -40,6 +53,9 @@ __device__ __forceinline__ int cb_idx(int t, int i) { return t * kCbW + (i ^ ((t
 // One backward pass for box `box`.  head_identity == 0: bounds of W_{k-1} relu(... ) + b_{k-1}, i.e. the pre-activation of hidden
 // layer k (k < K, raw, to the scratch) or the network output (k == K, post-fixed, to ymin / ymax).  head_identity == 1: the
 // post-activation of hidden layer k through an identity head (post-fixed, to acymin / acymax).
+// LIT: the literal pass (k == K, head_identity == 0): the head is a.H instead of M_{K-1}, nout = nlit, the results go raw to smin /
+// smax with the upper bound's coefficients and constant to uA / ub0.
+template <bool LIT>
 __device__ void crown_pass(const CrownArgs& a, double* lds, long long box, int k, int head_identity) {
   double* A[2] = {lds, lds + kCbW * kCbW};
   double* v_du = lds + 2 * kCbW * kCbW;
@@ -51,12 +67,12 @@ __device__ void crown_pass(const CrownArgs& a, double* lds, long long box, int k
   double* v_res = v_r + kCbW;     // 2 x 64: a pass's lower / upper results, for the post-fix
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, lr = lane & 15, lc = lane >> 4;
   const int mat = tid >> 6, row = tid & 63;      // the (matrix, row) a thread owns in the row passes (threads 0..127)
-  const int nout = a.xdims[k];
+  const int nout = LIT ? a.nlit : a.xdims[k];
   int d = head_identity ? nout : a.xdims[k - 1];
   const int jtop = head_identity ? k - 1 : k - 2;
   double bias = 0.0;
   {
-    const double* Mh = a.M + a.moff[k - 1];
+    const double* Mh = LIT ? a.H : a.M + a.moff[k - 1];
     for (int idx = tid; idx < nout * d; idx += 256) {
       const int t = idx / nout, i = idx - t * nout;
       const double v = head_identity ? (t == i ? 1.0 : 0.0) : Mh[(size_t)t * nout + i];
@@ -167,9 +183,20 @@ __device__ void crown_pass(const CrownArgs& a, double* lds, long long box, int k
       rr += fabs(x) * v_r[t];
     }
     v_res[mat * kCbW + row] = mat ? s + rr + bias : s - rr + bias;
+    if (LIT && mat && a.ub0) a.ub0[(size_t)box * nout + row] = bias;
   }
   __syncthreads();
-  if (tid < nout) {
+  if (LIT) {
+    if (tid < nout) {
+      if (a.smin) a.smin[(size_t)box * nout + tid] = v_res[tid];
+      if (a.smax) a.smax[(size_t)box * nout + tid] = v_res[kCbW + tid];
+    }
+    if (a.uA)
+      for (int idx = tid; idx < nout * d; idx += 256) {       // d == xdims[0] here; A[1] is the upper bound's matrix after the last product
+        const int i = idx / d, t = idx - i * d;
+        a.uA[((size_t)box * nout + i) * d + t] = A[1][cb_idx(t, i)];
+      }
+  } else if (tid < nout) {
     const double l = v_res[tid], u = v_res[kCbW + tid];
     if (!head_identity && k < a.K) {
       double* pre = a.scratch + (size_t)box * 2 * a.acdim + a.acoff[k - 1];
@@ -196,9 +223,10 @@ __global__ __launch_bounds__(256) void k_crown_batch(CrownArgs a) {
   extern __shared__ double cb_lds[];
   const long long box = blockIdx.x;
   for (int k = 1; k <= a.K; ++k) {
-    crown_pass(a, cb_lds, box, k, 0);
-    if (k < a.K) crown_pass(a, cb_lds, box, k, 1);
+    crown_pass<false>(a, cb_lds, box, k, 0);
+    if (k < a.K) crown_pass<false>(a, cb_lds, box, k, 1);
   }
+  if (a.nlit > 0) crown_pass<true>(a, cb_lds, box, a.K, 0);
   // one interval step per layer for the pre-activations, from the post-fixed bounds of the layer below
   const int n0 = a.xdims[0];
   for (int idx = threadIdx.x; idx < a.acdim; idx += 256) {

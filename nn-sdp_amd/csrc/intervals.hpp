@@ -29,7 +29,32 @@ struct DenseF {             // row-major float matrix
 struct IntervalsOut {
   std::vector<std::vector<double>> xlo, xhi;      // K+1 post-activation intervals (x_1 .. x_K, output)
   std::vector<std::vector<double>> plo, phi;      // K-1 pre-activation intervals (float64 interval step)
+  // with a literal head (LitHead): raw bounds of the literals, and the upper bound's linear form  uA x + ub0  (uA row-major nlit x n0)
+  std::vector<double> smin, smax, uA, ub0;
 };
+
+// The head of a literal pass: H = [C W_{K-1} | C b_{K-1}] for the nlit x ny matrix C of literal normals (normals: ny x nlit,
+// column-major), in fp64 with plain sums over ascending index.  Stored like an M_k block: nlit x (xdims[K-1] + 1), column-major.
+struct LitHead {
+  int nlit = 0, d = 0;
+  std::vector<double> H;
+};
+inline LitHead make_lit_head(int K, const int32_t* xdims, const double* M, int nlit, const double* normals) {
+  LitHead h;
+  h.nlit = nlit; h.d = xdims[K - 1];
+  const int ny = xdims[K], d = h.d;
+  size_t off = 0;
+  for (int k = 0; k + 1 < K; ++k) off += (size_t)xdims[k + 1] * (xdims[k] + 1);
+  const double* Mk = M + off;                  // ny x (d + 1), column-major
+  h.H.assign((size_t)nlit * (d + 1), 0.0);
+  for (int t = 0; t <= d; ++t)
+    for (int i = 0; i < nlit; ++i) {
+      double s = 0.0;
+      for (int j = 0; j < ny; ++j) s += normals[(size_t)i * ny + j] * Mk[(size_t)t * ny + j];
+      h.H[(size_t)t * nlit + i] = s;
+    }
+  return h;
+}
 
 // ---- tanh relaxation (exts/auto_LiRPA/operators/activation.py BoundTanh: dtanh :863-868, precompute_relaxation :872-917,
 // bound_relax_impl, non-optimised branch :925-956,992-1016; the reference's bridge maps torch.nn.Tanh onto it,
@@ -85,11 +110,13 @@ inline void tanh_relax(float l, float u, float& lw, float& lb, float& uw, float&
 }
 
 // backward bound of  Ws[L-1] act(... act(Ws[0] x + bs[0]) ...) + bs[L-1]  over the box [lo, hi] (act = relu, or tanh when tanh_act);
-// pre[j] = pre-activation bounds of layer j (j < L-1)
+// pre[j] = pre-activation bounds of layer j (j < L-1).  The head is Ws[L-1] / bs[L-1], whatever it is (a layer of the network, an
+// identity, a literal head); out_uA / out_ub (optional) receive the upper bound's linear form  uA x + ub  on the box.
 inline void crown_backward(const std::vector<const DenseF*>& Ws, const std::vector<const std::vector<float>*>& bs,
                            const std::vector<std::vector<float>>& prel, const std::vector<std::vector<float>>& preu,
                            const std::vector<float>& lo, const std::vector<float>& hi, std::vector<float>& out_lo,
-                           std::vector<float>& out_hi, bool tanh_act = false) {
+                           std::vector<float>& out_hi, bool tanh_act = false, DenseF* out_uA = nullptr,
+                           std::vector<float>* out_ub = nullptr) {
   const int L = (int)Ws.size();
   DenseF lA = *Ws[L - 1], uA = *Ws[L - 1];
   const int nout = lA.r;
@@ -144,11 +171,15 @@ inline void crown_backward(const std::vector<const DenseF*>& Ws, const std::vect
     out_lo[i] = sl - rl + lb[i];
     out_hi[i] = su + ru + ub[i];
   }
+  if (out_uA) *out_uA = std::move(uA);
+  if (out_ub) *out_ub = std::move(ub);
 }
 
 // M: K matrices [W_k b_k], column-major xdims[k+1] x (xdims[k]+1), back to back (include/nnsdp.h, nnsdp_problem::M)
+// head (optional): one more backward pass from the literal head over layers K-2 .. 0, float32 like the others, after them; it
+// changes none of the other outputs.
 inline IntervalsOut make_intervals(int K, const int32_t* xdims, const double* M, const double* x1min, const double* x1max,
-                                   bool tanh_act = false) {
+                                   bool tanh_act = false, const LitHead* head = nullptr) {
   if (K < 2 || !xdims || !M || !x1min || !x1max) throw std::invalid_argument("make_intervals: bad arguments");
   std::vector<DenseF> W(K);
   std::vector<std::vector<float>> b(K);
@@ -197,6 +228,22 @@ inline IntervalsOut make_intervals(int K, const int32_t* xdims, const double* M,
       crown_backward(Ws, bs, prel, preu, lo, hi, l, u, tanh_act);
       fix(l, u);
     }
+  }
+  if (head && head->nlit > 0) {
+    const int nlit = head->nlit, d = xdims[K - 1];
+    DenseF Hw(nlit, d), uA;
+    std::vector<float> Hb(nlit), l, u, ub;
+    for (int i = 0; i < nlit; ++i) {
+      for (int t = 0; t < d; ++t) Hw.at(i, t) = (float)head->H[(size_t)t * nlit + i];
+      Hb[i] = (float)head->H[(size_t)d * nlit + i];
+    }
+    std::vector<const DenseF*> Ws;
+    std::vector<const std::vector<float>*> bs;
+    for (int j = 0; j + 1 < K; ++j) { Ws.push_back(&W[j]); bs.push_back(&b[j]); }
+    Ws.push_back(&Hw); bs.push_back(&Hb);
+    crown_backward(Ws, bs, prel, preu, lo, hi, l, u, tanh_act, &uA, &ub);
+    out.smin.assign(l.begin(), l.end()); out.smax.assign(u.begin(), u.end());
+    out.uA.assign(uA.a.begin(), uA.a.end()); out.ub0.assign(ub.begin(), ub.end());
   }
   for (int k = 0; k + 1 < K; ++k) {           // float64 interval step per layer (intervals_auto_lirpa.jl:55-62)
     const int r = xdims[k + 1], c = xdims[k];

@@ -96,6 +96,10 @@ SYMBOLS = [
     ("nnsdp_make_intervals", C.c_int, [C.c_int32, c_int32_p, c_double_p, c_double_p, c_double_p] + [c_double_p] * 8),
     ("nnsdp_make_intervals_activ", C.c_int, [C.c_int32, c_int32_p, c_double_p, C.c_int32, c_double_p, c_double_p] + [c_double_p] * 8),
     ("nnsdp_make_intervals_batch", C.c_int, [C.c_int32, c_int32_p, c_double_p, C.c_int32, C.c_int32, c_double_p, c_double_p] + [c_double_p] * 7),
+    ("nnsdp_make_intervals_batch_lits", C.c_int, [C.c_int32, c_int32_p, c_double_p, C.c_int32, C.c_int32, c_double_p, c_double_p] + [c_double_p] * 6
+     + [C.c_int32, c_double_p] + [c_double_p] * 5),
+    ("nnsdp_make_intervals_lits", C.c_int, [C.c_int32, c_int32_p, c_double_p, C.c_int32, c_double_p, c_double_p] + [c_double_p] * 8
+     + [C.c_int32, c_double_p] + [c_double_p] * 4),
     ("nnsdp_project_psd_batched", C.c_int, [C.c_int32, c_int32_p, c_double_p, c_double_p, c_double_p, c_double_p]),
     ("nnsdp_project_psd_warm", C.c_int, [C.c_int32, c_int32_p, c_double_p, c_double_p, C.c_double, C.c_int32, c_double_p, c_int32_p, c_double_p]),
     ("nnsdp_project_psd_warm_state", C.c_int, [C.c_int32, c_int32_p, c_double_p, c_double_p, C.c_double, C.c_int32, c_double_p, c_int32_p, c_double_p, c_int32_p]),

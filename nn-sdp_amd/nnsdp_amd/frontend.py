@@ -14,7 +14,7 @@ These run once per query on the host; the interval pre-processing is native C++ 
 from __future__ import annotations
 
 import csv
-from typing import List, Sequence, Tuple
+from typing import List, NamedTuple, Sequence, Tuple
 
 import ctypes as C
 
@@ -189,9 +189,34 @@ def _net_arrays(net: M.FeedFwdNet):
     return xd, Mp
 
 
-def makeIntervalsBatch(net: M.FeedFwdNet, lo, hi, backend: str = "host", workers: int = 16, return_ms: bool = False):
+class LiteralBounds(NamedTuple):
+    """bounds of nlit literals  normal_i' f(x)  on nbox boxes (makeIntervalsBatch with normals):
+    smin <= normal' f(x) <= smax  and  normal' f(x) <= A[i, :, b]' x + b0[i, b]  on box b; smax = A' c + |A|' r + b0 (centre, radius)"""
+    smin: np.ndarray      # nlit x nbox, raw (no min / max post-fix)
+    smax: np.ndarray      # nlit x nbox
+    A: np.ndarray         # nlit x n0 x nbox
+    b0: np.ndarray        # nlit x nbox
+
+
+def _host_pool(one, nbox: int, workers: int, entry: str):
+    """one(b) -> return code of a one-box library call, for every box on at most 16 threads (ctypes releases the GIL)"""
+    nw = max(1, min(int(workers), 16, nbox))
+    if nw == 1:
+        for b in range(nbox):
+            _lib.check(one(b))
+    else:
+        from concurrent.futures import ThreadPoolExecutor
+        with ThreadPoolExecutor(max_workers=nw) as pool:
+            codes = list(pool.map(one, range(nbox)))
+        if any(codes):
+            raise _lib.NnsdpError(next(c for c in codes if c), f"{entry} failed for a box of the batch")
+
+
+def makeIntervalsBatch(net: M.FeedFwdNet, lo, hi, backend: str = "host", workers: int = 16, return_ms: bool = False, normals=None):
     """CROWN-sliced bounds of many input boxes of one network: lo / hi are xdims[0] x nbox, one column per box.
     -> (acymin, acymax, acxmin, acxmax, ymin, ymax), one column per box.
+    normals (nlit x xdims[K], nlit <= 64): the literals  normal_i' f(x)  are bounded in the same call by one more backward pass whose
+    head is the normal folded into the last affine layer; the six arrays (same bits) are followed by a LiteralBounds.
     backend="gpu":  nnsdp_make_intervals_batch (csrc/crown_batch.hpp), one launch, fp64; ReLU networks with every width <= 64,
                     anything else raises (no fall-back to the host).
     backend="host": nnsdp_make_intervals_activ (csrc/intervals.hpp, float32 arithmetic by design) once per box on a thread pool
@@ -209,6 +234,32 @@ def makeIntervalsBatch(net: M.FeedFwdNet, lo, hi, backend: str = "host", workers
     outs = [np.zeros((nbox, acdim)) for _ in range(4)] + [np.zeros((nbox, ny)) for _ in range(2)]
     dp = _lib.c_double_p
     ms = C.c_double(0.0)
+    if normals is not None:
+        nrm = np.ascontiguousarray(normals, dtype=np.float64)                   # nlit x ny row-major = ny x nlit column-major
+        if nrm.ndim != 2 or nrm.shape[1] != ny:
+            raise ValueError("normals must be nlit x xdims[K]")
+        nlit, n0 = nrm.shape[0], int(xd[0])
+        louts = [np.zeros((nbox, nlit)), np.zeros((nbox, nlit)), np.zeros((nbox, nlit, n0)), np.zeros((nbox, nlit))]    # smin, smax, uA, ub0
+        xdp, Mpp, nrp = xd.ctypes.data_as(_lib.c_int32_p), Mp.ctypes.data_as(dp), nrm.ctypes.data_as(dp)
+        if backend == "gpu":
+            _lib.check(lib.nnsdp_make_intervals_batch_lits(net.K, xdp, Mpp, M._activ_code(net.activ), nbox, loc.ctypes.data_as(dp),
+                                                           hic.ctypes.data_as(dp), *[o.ctypes.data_as(dp) for o in outs], nlit, nrp,
+                                                           *[o.ctypes.data_as(dp) for o in louts], C.byref(ms)))
+        elif backend == "host":
+            activ = M._activ_code(net.activ)
+
+            def one_lits(b):
+                rows = [o[b].ctypes.data_as(dp) for o in outs]
+                return lib.nnsdp_make_intervals_lits(net.K, xdp, Mpp, activ, loc[b].ctypes.data_as(dp), hic[b].ctypes.data_as(dp),
+                                                     rows[0], rows[1], rows[2], rows[3], None, None, rows[4], rows[5], nlit, nrp,
+                                                     *[o[b].ctypes.data_as(dp) for o in louts])
+
+            _host_pool(one_lits, nbox, workers, "nnsdp_make_intervals_lits")
+        else:
+            raise ValueError("backend must be 'gpu' or 'host'")
+        lits = LiteralBounds(louts[0].T, louts[1].T, louts[2].transpose(1, 2, 0), louts[3].T)
+        res = tuple(o.T for o in outs) + (lits,)
+        return res + (ms.value,) if return_ms else res
     if backend == "gpu":
         _lib.check(lib.nnsdp_make_intervals_batch(net.K, xd.ctypes.data_as(_lib.c_int32_p), Mp.ctypes.data_as(dp), M._activ_code(net.activ),
                                                   nbox, loc.ctypes.data_as(dp), hic.ctypes.data_as(dp),
@@ -223,16 +274,7 @@ def makeIntervalsBatch(net: M.FeedFwdNet, lo, hi, backend: str = "host", workers
                                                   rows[0].ctypes.data_as(dp), rows[1].ctypes.data_as(dp), rows[2].ctypes.data_as(dp),
                                                   rows[3].ctypes.data_as(dp), None, None, rows[4].ctypes.data_as(dp), rows[5].ctypes.data_as(dp))
 
-        nw = max(1, min(int(workers), 16, nbox))
-        if nw == 1:
-            for b in range(nbox):
-                _lib.check(one(b))
-        else:
-            from concurrent.futures import ThreadPoolExecutor
-            with ThreadPoolExecutor(max_workers=nw) as pool:
-                codes = list(pool.map(one, range(nbox)))
-            if any(codes):
-                raise _lib.NnsdpError(next(c for c in codes if c), "nnsdp_make_intervals_activ failed for a box of the batch")
+        _host_pool(one, nbox, workers, "nnsdp_make_intervals_activ")
     else:
         raise ValueError("backend must be 'gpu' or 'host'")
     res = tuple(o.T for o in outs)

@@ -4,9 +4,12 @@ A relaxation over a whole input box is often too loose to decide a literal, and 
 answers of a single solve.  verifySplit works level by level on the frontier of open sub-boxes:
 
   bound    one makeIntervalsBatch call for the whole frontier (csrc/crown_batch.hpp on the GPU, or the host routine per box);
-           a literal  normal' f(x) <= h  is proved on a box when  sum_j max(n_j ymin_j, n_j ymax_j) <= h
-  refute   the network at the box centres (plus `samples` seeded points per box): a point that violates every literal,
-           confirmed by the fp64 numpy evaluation, is a witness
+           a literal  normal' f(x) <= h  is proved on a box when  sum_j max(n_j ymin_j, n_j ymax_j) <= h.  With literal_bounds the
+           same call also back-propagates every normal folded into the last affine layer (the literal pass of the kernel /
+           nnsdp_make_intervals_lits), which keeps the correlation between the outputs; the smaller of the two bounds is used
+  refute   the network at the box centres (plus `samples` seeded points per box, plus with corner_points the corner of each box
+           that maximises the linear upper bound of its best literal): a point that violates every literal, confirmed by the
+           fp64 numpy evaluation, is a witness
   sdp      the boxes closest to a proof get one reach-hyperplane SDP per literal (vnnlib.reachForm) with the target h, decided
            early, in lockstep batches; the literals of a box form one solver family; the activation QCs come from the bounds of
            the first step (no second interval pass)
@@ -43,6 +46,12 @@ class SplitOptions:
     # the default until the kernel has been timed against 16 host workers (tools/split_timing.py)
     crown_backend: str = "host"
     samples: int = 0              # extra uniform points per open box in the refutation step, seeded from the box index
+    # bound the literals themselves in the bound step (makeIntervalsBatch(normals=...)) and use min(that bound, the per-output one)
+    # for proving, for Leaf.bound and for the order of the SDP stage: never proves less than without it (a clause of at most 64 literals)
+    literal_bounds: bool = False
+    # the refutation step also tries, per open box, the corner  where(A >= 0, hi, lo)  of its best literal's linear upper bound
+    # A' x + b0 (requests the literal bounds whatever literal_bounds says)
+    corner_points: bool = False
 
 
 @dataclass
@@ -52,7 +61,7 @@ class Leaf:
     depth: int
     proved_by: Optional[str]      # "crown" | "sdp" | None (open)
     literal: Optional[int]        # index of the literal that was proved
-    bound: Optional[float]        # the proved literal's upper bound of normal' f on the box (open: the smallest excess literal's cheap bound)
+    bound: Optional[float]        # the proved literal's upper bound of normal' f on the box (open: the smallest excess literal's bound)
     soln: Any = None              # the reach-form QuerySolution of an "sdp" leaf
 
 
@@ -180,10 +189,17 @@ def verifySplit(net: M.FeedFwdNet, x1min, x1max, literals: Sequence[Tuple[Any, f
         # 1. bound
         t0 = time.perf_counter()
         lo, hi = np.stack([b.lo for b in frontier], axis=1), np.stack([b.hi for b in frontier], axis=1)
-        iv = F.makeIntervalsBatch(net, lo, hi, backend=split.crown_backend)
+        lits = None
+        if split.literal_bounds or split.corner_points:
+            *iv, lits = F.makeIntervalsBatch(net, lo, hi, backend=split.crown_backend, normals=normals)
+            iv = tuple(iv)
+        else:
+            iv = F.makeIntervalsBatch(net, lo, hi, backend=split.crown_backend)
         seconds["crown"] += time.perf_counter() - t0
         ymin, ymax = iv[4], iv[5]
         cheap = np.stack([np.maximum(nrm[:, None] * ymin, nrm[:, None] * ymax).sum(axis=0) for nrm in normals])   # literal x box
+        if split.literal_bounds:
+            cheap = np.minimum(cheap, lits.smax)
         excess = cheap - hs[:, None]
         best = np.argmin(excess, axis=0)
         open_ids = []
@@ -195,6 +211,8 @@ def verifySplit(net: M.FeedFwdNet, x1min, x1max, literals: Sequence[Tuple[Any, f
         # 2. refute
         if open_ids:
             pts = [0.5 * (lo[:, open_ids] + hi[:, open_ids])]
+            if split.corner_points:
+                pts.append(np.stack([np.where(lits.A[best[b], :, b] >= 0.0, hi[:, b], lo[:, b]) for b in open_ids], axis=1))
             if split.samples > 0:
                 for b in open_ids:
                     rng = np.random.default_rng(frontier[b].index)

@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """Batched CROWN bounds: the GPU kernel against the host routine, and where one verifySplit spends its time.
-usage: python tools/split_timing.py [case ...]   cases: W10-D5 W40-D20 acas-shape   (default: all)
-Writes profiles/split_timing_<case>.json (or $SPLIT_TIMING_OUT/...).  Per case:
+usage: python tools/split_timing.py [--nlit] [case ...]   cases: W10-D5 W40-D20 acas-shape   (default: all)
+With --nlit only the literal leg runs and profiles/split_timing_nlit_<case>.json is written:
+  nlit     nnsdp_make_intervals_batch_lits at nbox = 256 with 0, 1 and 10 literals (y_0 - y_last, then seeded Gaussian normals): HIP-event
+           time of the launch and wall-clock of the call, median of 7 after 2 warm launches - what the literal pass adds to a launch
+Otherwise writes profiles/split_timing_<case>.json (or $SPLIT_TIMING_OUT/...).  Per case:
   crown    nnsdp_make_intervals_batch at nbox = 1, 256, 4096 sub-boxes of the root box: HIP-event time of the launch (median of 7 after 2
            warm launches) and the wall-clock of the whole call with its copies; beside it the host backend (nnsdp_make_intervals_activ per
            box) with 1 and 16 workers on the same boxes, wall-clock, one run (the 1-worker run on at most 256 boxes, scaled to nbox)
@@ -52,6 +55,26 @@ def crown_rows(net, lo, hi):
     return rows
 
 
+def nlit_rows(net, lo, hi, nbox=256):
+    blo, bhi = sub_boxes(lo, hi, nbox)
+    ny = net.xdims[-1]
+    Cm = np.random.default_rng(1).normal(size=(10, ny))
+    Cm[0] = 0.0; Cm[0, 0] = 1.0; Cm[0, ny - 1] -= 1.0
+    rows = []
+    for nlit in (0, 1, 10):
+        ker, wall = [], []
+        for i in range(9):
+            t = time.perf_counter()
+            *_, ms = na.makeIntervalsBatch(net, blo, bhi, backend="gpu", return_ms=True, normals=Cm[:nlit] if nlit else None)
+            if i >= 2:
+                ker.append(ms); wall.append(1e3 * (time.perf_counter() - t))
+        rows.append(dict(nbox=nbox, nlit=nlit, gpu_kernel_ms_median=statistics.median(ker), gpu_kernel_ms_min=min(ker), gpu_kernel_ms_max=max(ker),
+                         gpu_call_ms_median=statistics.median(wall)))
+        rows[-1]["kernel_over_nlit0"] = rows[-1]["gpu_kernel_ms_median"] / rows[0]["gpu_kernel_ms_median"]
+        print(rows[-1], flush=True)
+    return rows
+
+
 def split_row(net, lo, hi):
     nrm = np.zeros(net.xdims[-1]); nrm[0] = 1.0
     X = lo[:, None] + np.random.default_rng(0).random((len(lo), 20000)) * (hi - lo)[:, None]
@@ -71,11 +94,17 @@ def split_row(net, lo, hi):
 
 
 if __name__ == "__main__":
-    names = sys.argv[1:] or ["W10-D5", "W40-D20", "acas-shape"]
+    args = sys.argv[1:]
+    lit_leg = "--nlit" in args
+    names = [a for a in args if a != "--nlit"] or ["W10-D5", "W40-D20", "acas-shape"]
     out_dir = os.environ.get("SPLIT_TIMING_OUT", os.path.join(ROOT, "profiles"))
     os.makedirs(out_dir, exist_ok=True)
     for name in names:
         net, lo, hi = case(name)
+        if lit_leg:
+            with open(os.path.join(out_dir, f"split_timing_nlit_{name}.json"), "w") as fh:
+                json.dump(dict(case=name, xdims=net.xdims, nlit=nlit_rows(net, lo, hi)), fh, indent=1)
+            continue
         res = dict(case=name, xdims=net.xdims, crown=crown_rows(net, lo, hi), split=split_row(net, lo, hi))
         with open(os.path.join(out_dir, f"split_timing_{name}.json"), "w") as fh:
             json.dump(res, fh, indent=1)
