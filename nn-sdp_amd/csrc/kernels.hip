@@ -418,7 +418,7 @@ __device__ __forceinline__ void proj_body(const ProjArgs& a, const int k, const 
 #endif
   const int nv = V_LDS ? np : n;  // rows/cols of V that exist
   // A <- V' A V on the matrix cores (V in LDS); a lambda because the refinement stage's fall-back re-runs it
-  auto congruence = [&](const int part) {
+  auto congruence = [&](const int part, const bool t_only = false) {
     // A <- V' A V with v_mfma_f64_16x16x4_f64: T = A V (all 16x16 tiles), then A' = V' T (lower tiles; the
     // Jacobi sweeps read the lower triangle only).  Operand maps (verified on gfx950): lane l holds
     // A[l&15][l>>4], B[l>>4][l&15]; result reg r of lane l is C[(l>>4) + 4r][l&15].
@@ -472,6 +472,8 @@ __device__ __forceinline__ void proj_body(const ProjArgs& a, const int k, const 
       }
     }
     __syncthreads();
+    // t_only: the refinement stage takes the second product itself, on the tiles its waves own (it classifies B from the accumulators)
+    if (t_only) return;
     int tis[MAXT], tjs[MAXT];
 #pragma unroll
     for (int m = 0; m < MAXT; ++m) {
@@ -636,8 +638,24 @@ __device__ __forceinline__ void proj_body(const ProjArgs& a, const int k, const 
     }
     __syncthreads();
   };
+  // the refinement stage's state word (ping-pong variant), read in FRONT of the congruence: a block that enters the stage leaves the
+  // second product of the congruence to it (stage_b).  EVERY wave must have read the word before thread 0 rewrites it - a wave that
+  // loaded it after that store saw wait - 1, entered the stage and its barriers while the others skipped it (a barrier mismatch that
+  // showed only when three processes shared the card: the two-rank tests, one solve in five diverged); the barriers of the
+  // congruence stand between this read and either store (a cold block stores nothing)
+  int wait = 0, level = 0, credit = 0, gcred = 0;
+  double rdef = 0.0;      // estimate (upper bound) of the basis' defect |I - V'V|_F since it was last measured
+  bool stage_b = false;
+  if constexpr (PP) {
+    if (a.rstate) {
+      const int rs = a.rstate[4 * k]; wait = rs & 255; level = (rs >> 8) & 255; credit = (rs >> 16) & 255; gcred = (rs >> 24) & 15;
+      rdef = *reinterpret_cast<const double*>(a.rstate + 4 * k + 2);
+    }
+    // (a leader of a one-tile block owns no column of the split: it keeps the one-workgroup order of the phases)
+    stage_b = warm && a.refine != 0 && wait == 0 && role != 2 && !(role == 1 && npg < 32);
+  }
   if (warm && V_LDS) {
-    congruence(PP ? role : 0);
+    congruence(PP ? role : 0, stage_b);
     if (PP && role == 2) return;
   } else if (warm && PK) {
     pk_congruence();
@@ -755,16 +773,6 @@ __device__ __forceinline__ void proj_body(const ProjArgs& a, const int k, const 
   bool refined = false;
   int side_force = 0;     // refinement step accepted for ONE side of the spectrum: the reconstruction must use it (+1 positive, -1 negative)
   if constexpr (PP) {
-    int wait = 0, level = 0, credit = 0, gcred = 0;
-    double rdef = 0.0;      // estimate (upper bound) of the basis' defect |I - V'V|_F since it was last measured
-    if (a.rstate) {
-      const int rs = a.rstate[4 * k]; wait = rs & 255; level = (rs >> 8) & 255; credit = (rs >> 16) & 255; gcred = (rs >> 24) & 15;
-      rdef = *reinterpret_cast<const double*>(a.rstate + 4 * k + 2);
-    }
-    // EVERY wave must have read the block's back-off state before thread 0 rewrites it (the skip branch below does so at once): a
-    // wave that loaded the word after that store saw wait - 1, entered the stage and its barriers while the others skipped it - a
-    // barrier mismatch that showed only when three processes shared the card (the two-rank tests: one solve in five diverged)
-    __syncthreads();
     const int rmode = a.refine;
     if (warm && rmode != 0 && wait == 0) {
       constexpr int NW = NT / 64;
@@ -783,6 +791,12 @@ __device__ __forceinline__ void proj_body(const ProjArgs& a, const int k, const 
         tti[m] = ti; ttj[m] = tj;
       }
       d4_t g[2];
+      d4_t bt[2];           // the wave's tiles of B = V'T when the stage takes the congruence's second product itself (stage_b)
+      // The Gram product is not taken on every visit: a step with an antisymmetric K leaves (I + K + K^2 / 2)'(I + K + K^2 / 2) =
+      // I + K^4 / 4, so the defect of V grows by |K|_F^4 / 4 per step at most - the estimate rdef carries that bound from the last
+      // measurement, three visits in four run with R = 0 (no re-orthogonalisation term, a fifth of the stage's matrix work saved),
+      // and any visit whose estimate comes near the accepted error level measures again.  Zero-initialised state measures first.
+      const bool do_gram = !a.rstate || gcred == 0 || !(rdef <= 0.03 * a.refine_acc * tolv);
       // Gram matrix V'V on the wave's lower tiles (registers)
       auto gram = [&]() {
 #pragma unroll
@@ -849,8 +863,30 @@ __device__ __forceinline__ void proj_body(const ProjArgs& a, const int k, const 
       // only has to keep its inertia (b^2 < d_i d_j).  So the unresolved mass is kept per side and the side to rebuild from is the
       // smaller one when that passes, the other one when only that passes (measured on W40-D20 iterates at residual 4e-5: rejected
       // blocks 25 % -> 7 %; the near-degenerate pairs sit almost always among the negative eigenvalues).
-      auto analyse = [&]() {
-        double o2 = 0.0, q2 = 0.0, upp = 0.0, unn = 0.0, ux = 0.0, qd2 = 0.0;
+      // from_regs (the visit's first analysis, block arriving from the stage's own second product): B is still in the accumulators bt
+      // and is classified from there - T still stands in the A buffer while other waves run their second chain, so NOTHING is stored
+      // before the reduction's first barrier; behind it go the tiles of B, then the mirror entries (a diagonal tile's own upper half is
+      // overwritten in that order, as it was when the congruence stored B).  The Gram defect's sum rides in the same reduction (its own
+      // row of rsc: per lane, per wave, over the waves exactly as gram_diag's block_sum takes it)
+      auto analyse = [&](auto from_regs_) {
+        constexpr bool from_regs = decltype(from_regs_)::value;
+        double o2 = 0.0, q2 = 0.0, upp = 0.0, unn = 0.0, ux = 0.0, qd2 = 0.0, rl2 = 0.0;
+        d4_t ev[2];
+        if constexpr (from_regs) {
+          if (do_gram) {
+#pragma unroll
+            for (int m = 0; m < 2; ++m)
+              if (tti[m] >= 0)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                  const int i = 16 * tti[m] + lc + 4 * r, j = 16 * ttj[m] + lr;
+                  if (i < n && j < n) {
+                    if (i == j) { const double v = 1.0 - g[m][r]; rl2 += v * v; }
+                    else if (i > j) rl2 += 2.0 * g[m][r] * g[m][r];
+                  }
+                }
+          }
+        }
 #pragma unroll
         for (int m = 0; m < 2; ++m)
           if (tti[m] >= 0)
@@ -858,7 +894,9 @@ __device__ __forceinline__ void proj_body(const ProjArgs& a, const int k, const 
             for (int r = 0; r < 4; ++r) {
               const int i = 16 * tti[m] + lc + 4 * r, j = 16 * ttj[m] + lr;
               if (i > j && i < n) {
-                const double b = A[i * lda + j], rr = -g[m][r];
+                double b;
+                if constexpr (from_regs) b = bt[m][r]; else b = A[i * lda + j];
+                const double rr = -g[m][r];
                 const double li = dvec[i] * (1.0 + rdg[i]), lj = dvec[j] * (1.0 + rdg[j]);
                 const double gap = lj - li;
                 o2 += 2.0 * b * b;
@@ -866,9 +904,11 @@ __device__ __forceinline__ void proj_body(const ProjArgs& a, const int k, const 
                   const double e = (b + lj * rr) * rcp_nr2(gap), f = rr - e;
                   q2 += e * e + f * f;
                   qd2 += e * e * lj * lj + f * f * li * li;
-                  A[j * lda + i] = e;            // kept for the step in the mirror position (nothing reads the upper triangle of B)
+                  // kept for the step in the mirror position (nothing reads the upper triangle of B)
+                  if constexpr (from_regs) ev[m][r] = e; else A[j * lda + i] = e;
                 } else {
-                  A[j * lda + i] = __longlong_as_double(0x7ff8000000000000LL);      // "not resolved"
+                  const double unres = __longlong_as_double(0x7ff8000000000000LL);      // "not resolved"
+                  if constexpr (from_regs) ev[m][r] = unres; else A[j * lda + i] = unres;
                   q2 += 0.5 * rr * rr;
                   const double dd = dvec[i] * dvec[j];
                   if (b * b < dd) { if (dvec[i] > 0.0) upp += 2.0 * b * b; else unn += 2.0 * b * b; }   // same sign, inertia kept
@@ -884,18 +924,37 @@ __device__ __forceinline__ void proj_body(const ProjArgs& a, const int k, const 
         static_assert(NW == 16, "the refinement stage's reductions assume 16 waves");
         o2 = wave_sum(o2); q2 = wave_sum(q2); upp = wave_sum(upp); unn = wave_sum(unn); ux = wave_sum(ux); qd2 = wave_sum(qd2);
         if (lane == 0) { rsc[wv] = o2; rsc[16 + wv] = q2; rsc[32 + wv] = upp; rsc[48 + wv] = unn; rsc[64 + wv] = ux; rsc[80 + wv] = qd2; }
+        if constexpr (from_regs) { rl2 = wave_sum(rl2); if (lane == 0) rsc[112 + wv] = rl2; }      // (rsc has npg + 200 doubles)
         if (tid < 128) {
           const double dv = tid < n ? dvec[tid] : 0.0;
           const unsigned long long bp = __ballot(dv > 0.0), bn = __ballot(dv < 0.0);
           if (lane == 0) { rsc[96 + 2 * wv] = (double)__popcll(bp); rsc[97 + 2 * wv] = (double)__popcll(bn); }
         }
         __syncthreads();
-        if (tid < 96) {
-          const double v = row_sum16(rsc[tid]);
+        if constexpr (from_regs) {
+          // (every chain of the second product is through: T is dead)
+#pragma unroll
+          for (int m = 0; m < 2; ++m)
+            if (tti[m] >= 0) {
+#pragma unroll
+              for (int r = 0; r < 4; ++r) A[(16 * tti[m] + lc + 4 * r) * lda + 16 * ttj[m] + lr] = bt[m][r];
+            }
+#pragma unroll
+          for (int m = 0; m < 2; ++m)
+            if (tti[m] >= 0)
+#pragma unroll
+              for (int r = 0; r < 4; ++r) {
+                const int i = 16 * tti[m] + lc + 4 * r, j = 16 * ttj[m] + lr;
+                if (i > j && i < n) A[j * lda + i] = ev[m][r];
+              }
+        }
+        if (tid < (from_regs ? 128 : 96)) {
+          const double v = row_sum16(rsc[tid]);      // (from_regs: row 6 holds the sign counts and is not a sum; its slot of red is not read)
           if ((tid & 15) == 0) red[tid >> 4] = v;
         }
         __syncthreads();
         off2 = uniform(red[0]); k2 = uniform(red[1]); unpp = uniform(red[2]); unnn = uniform(red[3]); unx = uniform(red[4]); kd2 = uniform(red[5]);
+        if constexpr (from_regs) { if (do_gram) r2 = uniform(red[7]); }
         cpos = uniform(rsc[96] + rsc[98]); cneg = uniform(rsc[97] + rsc[99]);
         __syncthreads();      // (the reduction scratch is free again: the paths that follow reuse it without another barrier)
       };
@@ -1002,25 +1061,99 @@ __device__ __forceinline__ void proj_body(const ProjArgs& a, const int k, const 
           far = fmin(pred_pos, pred_neg) > 10.0 * accT;
         }
       };
-      // The Gram product is not taken on every visit: a step with an antisymmetric K leaves (I + K + K^2 / 2)'(I + K + K^2 / 2) =
-      // I + K^4 / 4, so the defect of V grows by |K|_F^4 / 4 per step at most - the estimate rdef carries that bound from the last
-      // measurement, three visits in four run with R = 0 (no re-orthogonalisation term, a fifth of the stage's matrix work saved),
-      // and any visit whose estimate comes near the accepted error level measures again.  Zero-initialised state measures first.
-      const bool do_gram = !a.rstate || gcred == 0 || !(rdef <= 0.03 * a.refine_acc * tolv);
       bool measured = do_gram;
-      if (do_gram) {
-        gram();
-        RST(1)
-        if (tid < npg) dvec[tid] = tid < n ? A[tid * lda + tid] : 0.0;
-        r2 = uniform(gram_diag());           // (two barriers inside: dvec / rdg are visible afterwards)
+      if (stage_b) {
+        // The second product of the congruence, B = V'T, dealt as the stage deals its tiles: what a wave classifies is what it has just
+        // accumulated (same chain per tile as the congruence runs: identical bits).  The analysis needs nothing of the other waves but
+        // the diagonal, so a wave that owns a diagonal tile runs that chain first and publishes its 16 entries of dvec and rdg; behind
+        // ONE barrier the waves with a single tile classify it on the vector units while the others run their second chain.
+        const int hc = nt >= 6 ? nt / 3 : 1;      // (two workgroups per block: the helper's tile columns 1 .. hc, as the congruence splits them)
+        auto own = [&](const int m) { return role != 1 || ttj[m] == 0 || ttj[m] > hc; };
+        auto chains = [&](auto m_) {
+          constexpr int m = decltype(m_)::value;
+          d4_t c = {0.0, 0.0, 0.0, 0.0}, c2 = {0.0, 0.0, 0.0, 0.0};
+          if (tti[m] >= 0) {
+            if (own(m)) {
+              const double* ap = V + lc + (size_t)(16 * tti[m] + lr) * ldv;   // V'[i][k] = V[k][i]
+              const double* bp = A + lc * lda + 16 * ttj[m] + lr;             // T[k][j]
+              for (int kk = 0; kk < ks; ++kk) c = __builtin_amdgcn_mfma_f64_16x16x4f64(ap[4 * kk], bp[4 * kk * lda], c, 0, 0, 0);
+            }
+            if (do_gram) {
+              const double* ap = V + lc + (size_t)(16 * tti[m] + lr) * ldv;
+              const double* bp = V + lc + (size_t)(16 * ttj[m] + lr) * ldv;
+              for (int kk = 0; kk < ks; ++kk) c2 = __builtin_amdgcn_mfma_f64_16x16x4f64(ap[4 * kk], bp[4 * kk], c2, 0, 0, 0);
+            }
+          }
+          bt[m] = c; g[m] = c2;
+        };
+        // B_ii and R_ii of a diagonal tile (zero in the padding, R = 0 on a visit without the Gram product)
+        auto publish = [&](auto m_) {
+          constexpr int m = decltype(m_)::value;
+          if (tti[m] >= 0 && tti[m] == ttj[m]) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+              if (lr == lc + 4 * r) {
+                const int i = 16 * tti[m] + lr;
+                dvec[i] = i < n ? bt[m][r] : 0.0;
+                rdg[i] = (do_gram && i < n) ? 1.0 - g[m][r] : 0.0;
+              }
+          }
+        };
+        const std::integral_constant<int, 0> m0{}; const std::integral_constant<int, 1> m1{};
+        if (role == 1) {
+          // leader of a split block: its own tiles and the whole Gram product first - they run while the helper's tiles travel - then
+          // the hand-over, with the helper's tiles taken by the waves that own them in the stage (the element a lane reads is the
+          // element of the accumulator it would have computed: 64 r + lane of the tile)
+          chains(m0); chains(m1);
+          RST(1)
+          const unsigned want = a.sseen[k] + 1u;
+          if (tid == 0) {
+            long long spins = 0;
+            while (__hip_atomic_load(a.sack + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < want) {
+              __builtin_amdgcn_s_sleep(2);
+              if (++spins > a.spin_limit) { atomicExch(a.serr, 1); break; }
+            }
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");       // (one invalidate, after the count has arrived - not one per poll)
+          }
+          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+          __syncthreads();
+          const double* const in = a.sB + (size_t)k * kSplitTileDoubles;
+#pragma unroll
+          for (int m = 0; m < 2; ++m)
+            if (tti[m] >= 0 && !own(m)) {
+#pragma unroll
+              for (int r = 0; r < 4; ++r)
+                bt[m][r] = __hip_atomic_load(in + (size_t)(tti[m] * nt + ttj[m]) * 256 + 64 * r + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+          __syncthreads();
+          if (tid == 0) a.sseen[k] = want;
+          publish(m0); publish(m1);
+          __syncthreads();
+        } else {
+          const bool second_first = tti[1] >= 0 && tti[1] == ttj[1];      // (wave-uniform; no wave owns two diagonal tiles: their numbers never differ by 16)
+          if (second_first) { chains(m1); publish(m1); } else { chains(m0); publish(m0); }
+          RST(1)
+          __syncthreads();
+          if (second_first) chains(m0); else chains(m1);
+        }
+        if (!do_gram) r2 = rdef * rdef;
+        RST(2)
+        analyse(std::true_type{});           // (r2 of a visit with the Gram product comes out of its reduction)
       } else {
-        g[0] = d4_t{0.0, 0.0, 0.0, 0.0}; g[1] = d4_t{0.0, 0.0, 0.0, 0.0};
-        if (tid < npg) { dvec[tid] = tid < n ? A[tid * lda + tid] : 0.0; rdg[tid] = 0.0; }
-        r2 = rdef * rdef;
-        __syncthreads();
+        if (do_gram) {
+          gram();
+          RST(1)
+          if (tid < npg) dvec[tid] = tid < n ? A[tid * lda + tid] : 0.0;
+          r2 = uniform(gram_diag());           // (two barriers inside: dvec / rdg are visible afterwards)
+        } else {
+          g[0] = d4_t{0.0, 0.0, 0.0, 0.0}; g[1] = d4_t{0.0, 0.0, 0.0, 0.0};
+          if (tid < npg) { dvec[tid] = tid < n ? A[tid * lda + tid] : 0.0; rdg[tid] = 0.0; }
+          r2 = rdef * rdef;
+          __syncthreads();
+        }
+        RST(2)
+        analyse(std::false_type{});
       }
-      RST(2)
-      analyse();
       decide();
       RST(3)
       // What first order cannot resolve late in a solve is almost always ONE pair of eigenvalues on either side of zero (two thirds of
@@ -1085,7 +1218,7 @@ __device__ __forceinline__ void proj_body(const ProjArgs& a, const int k, const 
             if (tid < npg) dvec[tid] = tid < n ? A[tid * lda + tid] : 0.0;
             __syncthreads();
           }
-          analyse();
+          analyse(std::false_type{});
           decide();
           if (pivots >= a.refine_pivots || refined || side_force != 0 || !(r2 <= 1e-4) || !(k2 <= a.refine_k2cap) || !(unx > 0.0)) break;
         }
