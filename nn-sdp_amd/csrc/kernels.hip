@@ -265,6 +265,328 @@ static constexpr int kPpLda = 99;          // ping-pong variant: fixed stride of
 static constexpr int kPpLdp = 100;         // ping-pong variant: stride of the sweep layout (even: aligned 16-byte row pairs)
 static constexpr int kSysHead = 16 + 66;   // red[16], sel[npg + 2 <= 130 ints] in front of A (fixed offsets)
 
+// cycle stamps of the diagnostic build (-DNNSDP_STAMPS; tools/refine_stamps.py, tools/packed_stamps.py) into proj_body's rst[] / st_acc[]
+#ifdef NNSDP_STAMPS
+#define RST(i) { rst[i] = clock64(); }
+#define STAMP(i, tprev) { long long tn_ = clock64(); st_acc[i] += tn_ - tprev; tprev = tn_; }
+#else
+#define RST(i)
+#define STAMP(i, tprev)
+#endif
+
+// One block of a launch as the phases below see it: proj_body's geometry and pointers under their names, filled once per block
+struct ProjBlock {
+  int n, np, npg, half, lda, nrow, ldv, nv, tid;
+  double *A, *desc, *red, *V;
+  const double* nuk; int* sel;
+  // element (i, j) of the lower triangle (i >= j) / of the symmetric matrix in the variant's storage (PK: the packed triangle)
+  template <bool PK> __device__ __forceinline__ int ixl(int i, int j) const { return PK ? ((i * (i + 1)) >> 1) + j : i * lda + j; }
+  template <bool PK> __device__ __forceinline__ int ixs(int i, int j) const { return i >= j ? ixl<PK>(i, j) : ixl<PK>(j, i); }
+};
+
+// lower tile number t -> (ti, tj), row by row; (-1, -1) past the last of the ntl tiles
+__device__ __forceinline__ void proj_lower_tile(const int t, const int ntl, int& ti, int& tj) {
+  ti = -1; tj = -1;
+  if (t < ntl) { ti = 0; while ((ti + 1) * (ti + 2) / 2 <= t) ++ti; tj = t - ti * (ti + 1) / 2; }
+}
+
+// leader of a split block: waits (thread 0 polls) until the helper has released the block's next exchange; returns its number
+__device__ __forceinline__ unsigned proj_await_helper(const ProjArgs& a, const int k, const int tid) {
+  const unsigned want = a.sseen[k] + 1u;
+  if (tid == 0) {
+    long long spins = 0;
+    while (__hip_atomic_load(a.sack + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < want) {
+      __builtin_amdgcn_s_sleep(2);
+      if (++spins > a.spin_limit) { atomicExch(a.serr, 1); break; }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");       // (one invalidate, after the count has arrived - not one per poll)
+  }
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  __syncthreads();
+  return want;
+}
+// the largest (pm, pidx) over the workgroup (ties: the larger index) in every thread; cs1 / cs2: NW doubles of LDS each
+template <int NW>
+__device__ __forceinline__ void proj_block_argmax(double& pm, int& pidx, double* const cs1, double* const cs2) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const double om = __shfl_xor(pm, o, 64);
+    const int oi = __shfl_xor(pidx, o, 64);
+    if (om > pm || (om == pm && oi > pidx)) { pm = om; pidx = oi; }
+  }
+  if (lane == 0) { cs1[wv] = pm; cs2[wv] = (double)pidx; }
+  __syncthreads();
+  pm = 0.0; pidx = 0;
+  for (int w_ = 0; w_ < NW; ++w_) { const double om = cs1[w_]; const int oi = (int)cs2[w_]; if (om > pm || (om == pm && oi > pidx)) { pm = om; pidx = oi; } }
+}
+
+// A = sym(nu_k) in the variant's storage (PK: the lower triangle only), zero in the padding; returns the thread's share of |A|_F^2
+template <int NT, bool PK>
+__device__ __forceinline__ double proj_fill_sym(const ProjBlock& b) {
+  const int n = b.n, npg = b.npg, tid = b.tid;
+  double fro2 = 0.0;
+  for (int j = tid >> 6; j < npg; j += NT >> 6)
+    for (int i = (tid & 63) + (PK ? j : 0); i < npg; i += 64) {
+      double v = 0.0;
+      if (i < n && j < n) v = 0.5 * (b.nuk[(size_t)j * n + i] + b.nuk[(size_t)i * n + j]);
+      b.A[b.ixl<PK>(i, j)] = v;
+      fro2 += (PK && i != j) ? 2.0 * v * v : v * v;
+    }
+  return fro2;
+}
+// the load of the round-robin, systolic and packed variants (the ping-pong variant loads linearly, in proj_body); returns |A|_F^2
+template <bool V_LDS, int NT, bool PK>
+__device__ __forceinline__ double proj_load_sym(const ProjBlock& b, const ProjArgs& a, const int k, const bool warm) {
+  const int n = b.n, npg = b.npg, ldv = b.ldv, tid = b.tid;
+  double* const V = b.V;
+  const double fro2 = block_sum(proj_fill_sym<NT, PK>(b), b.red);
+  // ---- starting basis
+  if (V_LDS) {
+    for (int j = tid >> 6; j < npg; j += NT >> 6)
+      for (int i = tid & 63; i < npg; i += 64) {
+        double v = (i == j) ? 1.0 : 0.0;
+        if (warm && i < n && j < n) v = a.Vg[a.coff[k] + (size_t)j * n + i];
+        V[i + j * ldv] = v;
+      }
+  } else if (!warm) {
+    for (int j = tid >> 6; j < n; j += NT >> 6)
+      for (int i = tid & 63; i < n; i += 64) V[i + (size_t)j * ldv] = (i == j) ? 1.0 : 0.0;
+  }
+  return fro2;
+}
+
+// (blocks too large to keep V in LDS) A <- V' A V as two register-tiled products (4 x 2 tiles, accumulators in VGPRs):
+//   T = A V   (written over A),   A' = V' T   (written over T)
+template <int NT>
+__device__ __forceinline__ void proj_congruence_regs(const ProjBlock& b) {
+  const int np = b.np, nv = b.nv, lda = b.lda, ldv = b.ldv, tid = b.tid;
+  double* const A = b.A; double* const V = b.V;
+  constexpr int kTilesMax = 2048 / NT;               // (128/4) * (128/2) tiles at most
+  const int ti_n = (np + 3) >> 2, tj_n = np >> 1;    // tile grid
+  double acc[kTilesMax][8];
+#pragma unroll
+  for (int pass = 0; pass < 2; ++pass) {
+#pragma unroll
+    for (int m = 0; m < kTilesMax; ++m) {
+      int t = tid + m * NT;
+      int tj = t / ti_n, ti = t - tj * ti_n;         // consecutive threads -> consecutive row tiles
+      double c0 = 0, c1 = 0, c2 = 0, c3 = 0, d0 = 0, d1 = 0, d2 = 0, d3 = 0;
+      if (tj < tj_n) {
+        int i0 = ti * 4, j0 = tj * 2;
+        int i1 = min(i0 + 1, np - 1), i2 = min(i0 + 2, np - 1), i3 = min(i0 + 3, np - 1);
+        if (pass == 0) {
+          // T[i][j] = sum_l A[i][l] V[l][j]
+          const double* v0 = V + (size_t)min(j0, nv - 1) * ldv;
+          const double* v1 = V + (size_t)min(j0 + 1, nv - 1) * ldv;
+          const double *a0 = A + i0 * lda, *a1 = A + i1 * lda, *a2 = A + i2 * lda, *a3 = A + i3 * lda;
+          for (int l = 0; l < nv; ++l) {
+            double x0 = v0[l], x1 = v1[l];
+            double y0 = a0[l], y1 = a1[l], y2 = a2[l], y3 = a3[l];
+            c0 += y0 * x0; c1 += y1 * x0; c2 += y2 * x0; c3 += y3 * x0;
+            d0 += y0 * x1; d1 += y1 * x1; d2 += y2 * x1; d3 += y3 * x1;
+          }
+          if (j0 >= nv) { c0 = a0[j0]; c1 = a1[j0]; c2 = a2[j0]; c3 = a3[j0]; }
+          if (j0 + 1 >= nv) { d0 = a0[j0 + 1]; d1 = a1[j0 + 1]; d2 = a2[j0 + 1]; d3 = a3[j0 + 1]; }
+        } else {
+          // A'[i][j] = sum_l V[l][i] T[l][j]
+          const double *u0 = V + (size_t)min(i0, nv - 1) * ldv, *u1 = V + (size_t)min(i1, nv - 1) * ldv;
+          const double *u2 = V + (size_t)min(i2, nv - 1) * ldv, *u3 = V + (size_t)min(i3, nv - 1) * ldv;
+          for (int l = 0; l < nv; ++l) {
+            double x0 = A[l * lda + j0], x1 = A[l * lda + j0 + 1];
+            double y0 = u0[l], y1 = u1[l], y2 = u2[l], y3 = u3[l];
+            c0 += y0 * x0; c1 += y1 * x0; c2 += y2 * x0; c3 += y3 * x0;
+            d0 += y0 * x1; d1 += y1 * x1; d2 += y2 * x1; d3 += y3 * x1;
+          }
+          if (i0 >= nv) { c0 = A[i0 * lda + j0]; d0 = A[i0 * lda + j0 + 1]; }
+          if (i1 >= nv) { c1 = A[i1 * lda + j0]; d1 = A[i1 * lda + j0 + 1]; }
+          if (i2 >= nv) { c2 = A[i2 * lda + j0]; d2 = A[i2 * lda + j0 + 1]; }
+          if (i3 >= nv) { c3 = A[i3 * lda + j0]; d3 = A[i3 * lda + j0 + 1]; }
+        }
+      }
+      acc[m][0] = c0; acc[m][1] = c1; acc[m][2] = c2; acc[m][3] = c3;
+      acc[m][4] = d0; acc[m][5] = d1; acc[m][6] = d2; acc[m][7] = d3;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int m = 0; m < kTilesMax; ++m) {
+      int t = tid + m * NT;
+      int tj = t / ti_n, ti = t - tj * ti_n;
+      if (tj < tj_n) {
+        int i0 = ti * 4, j0 = tj * 2;
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if (i0 + r < np) { A[(i0 + r) * lda + j0] = acc[m][r]; A[(i0 + r) * lda + j0 + 1] = acc[m][4 + r]; }
+      }
+    }
+    __syncthreads();
+  }
+  // exact symmetry into the lower triangle (the two passes round differently)
+  for (int j = tid >> 6; j < np; j += NT >> 6)
+    for (int i = tid & 63; i < np; i += 64)
+      if (i > j) A[i * lda + j] = 0.5 * (A[i * lda + j] + A[j * lda + i]);
+  __syncthreads();
+}
+
+// selection list in index order, built by two (three: packed variant) waves with ballots (positions 0..127 / 0..191)
+template <bool PK, bool PADDED>
+__device__ __forceinline__ void proj_select_side(const ProjBlock& b, const int side_force) {
+  const int n = b.n, np = b.np, npg = b.npg, tid = b.tid;
+  double* const A = b.A; double* const red = b.red; int* const sel = b.sel;
+  const int nl = PADDED ? np : n;   // positions that can hold an eigenvalue (the padded one is exactly 0: never selected)
+  constexpr int kSelThreads = PK ? 192 : 128;
+  int* cnt = reinterpret_cast<int*>(red);
+  const int ln = tid & 63, w2 = tid >> 6;
+  double l = 0.0;
+  if (tid < kSelThreads) {
+    if (tid < nl) l = A[b.ixl<PK>(tid, tid)];
+    const unsigned long long bp = __ballot(l > 0.0), bn = __ballot(l < 0.0);
+    if (ln == 0) { cnt[2 * w2] = __popcll(bp); cnt[2 * w2 + 1] = __popcll(bn); }
+  }
+  if (!PK && tid == 0) { cnt[4] = 0; cnt[5] = 0; }
+  __syncthreads();
+  const int npos = cnt[0] + cnt[2] + cnt[4], nneg = cnt[1] + cnt[3] + cnt[5];
+  const bool up = side_force != 0 ? side_force > 0 : npos <= nneg;
+  if (tid < kSelThreads) {
+    const bool me = up ? (l > 0.0) : (l < 0.0);
+    const unsigned long long mk = __ballot(me);
+    int before = 0;
+    for (int q = 0; q < w2; ++q) before += up ? cnt[2 * q] : cnt[2 * q + 1];
+    const int rank = __popcll(mk & ((1ull << ln) - 1ull)) + before;
+    if (me) sel[rank] = tid;
+  }
+  if (tid == 0) { sel[npg] = up ? npos : nneg; sel[npg + 1] = up ? 1 : 0; }
+}
+
+// W = sum_t lam_t v_t v_t' over the selected eigenpairs as MFMA tiles (K = nsel padded to 4), V in LDS; lower
+// tiles are computed and mirrored; !use_pos: W = sym(nu) - (negative part)
+template <int NT>
+__device__ __forceinline__ void proj_reconstruct_mfma(const ProjBlock& b, double* const wk, const int nsel, const bool use_pos) {
+  const int n = b.n, lda = b.lda, ldv = b.ldv, tid = b.tid;
+  const double* const A = b.A; const double* const V = b.V; const int* const sel = b.sel; const double* const nuk = b.nuk;
+  constexpr int NW = NT / 64;
+  const int nt = (n + 15) >> 4, ntl = nt * (nt + 1) / 2, ks = (nsel + 3) >> 2;
+  const int lane = tid & 63, wv = tid >> 6;
+  const int lr = lane & 15, lc = lane >> 4;
+  for (int t = wv; t < ntl; t += NW) {
+    int ti, tj;
+    proj_lower_tile(t, ntl, ti, tj);
+    d4_t c = {0.0, 0.0, 0.0, 0.0};
+    double sn[4] = {0.0, 0.0, 0.0, 0.0};      // sym(nu) of the tile, requested before the products (L2 latency behind the matrix work)
+    if (!use_pos) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int row = 16 * ti + lc + 4 * r, col = 16 * tj + lr;
+        if (row < n && col < n) sn[r] = 0.5 * (nuk[(size_t)col * n + row] + nuk[(size_t)row * n + col]);
+      }
+    }
+    for (int kk = 0; kk < ks; ++kk) {
+      int tt = 4 * kk + lc;
+      double av = 0.0, bv = 0.0;
+      if (tt < nsel) {
+        int l = sel[tt];
+        av = A[l * lda + l] * V[16 * ti + lr + (size_t)l * ldv];
+        bv = V[16 * tj + lr + (size_t)l * ldv];
+      }
+      c = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, c, 0, 0, 0);
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      int row = 16 * ti + lc + 4 * r, col = 16 * tj + lr;
+      if (row < n && col < n) {
+        double v = c[r];
+        if (!use_pos) v = sn[r] - v;
+        wk[(size_t)col * n + row] = v;
+        if (ti != tj) wk[(size_t)row * n + col] = v;
+      }
+    }
+  }
+}
+// packed variant: W = sum_t lam_t v_t v_t' on the matrix cores, the selected eigenvectors staged through LDS 16 at a time
+// (k-major panel in the space the sweeps' eigenvector panel used; every thread re-reading its 2 nsel operands from L2 - the form
+// below - was 16 % of a warm launch of the 151-wide blocks).  Lower tiles, four per wave at most (55 tiles at n = 160).
+template <int NT>
+__device__ __forceinline__ void proj_reconstruct_packed(const ProjBlock& b, double* const wk, const int nsel, const bool use_pos) {
+  const int n = b.n, npg = b.npg, ldv = b.ldv, tid = b.tid;
+  const double* const A = b.A; const double* const V = b.V; double* const red = b.red; const int* const sel = b.sel; const double* const nuk = b.nuk;
+  constexpr int NW = NT / 64, kPanelLd = 161, kTilesPerWave = 4;
+  double* const Pn = red + 16 + (npg >> 1) + 2;       // 16 x kPanelLd
+  double* const lamc = Pn + 16 * kPanelLd;            // the chunk's 16 eigenvalues (0 past the selection)
+  const int nt = (n + 15) >> 4, ntl = nt * (nt + 1) / 2;
+  const int lane = tid & 63, wv = tid >> 6, lr = lane & 15, lc = lane >> 4;
+  int tti[kTilesPerWave], ttj[kTilesPerWave];
+  d4_t acc[kTilesPerWave];
+#pragma unroll
+  for (int m = 0; m < kTilesPerWave; ++m) { proj_lower_tile(wv + m * NW, ntl, tti[m], ttj[m]); acc[m] = d4_t{0.0, 0.0, 0.0, 0.0}; }
+  __syncthreads();      // (the selection list is complete; the panel space is free)
+  for (int c0 = 0; c0 < nsel; c0 += 16) {
+    {
+      const int kk = tid >> 6, l = c0 + kk < nsel ? sel[c0 + kk] : -1;
+      for (int i = tid & 63; i < 16 * nt; i += 64) Pn[kk * kPanelLd + i] = (l >= 0 && i < n) ? V[i + (size_t)l * ldv] : 0.0;
+      if ((tid & 63) == 0) lamc[kk] = l >= 0 ? A[b.ixl<true>(l, l)] : 0.0;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int m = 0; m < kTilesPerWave; ++m)
+      if (tti[m] >= 0) {
+#pragma unroll
+        for (int k4 = 0; k4 < 4; ++k4) {
+          const int kx = 4 * k4 + lc;
+          const double av = lamc[kx] * Pn[kx * kPanelLd + 16 * tti[m] + lr], bv = Pn[kx * kPanelLd + 16 * ttj[m] + lr];
+          acc[m] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc[m], 0, 0, 0);
+        }
+      }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int m = 0; m < kTilesPerWave; ++m)
+    if (tti[m] >= 0) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int row = 16 * tti[m] + lc + 4 * r, col = 16 * ttj[m] + lr;
+        if (row < n && col < n) {
+          double v = acc[m][r];
+          if (!use_pos) v = 0.5 * (nuk[(size_t)col * n + row] + nuk[(size_t)row * n + col]) - v;
+          wk[(size_t)col * n + row] = v;
+          if (tti[m] != ttj[m]) wk[(size_t)row * n + col] = v;
+        }
+      }
+    }
+}
+// V in HBM, the matrix unpacked: every thread sums its element over the selection
+template <int NT>
+__device__ __forceinline__ void proj_reconstruct_scalar(const ProjBlock& b, double* const wk, const int nsel, const bool use_pos, const int pofs) {
+  const int n = b.n, ldv = b.ldv, tid = b.tid;
+  const double* const A = b.A; const double* const V = b.V; const int* const sel = b.sel; const double* const nuk = b.nuk;
+  for (int j = tid >> 6; j < n; j += NT >> 6)
+    for (int i = tid & 63; i < n; i += 64) {
+      double s = 0.0;
+      for (int t = 0; t < nsel; ++t) {
+        int l = sel[t], lv = l - pofs;   // V in HBM is stored without the padded column
+        s += A[b.ixl<false>(l, l)] * V[i + (size_t)lv * ldv] * V[j + (size_t)lv * ldv];
+      }
+      double nij = nuk[(size_t)j * n + i], nji = nuk[(size_t)i * n + j];
+      if (!use_pos) s = 0.5 * (nij + nji) - s;
+      wk[(size_t)j * n + i] = s;
+    }
+}
+
+// nu <- w + kappa (nu - w) (penalty change), and the eigenvectors of a block that kept them in LDS, for the next warm start
+template <bool V_LDS, int NT>
+__device__ __forceinline__ void proj_rescale_store(const ProjBlock& b, const ProjArgs& a, const int k, const double kap, const double* const wk, double* const nuw, const int pofs) {
+  const int n = b.n, ldv = b.ldv, tid = b.tid;
+  const double* const V = b.V;
+  if (kap != 1.0) {
+    __syncthreads();
+    for (int idx = tid; idx < n * n; idx += NT) { double wv = wk[idx]; nuw[idx] = wv + kap * (nuw[idx] - wv); }
+  }
+  if (V_LDS) {
+    double* vg = a.Vg + a.coff[k];
+    for (int j = tid >> 6; j < n; j += NT >> 6)
+      for (int i = tid & 63; i < n; i += 64) vg[(size_t)j * n + i] = V[i + (j + pofs) * ldv];
+  }
+}
+
 // ALG = 2: register-resident systolic sweeps (below).  SPW = pair slots (2 matrix rows each) per wave, RPW = eigenvector
 // rows per wave; NT/64 * SPW >= ceil(n/2) and NT/64 * RPW >= n + 1 for every block of the launch.
 template <bool V_LDS, int NT, int ALG = 0, int SPW = 1, int RPW = 1>
@@ -284,18 +606,15 @@ __device__ __forceinline__ void proj_body(const ProjArgs& a, const int k, const 
   const int np = (n + 1) & ~1;   // Jacobi dimension (even)
   const int npg = (n + 15) & ~15;  // storage / MFMA dimension (multiple of 16; zero rows, identity in V)
   const int half = np >> 1;
-  constexpr bool PPL = ALG == 3;   // ping-pong sweeps keep a one-cell border around the matrix: 2 more rows / columns of storage
-  const int lda = PPL ? kPpLda : npg + 1;    // odd stride (in doubles): column walks hit distinct banks; a constant for the ping-pong variant (immediate LDS offsets)
-  const int nrow = PPL ? npg + 2 : npg;      // rows of LDS storage per matrix
+  // (ping-pong sweeps keep a one-cell border around the matrix: 2 more rows / columns of storage)
+  const int lda = PP ? kPpLda : npg + 1;    // odd stride (in doubles): column walks hit distinct banks; a constant for the ping-pong variant (immediate LDS offsets)
+  const int nrow = PP ? npg + 2 : npg;      // rows of LDS storage per matrix
   const int tid = threadIdx.x;
   // systolic variant: reduction scratch and the selection list sit in FRONT of A at fixed offsets, because the sweeps
   // reuse the (then dead) A / V storage as exchange scratch whatever this block's own size is
   double* A = SYS ? lds + kSysHead : lds;
   // 2 buffers x half pair descriptors {c, s, (p, q), pad} = 4 doubles each, 16-byte aligned
-  double* desc = A + (PPL ? (size_t)nrow * kPpLdp : PK ? ((((size_t)npg * (npg + 1)) / 2 + 1) & ~(size_t)1) : (((size_t)nrow * lda + 1) & ~(size_t)1));
-  // element (i, j) of the lower triangle (i >= j) / of the symmetric matrix in the variant's storage
-  auto ixl = [&](int i, int j) { return PK ? ((i * (i + 1)) >> 1) + j : i * lda + j; };
-  auto ixs = [&](int i, int j) { return i >= j ? ixl(i, j) : ixl(j, i); };
+  double* desc = A + (PP ? (size_t)nrow * kPpLdp : PK ? ((((size_t)npg * (npg + 1)) / 2 + 1) & ~(size_t)1) : (((size_t)nrow * lda + 1) & ~(size_t)1));
   double* red = SYS ? lds : desc + 4 * npg;   // 16 doubles of reduction scratch
   int* sel = reinterpret_cast<int*>(red + 16);  // npg + 2 ints: eigen-indices on the chosen side, counters
   double* V;
@@ -304,13 +623,14 @@ __device__ __forceinline__ void proj_body(const ProjArgs& a, const int k, const 
   else { V = a.Vg + a.coff[k]; ldv = n; }
   const double* nuk = a.nu + a.coff[k];
 
+  const int nv = V_LDS ? np : n;  // rows/cols of V that exist
+  const ProjBlock b{n, np, npg, half, lda, nrow, ldv, nv, tid, A, desc, red, V, nuk, sel};
+  auto ixl = [&](int i, int j) { return b.ixl<PK>(i, j); };
+  auto ixs = [&](int i, int j) { return b.ixs<PK>(i, j); };
 #ifdef NNSDP_STAMPS
   long long sec_t[6]; sec_t[0] = clock64();
-  long long rst[20];
+  long long rst[20], st_acc[4] = {0, 0, 0, 0};
   for (int i_ = 0; i_ < 20; ++i_) rst[i_] = 0;
-#define RST(i) { rst[i] = clock64(); }
-#else
-#define RST(i)
 #endif
   // ---- load: A = sym(nu_k) (full, both triangles, for the warm-start products), padded row/col zero; starting basis
   double fro2 = 0.0;
@@ -381,42 +701,12 @@ __device__ __forceinline__ void proj_body(const ProjArgs& a, const int k, const 
     RST(14)
     fro2 = block_sum(fro2, red);
   } else {
-  if constexpr (PK) {
-    for (int j = tid >> 6; j < npg; j += NT >> 6)
-      for (int i = (tid & 63) + j; i < npg; i += 64) {
-        double v = 0.0;
-        if (i < n && j < n) v = 0.5 * (nuk[(size_t)j * n + i] + nuk[(size_t)i * n + j]);
-        A[ixl(i, j)] = v;
-        fro2 += (i == j) ? v * v : 2.0 * v * v;
-      }
-  } else {
-  for (int j = tid >> 6; j < npg; j += NT >> 6)
-    for (int i = tid & 63; i < npg; i += 64) {
-      double v = 0.0;
-      if (i < n && j < n) v = 0.5 * (nuk[(size_t)j * n + i] + nuk[(size_t)i * n + j]);
-      A[i * lda + j] = v;
-      fro2 += v * v;
-    }
-  }
-  fro2 = block_sum(fro2, red);
-  // ---- starting basis
-  if (V_LDS) {
-    for (int j = tid >> 6; j < npg; j += NT >> 6)
-      for (int i = tid & 63; i < npg; i += 64) {
-        double v = (i == j) ? 1.0 : 0.0;
-        if (warm && i < n && j < n) v = a.Vg[a.coff[k] + (size_t)j * n + i];
-        V[i + j * ldv] = v;
-      }
-  } else if (!warm) {
-    for (int j = tid >> 6; j < n; j += NT >> 6)
-      for (int i = tid & 63; i < n; i += 64) V[i + (size_t)j * ldv] = (i == j) ? 1.0 : 0.0;
-  }
+  fro2 = proj_load_sym<V_LDS, NT, PK>(b, a, k, warm);
   }
   __syncthreads();
 #ifdef NNSDP_STAMPS
   sec_t[1] = clock64();
 #endif
-  const int nv = V_LDS ? np : n;  // rows/cols of V that exist
   // A <- V' A V on the matrix cores (V in LDS); a lambda because the refinement stage's fall-back re-runs it
   auto congruence = [&](const int part, const bool t_only = false) {
     // A <- V' A V with v_mfma_f64_16x16x4_f64: T = A V (all 16x16 tiles), then A' = V' T (lower tiles; the
@@ -434,13 +724,7 @@ __device__ __forceinline__ void proj_body(const ProjArgs& a, const int k, const 
     auto colof = [&](int c) { return part == 0 ? c : part == 2 ? c + 1 : (c == 0 ? 0 : hc + c); };
     // lower tile number t of this part -> (ti, tj); false past the end
     auto lower_tile = [&](int t, int& ti, int& tj) {
-      if (part == 0) {
-        if (t >= nt * (nt + 1) / 2) return false;
-        ti = 0;
-        while ((ti + 1) * (ti + 2) / 2 <= t) ++ti;
-        tj = t - ti * (ti + 1) / 2;
-        return true;
-      }
+      if (part == 0) { proj_lower_tile(t, nt * (nt + 1) / 2, ti, tj); return ti >= 0; }
       for (int c = 0; c < ncol; ++c) {
         const int cj = colof(c), cnt = nt - cj;
         if (t < cnt) { tj = cj; ti = cj + t; return true; }
@@ -524,17 +808,7 @@ __device__ __forceinline__ void proj_body(const ProjArgs& a, const int k, const 
     }
     if (part == 1) {
       // leader: the helper's tiles (columns 1 .. hc), one per wave and round, behind an acquire of the exchange count
-      const unsigned want = a.sseen[k] + 1u;
-      if (tid == 0) {
-        long long spins = 0;
-        while (__hip_atomic_load(a.sack + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < want) {
-          __builtin_amdgcn_s_sleep(2);
-          if (++spins > a.spin_limit) { atomicExch(a.serr, 1); break; }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");       // (one invalidate, after the count has arrived - not one per poll)
-      }
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-      __syncthreads();
+      const unsigned want = proj_await_helper(a, k, tid);
       const double* const in = a.sB + (size_t)k * kSplitTileDoubles;
       int nth = 0;
       for (int c = 1; c <= hc; ++c) nth += nt - c;
@@ -600,13 +874,7 @@ __device__ __forceinline__ void proj_body(const ProjArgs& a, const int k, const 
       int tti[kTilesPerWave], ttj[kTilesPerWave];
       d4_t acc[kTilesPerWave];
 #pragma unroll
-      for (int m = 0; m < kTilesPerWave; ++m) {
-        const int t = wv + m * NW;
-        int ti = -1, tj = -1;
-        if (t < ntl) { ti = 0; while ((ti + 1) * (ti + 2) / 2 <= t) ++ti; tj = t - ti * (ti + 1) / 2; }
-        tti[m] = ti; ttj[m] = tj;
-        acc[m] = d4_t{0.0, 0.0, 0.0, 0.0};
-      }
+      for (int m = 0; m < kTilesPerWave; ++m) { proj_lower_tile(wv + m * NW, ntl, tti[m], ttj[m]); acc[m] = d4_t{0.0, 0.0, 0.0, 0.0}; }
       for (int l0 = 0; l0 < n; l0 += 16) {
         {
           const int ll = tid >> 6, l = l0 + ll;              // T: one wave per row l, lanes along i
@@ -660,72 +928,7 @@ __device__ __forceinline__ void proj_body(const ProjArgs& a, const int k, const 
   } else if (warm && PK) {
     pk_congruence();
   } else if (warm) {
-    // (blocks too large to keep V in LDS) A <- V' A V as two register-tiled products (4 x 2 tiles, accumulators in VGPRs):
-    //   T = A V   (written over A),   A' = V' T   (written over T)
-    constexpr int kTilesMax = 2048 / NT;               // (128/4) * (128/2) tiles at most
-    const int ti_n = (np + 3) >> 2, tj_n = np >> 1;    // tile grid
-    double acc[kTilesMax][8];
-#pragma unroll
-    for (int pass = 0; pass < 2; ++pass) {
-#pragma unroll
-      for (int m = 0; m < kTilesMax; ++m) {
-        int t = tid + m * NT;
-        int tj = t / ti_n, ti = t - tj * ti_n;         // consecutive threads -> consecutive row tiles
-        double c0 = 0, c1 = 0, c2 = 0, c3 = 0, d0 = 0, d1 = 0, d2 = 0, d3 = 0;
-        if (tj < tj_n) {
-          int i0 = ti * 4, j0 = tj * 2;
-          int i1 = min(i0 + 1, np - 1), i2 = min(i0 + 2, np - 1), i3 = min(i0 + 3, np - 1);
-          if (pass == 0) {
-            // T[i][j] = sum_l A[i][l] V[l][j]
-            const double* v0 = V + (size_t)min(j0, nv - 1) * ldv;
-            const double* v1 = V + (size_t)min(j0 + 1, nv - 1) * ldv;
-            const double *a0 = A + i0 * lda, *a1 = A + i1 * lda, *a2 = A + i2 * lda, *a3 = A + i3 * lda;
-            for (int l = 0; l < nv; ++l) {
-              double x0 = v0[l], x1 = v1[l];
-              double y0 = a0[l], y1 = a1[l], y2 = a2[l], y3 = a3[l];
-              c0 += y0 * x0; c1 += y1 * x0; c2 += y2 * x0; c3 += y3 * x0;
-              d0 += y0 * x1; d1 += y1 * x1; d2 += y2 * x1; d3 += y3 * x1;
-            }
-            if (j0 >= nv) { c0 = a0[j0]; c1 = a1[j0]; c2 = a2[j0]; c3 = a3[j0]; }
-            if (j0 + 1 >= nv) { d0 = a0[j0 + 1]; d1 = a1[j0 + 1]; d2 = a2[j0 + 1]; d3 = a3[j0 + 1]; }
-          } else {
-            // A'[i][j] = sum_l V[l][i] T[l][j]
-            const double *u0 = V + (size_t)min(i0, nv - 1) * ldv, *u1 = V + (size_t)min(i1, nv - 1) * ldv;
-            const double *u2 = V + (size_t)min(i2, nv - 1) * ldv, *u3 = V + (size_t)min(i3, nv - 1) * ldv;
-            for (int l = 0; l < nv; ++l) {
-              double x0 = A[l * lda + j0], x1 = A[l * lda + j0 + 1];
-              double y0 = u0[l], y1 = u1[l], y2 = u2[l], y3 = u3[l];
-              c0 += y0 * x0; c1 += y1 * x0; c2 += y2 * x0; c3 += y3 * x0;
-              d0 += y0 * x1; d1 += y1 * x1; d2 += y2 * x1; d3 += y3 * x1;
-            }
-            if (i0 >= nv) { c0 = A[i0 * lda + j0]; d0 = A[i0 * lda + j0 + 1]; }
-            if (i1 >= nv) { c1 = A[i1 * lda + j0]; d1 = A[i1 * lda + j0 + 1]; }
-            if (i2 >= nv) { c2 = A[i2 * lda + j0]; d2 = A[i2 * lda + j0 + 1]; }
-            if (i3 >= nv) { c3 = A[i3 * lda + j0]; d3 = A[i3 * lda + j0 + 1]; }
-          }
-        }
-        acc[m][0] = c0; acc[m][1] = c1; acc[m][2] = c2; acc[m][3] = c3;
-        acc[m][4] = d0; acc[m][5] = d1; acc[m][6] = d2; acc[m][7] = d3;
-      }
-      __syncthreads();
-#pragma unroll
-      for (int m = 0; m < kTilesMax; ++m) {
-        int t = tid + m * NT;
-        int tj = t / ti_n, ti = t - tj * ti_n;
-        if (tj < tj_n) {
-          int i0 = ti * 4, j0 = tj * 2;
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-            if (i0 + r < np) { A[(i0 + r) * lda + j0] = acc[m][r]; A[(i0 + r) * lda + j0 + 1] = acc[m][4 + r]; }
-        }
-      }
-      __syncthreads();
-    }
-    // exact symmetry into the lower triangle (the two passes round differently)
-    for (int j = tid >> 6; j < np; j += NT >> 6)
-      for (int i = tid & 63; i < np; i += 64)
-        if (i > j) A[i * lda + j] = 0.5 * (A[i * lda + j] + A[j * lda + i]);
-    __syncthreads();
+    proj_congruence_regs<NT>(b);
   }
 
 #ifdef NNSDP_STAMPS
@@ -752,12 +955,6 @@ __device__ __forceinline__ void proj_body(const ProjArgs& a, const int k, const 
   // ceil(half * ceil(nv/32) / VG) for the sizes each variant is launched with (n <= 96 when V is in LDS)
   constexpr int MAXU = PK ? 15 : (NT == 1024) ? (V_LDS ? 5 : 9) : 7;   // V in HBM: blocks up to n = 128 (160 packed: 80 x 5 units over 28 groups)
   constexpr int VG = (NT - kParamLanes) / 32;
-#ifdef NNSDP_STAMPS
-  long long st_acc[4] = {0, 0, 0, 0};
-#define STAMP(i, tprev) { long long tn_ = clock64(); st_acc[i] += tn_ - tprev; tprev = tn_; }
-#else
-#define STAMP(i, tprev)
-#endif
   int sweeps = 0;
   int pofs = 0;   // systolic sweeps: eigen-index j of the result sits at position j + pofs (the padded index travels)
   // ---- refinement stage (ping-pong variant, warm blocks): GEMM-only update of the PERSISTENT eigenbasis.
@@ -784,12 +981,7 @@ __device__ __forceinline__ void proj_body(const ProjArgs& a, const int k, const 
       double* const cs2 = desc + 3 * npg;   // column sums of E~^2 d
       int tti[2], ttj[2];
 #pragma unroll
-      for (int m = 0; m < 2; ++m) {
-        const int t = wv + m * NW;
-        int ti = -1, tj = -1;
-        if (t < ntl) { ti = 0; while ((ti + 1) * (ti + 2) / 2 <= t) ++ti; tj = t - ti * (ti + 1) / 2; }
-        tti[m] = ti; ttj[m] = tj;
-      }
+      for (int m = 0; m < 2; ++m) proj_lower_tile(wv + m * NW, ntl, tti[m], ttj[m]);
       d4_t g[2];
       d4_t bt[2];           // the wave's tiles of B = V'T when the stage takes the congruence's second product itself (stage_b)
       // The Gram product is not taken on every visit: a step with an antisymmetric K leaves (I + K + K^2 / 2)'(I + K + K^2 / 2) =
@@ -1023,12 +1215,7 @@ __device__ __forceinline__ void proj_body(const ProjArgs& a, const int k, const 
       };
       // B = V'AV again from the matrix in HBM (the A buffer held X)
       auto rebuild_B = [&]() {
-        for (int j = wv; j < npg; j += NW)
-          for (int i = lane; i < npg; i += 64) {
-            double v = 0.0;
-            if (i < n && j < n) v = 0.5 * (nuk[(size_t)j * n + i] + nuk[(size_t)i * n + j]);
-            A[i * lda + j] = v;
-          }
+        proj_fill_sym<NT, false>(b);
         __syncthreads();
         congruence(0);
       };
@@ -1106,17 +1293,7 @@ __device__ __forceinline__ void proj_body(const ProjArgs& a, const int k, const 
           // element of the accumulator it would have computed: 64 r + lane of the tile)
           chains(m0); chains(m1);
           RST(1)
-          const unsigned want = a.sseen[k] + 1u;
-          if (tid == 0) {
-            long long spins = 0;
-            while (__hip_atomic_load(a.sack + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < want) {
-              __builtin_amdgcn_s_sleep(2);
-              if (++spins > a.spin_limit) { atomicExch(a.serr, 1); break; }
-            }
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");       // (one invalidate, after the count has arrived - not one per poll)
-          }
-          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-          __syncthreads();
+          const unsigned want = proj_await_helper(a, k, tid);
           const double* const in = a.sB + (size_t)k * kSplitTileDoubles;
 #pragma unroll
           for (int m = 0; m < 2; ++m)
@@ -1179,16 +1356,7 @@ __device__ __forceinline__ void proj_body(const ProjArgs& a, const int k, const 
                   if (!(fabs(b) <= kcap * fabs(gap) && gap != 0.0) && !(b * b < dvec[i] * dvec[j]) && b * b > pm) { pm = b * b; pidx = (i << 8) | j; }
                 }
               }
-#pragma unroll
-          for (int o = 32; o > 0; o >>= 1) {
-            const double om = __shfl_xor(pm, o, 64);
-            const int oi = __shfl_xor(pidx, o, 64);
-            if (om > pm || (om == pm && oi > pidx)) { pm = om; pidx = oi; }
-          }
-          if (lane == 0) { cs1[wv] = pm; cs2[wv] = (double)pidx; }
-          __syncthreads();
-          pm = 0.0; pidx = 0;
-          for (int w_ = 0; w_ < NW; ++w_) { const double om = cs1[w_]; const int oi = (int)cs2[w_]; if (om > pm || (om == pm && oi > pidx)) { pm = om; pidx = oi; } }
+          proj_block_argmax<NW>(pm, pidx, cs1, cs2);
           pm = uniform(pm); pidx = __builtin_amdgcn_readfirstlane(pidx);
           if (!(pm > 0.0) || !(pred0 + sqrt(fmax(fmin(unpp, unnn) + unx - 2.0 * pm, 0.0)) <= accT)) break;     // (uniform)
           const int p_ = pidx >> 8, q_ = pidx & 255;       // p_ > q_
@@ -1269,13 +1437,9 @@ __device__ __forceinline__ void proj_body(const ProjArgs& a, const int k, const 
         outcome = 2;
         if (!(r2 <= 0.01)) {
           // (cannot happen with the guards above; Newton-Schulz only converges from |R| < 1) restart the block cold: V = I, B = sym(nu)
+          proj_fill_sym<NT, false>(b);
           for (int j = wv; j < npg; j += NW)
-            for (int i = lane; i < npg; i += 64) {
-              double v = 0.0;
-              if (i < n && j < n) v = 0.5 * (nuk[(size_t)j * n + i] + nuk[(size_t)i * n + j]);
-              A[i * lda + j] = v;
-              V[i + (size_t)j * ldv] = (i == j) ? 1.0 : 0.0;
-            }
+            for (int i = lane; i < npg; i += 64) V[i + (size_t)j * ldv] = (i == j) ? 1.0 : 0.0;
           __syncthreads();
           r2 = 0.0; measured = true;
         } else if (r2 > a.refine_acc * a.refine_acc * tolv * tolv) {
@@ -1352,12 +1516,7 @@ __device__ __forceinline__ void proj_body(const ProjArgs& a, const int k, const 
       double* const nrm = desc + 3 * npg;        // squared column norms of the new basis
       int tti[kTilesPerWave], ttj[kTilesPerWave];
 #pragma unroll
-      for (int m = 0; m < kTilesPerWave; ++m) {
-        const int t = wv + m * NW;
-        int ti = -1, tj = -1;
-        if (t < ntl) { ti = 0; while ((ti + 1) * (ti + 2) / 2 <= t) ++ti; tj = t - ti * (ti + 1) / 2; }
-        tti[m] = ti; ttj[m] = tj;
-      }
+      for (int m = 0; m < kTilesPerWave; ++m) proj_lower_tile(wv + m * NW, ntl, tti[m], ttj[m]);
       // V <- V M with M (n x n, row-major, identity included) in the first scratch: 16-column chunks of V against 16-row chunks of M,
       // all n^2 output tiles in two halves of the tile columns (four accumulators per wave), the result through the second scratch;
       // the copy back also takes the squared column norms
@@ -1475,12 +1634,7 @@ __device__ __forceinline__ void proj_body(const ProjArgs& a, const int k, const 
               }
           __syncthreads();
           apply_M();
-          for (int j = tid >> 6; j < npg; j += NT >> 6)
-            for (int i = (tid & 63) + j; i < npg; i += 64) {
-              double v = 0.0;
-              if (i < n && j < n) v = 0.5 * (nuk[(size_t)j * n + i] + nuk[(size_t)i * n + j]);
-              A[ixl(i, j)] = v;
-            }
+          proj_fill_sym<NT, true>(b);
           __syncthreads();
           pk_congruence();
           r2 = r2 * r2;         // (the defect is squared by the step, up to a factor 3/8)
@@ -1537,16 +1691,7 @@ __device__ __forceinline__ void proj_body(const ProjArgs& a, const int k, const 
               const double b = A[ixl(i, j)], di = dvec[i], dj = dvec[j], gap = dj - di;
               if (!(fabs(b) <= kcap * fabs(gap) && gap != 0.0) && !(b * b < di * dj) && b * b > pm) { pm = b * b; pidx = (i << 8) | j; }
             }
-#pragma unroll
-          for (int o = 32; o > 0; o >>= 1) {
-            const double om = __shfl_xor(pm, o, 64);
-            const int oi = __shfl_xor(pidx, o, 64);
-            if (om > pm || (om == pm && oi > pidx)) { pm = om; pidx = oi; }
-          }
-          if (lane == 0) { cs1[wv] = pm; cs2[wv] = (double)pidx; }
-          __syncthreads();
-          pm = 0.0; pidx = 0;
-          for (int w_ = 0; w_ < NW; ++w_) { const double om = cs1[w_]; const int oi = (int)cs2[w_]; if (om > pm || (om == pm && oi > pidx)) { pm = om; pidx = oi; } }
+          proj_block_argmax<NW>(pm, pidx, cs1, cs2);
           pm = uniform(pm); pidx = __builtin_amdgcn_readfirstlane(pidx);
           if (!(pm > 0.0) || !(pred0 + sqrt(fmax(fmin(unpp, unnn) + unx - 2.0 * pm, 0.0)) <= accT)) break;     // (uniform)
           const int p_ = pidx >> 8, q_ = pidx & 255;       // p_ > q_
@@ -2321,32 +2466,7 @@ __device__ __forceinline__ void proj_body(const ProjArgs& a, const int k, const 
   if (a.stats && sweeps > 0 && plane >= 0 && plane < half) { atomicAdd(&a.stats[2], nrot); atomicAdd(&a.stats[3], sweeps * M); }
 
   // ---- eigenvalues on the diagonal; the smaller side of the spectrum gives the rank-k update
-  {
-    // selection list in index order, built by two (three: packed variant) waves with ballots (positions 0..127 / 0..191)
-    const int nl = (SYS || PP) ? np : n;   // positions that can hold an eigenvalue (the padded one is exactly 0: never selected)
-    constexpr int kSelThreads = PK ? 192 : 128;
-    int* cnt = reinterpret_cast<int*>(red);
-    const int ln = tid & 63, w2 = tid >> 6;
-    double l = 0.0;
-    if (tid < kSelThreads) {
-      if (tid < nl) l = A[ixl(tid, tid)];
-      const unsigned long long bp = __ballot(l > 0.0), bn = __ballot(l < 0.0);
-      if (ln == 0) { cnt[2 * w2] = __popcll(bp); cnt[2 * w2 + 1] = __popcll(bn); }
-    }
-    if (!PK && tid == 0) { cnt[4] = 0; cnt[5] = 0; }
-    __syncthreads();
-    const int npos = cnt[0] + cnt[2] + cnt[4], nneg = cnt[1] + cnt[3] + cnt[5];
-    const bool up = side_force != 0 ? side_force > 0 : npos <= nneg;
-    if (tid < kSelThreads) {
-      const bool me = up ? (l > 0.0) : (l < 0.0);
-      const unsigned long long mk = __ballot(me);
-      int before = 0;
-      for (int q = 0; q < w2; ++q) before += up ? cnt[2 * q] : cnt[2 * q + 1];
-      const int rank = __popcll(mk & ((1ull << ln) - 1ull)) + before;
-      if (me) sel[rank] = tid;
-    }
-    if (tid == 0) { sel[npg] = up ? npos : nneg; sel[npg + 1] = up ? 1 : 0; }
-  }
+  proj_select_side<PK, SYS || PP>(b, side_force);
   __syncthreads();
   RST(10)
   const int nsel = sel[npg];
@@ -2355,123 +2475,11 @@ __device__ __forceinline__ void proj_body(const ProjArgs& a, const int k, const 
   const double kap = a.kappa ? *a.kappa : 1.0;
   double* wk = a.w + a.coff[k];
   double* nuw = a.nu + a.coff[k];
-  if (V_LDS) {
-    // W = sum_t lam_t v_t v_t' over the selected eigenpairs as MFMA tiles (K = nsel padded to 4); lower
-    // tiles are computed and mirrored; !use_pos: W = sym(nu) - (negative part)
-    constexpr int NW = NT / 64;
-    const int nt = (n + 15) >> 4, ntl = nt * (nt + 1) / 2, ks = (nsel + 3) >> 2;
-    const int lane = tid & 63, wv = tid >> 6;
-    const int lr = lane & 15, lc = lane >> 4;
-    for (int t = wv; t < ntl; t += NW) {
-      int ti = 0;
-      while ((ti + 1) * (ti + 2) / 2 <= t) ++ti;
-      int tj = t - ti * (ti + 1) / 2;
-      d4_t c = {0.0, 0.0, 0.0, 0.0};
-      double sn[4] = {0.0, 0.0, 0.0, 0.0};      // sym(nu) of the tile, requested before the products (L2 latency behind the matrix work)
-      if (!use_pos) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int row = 16 * ti + lc + 4 * r, col = 16 * tj + lr;
-          if (row < n && col < n) sn[r] = 0.5 * (nuk[(size_t)col * n + row] + nuk[(size_t)row * n + col]);
-        }
-      }
-      for (int kk = 0; kk < ks; ++kk) {
-        int tt = 4 * kk + lc;
-        double av = 0.0, bv = 0.0;
-        if (tt < nsel) {
-          int l = sel[tt];
-          av = A[l * lda + l] * V[16 * ti + lr + (size_t)l * ldv];
-          bv = V[16 * tj + lr + (size_t)l * ldv];
-        }
-        c = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, c, 0, 0, 0);
-      }
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        int row = 16 * ti + lc + 4 * r, col = 16 * tj + lr;
-        if (row < n && col < n) {
-          double v = c[r];
-          if (!use_pos) v = sn[r] - v;
-          wk[(size_t)col * n + row] = v;
-          if (ti != tj) wk[(size_t)row * n + col] = v;
-        }
-      }
-    }
-  } else if constexpr (PK) {
-    // packed variant: W = sum_t lam_t v_t v_t' on the matrix cores, the selected eigenvectors staged through LDS 16 at a time
-    // (k-major panel in the space the sweeps' eigenvector panel used; every thread re-reading its 2 nsel operands from L2 - the form
-    // below - was 16 % of a warm launch of the 151-wide blocks).  Lower tiles, four per wave at most (55 tiles at n = 160).
-    constexpr int NW = NT / 64, kPanelLd = 161, kTilesPerWave = 4;
-    double* const Pn = red + 16 + (npg >> 1) + 2;       // 16 x kPanelLd
-    double* const lamc = Pn + 16 * kPanelLd;            // the chunk's 16 eigenvalues (0 past the selection)
-    const int nt = (n + 15) >> 4, ntl = nt * (nt + 1) / 2;
-    const int lane = tid & 63, wv = tid >> 6, lr = lane & 15, lc = lane >> 4;
-    int tti[kTilesPerWave], ttj[kTilesPerWave];
-    d4_t acc[kTilesPerWave];
-#pragma unroll
-    for (int m = 0; m < kTilesPerWave; ++m) {
-      const int t = wv + m * NW;
-      int ti = -1, tj = -1;
-      if (t < ntl) { ti = 0; while ((ti + 1) * (ti + 2) / 2 <= t) ++ti; tj = t - ti * (ti + 1) / 2; }
-      tti[m] = ti; ttj[m] = tj;
-      acc[m] = d4_t{0.0, 0.0, 0.0, 0.0};
-    }
-    __syncthreads();      // (the selection list is complete; the panel space is free)
-    for (int c0 = 0; c0 < nsel; c0 += 16) {
-      {
-        const int kk = tid >> 6, l = c0 + kk < nsel ? sel[c0 + kk] : -1;
-        for (int i = tid & 63; i < 16 * nt; i += 64) Pn[kk * kPanelLd + i] = (l >= 0 && i < n) ? V[i + (size_t)l * ldv] : 0.0;
-        if ((tid & 63) == 0) lamc[kk] = l >= 0 ? A[ixl(l, l)] : 0.0;
-      }
-      __syncthreads();
-#pragma unroll
-      for (int m = 0; m < kTilesPerWave; ++m)
-        if (tti[m] >= 0) {
-#pragma unroll
-          for (int k4 = 0; k4 < 4; ++k4) {
-            const int kx = 4 * k4 + lc;
-            const double av = lamc[kx] * Pn[kx * kPanelLd + 16 * tti[m] + lr], bv = Pn[kx * kPanelLd + 16 * ttj[m] + lr];
-            acc[m] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc[m], 0, 0, 0);
-          }
-        }
-      __syncthreads();
-    }
-#pragma unroll
-    for (int m = 0; m < kTilesPerWave; ++m)
-      if (tti[m] >= 0) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int row = 16 * tti[m] + lc + 4 * r, col = 16 * ttj[m] + lr;
-          if (row < n && col < n) {
-            double v = acc[m][r];
-            if (!use_pos) v = 0.5 * (nuk[(size_t)col * n + row] + nuk[(size_t)row * n + col]) - v;
-            wk[(size_t)col * n + row] = v;
-            if (tti[m] != ttj[m]) wk[(size_t)row * n + col] = v;
-          }
-        }
-      }
-  } else {
-    for (int j = tid >> 6; j < n; j += NT >> 6)
-      for (int i = tid & 63; i < n; i += 64) {
-        double s = 0.0;
-        for (int t = 0; t < nsel; ++t) {
-          int l = sel[t], lv = l - pofs;   // V in HBM is stored without the padded column
-          s += A[ixl(l, l)] * V[i + (size_t)lv * ldv] * V[j + (size_t)lv * ldv];
-        }
-        double nij = nuk[(size_t)j * n + i], nji = nuk[(size_t)i * n + j];
-        if (!use_pos) s = 0.5 * (nij + nji) - s;
-        wk[(size_t)j * n + i] = s;
-      }
-  }
+  if constexpr (V_LDS) proj_reconstruct_mfma<NT>(b, wk, nsel, use_pos);
+  else if constexpr (PK) proj_reconstruct_packed<NT>(b, wk, nsel, use_pos);
+  else proj_reconstruct_scalar<NT>(b, wk, nsel, use_pos, pofs);
   RST(11)
-  if (kap != 1.0) {
-    __syncthreads();
-    for (int idx = tid; idx < n * n; idx += NT) { double wv = wk[idx]; nuw[idx] = wv + kap * (nuw[idx] - wv); }
-  }
-  if (V_LDS) {
-    double* vg = a.Vg + a.coff[k];
-    for (int j = tid >> 6; j < n; j += NT >> 6)
-      for (int i = tid & 63; i < n; i += 64) vg[(size_t)j * n + i] = V[i + (j + pofs) * ldv];
-  }
+  proj_rescale_store<V_LDS, NT>(b, a, k, kap, wk, nuw, pofs);
 #ifdef NNSDP_STAMPS
   if (k == 0 && tid == 0 && a.eig) { long long* dbg = reinterpret_cast<long long*>(a.eig + 4096); dbg[69] = clock64() - dbg[68]; }
   if (PK && k == 0 && tid == 0 && !a.eig) {
@@ -2584,7 +2592,7 @@ inline ProjPlan plan_projection(int nmax, bool warm_refine = false) {
   } else if (nmax > kSmallBlock) {
     if (p.v_lds) p.use<true, 1024>(); else p.use<false, 1024>();
   } else {
-    if (p.v_lds) p.use<true, 256>(); else p.use<false, 256>();
+    p.use<true, 256>();      // (up to kSmallBlock V always fits LDS beside A: 38 KB at 40, so <false, 256> was never chosen)
   }
   return p;
 }

@@ -1,0 +1,49 @@
+"""Every variant of the projection kernel, bit for bit against the digests recorded from the commit in front of the change that made
+proj_body's shared phases functions over a per-block context (tools/proj_bits.py wrote tests/golden/proj_bits_parent.json on that
+build): the change moved code between functions - every floating-point operation kept its order, every barrier its place - so W, the
+eigenvalues, V, the outcome counts and the state words are the same bytes.  Cases: a cold launch per instantiation plan_projection
+reaches under NNSDP_PROJ_ALG unset, 0, 2, 3 and 4 (smallest, largest and an odd size of its range, and a 1 x 1 block); warm launches on
+carried bases and state (two visits; a converged, a 1e-6 and a 1e-4 move) of the packed variant with its stage off, on and checked,
+of the systolic and of the round-robin variant with V in LDS and in HBM.  The ping-pong stage has tests/test_stage_shadow_bits.py."""
+import json
+import os
+import sys
+
+import pytest
+
+import helpers  # noqa: F401
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+import proj_bits  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+with open(proj_bits.GOLDEN) as _f:
+    _GOLDEN = json.load(_f)
+_CASES = proj_bits.cases()
+
+
+def test_every_case_has_a_recorded_digest():
+    assert sorted(c[0] for c in _CASES) == sorted(_GOLDEN)
+    assert len(_CASES) == (7 + 4 + 6 + 6 + 4) + 3 * (4 * 3 + 6)
+
+
+def test_the_warm_cases_reach_the_stage_and_the_sweeps():
+    """(of the record itself) a packed block with the stage on and a converged or slowly moving basis never reaches the sweeps; with
+    the stage off, and in the variants without one, no launch reports an outcome of the stage"""
+    for cid, v in _GOLDEN.items():
+        if cid.startswith("warm-packed") and "-refine0-" not in cid and not cid.endswith("-eta0.0001"):
+            assert all(r["counts"][2] == 0 and sum(r["counts"]) == 1 for r in v), cid
+        if cid.startswith("warm-") and "-refine0-" in cid:
+            assert all(sum(r["counts"]) == 0 for r in v), cid
+
+
+@pytest.mark.parametrize("case", _CASES, ids=[c[0] for c in _CASES])
+def test_proj_bits_match_the_parent(case):
+    want = _GOLDEN[case[0]]           # (a case without a record is an error, never a skip)
+    got = proj_bits.run_case(case)
+    assert len(got) == len(want)
+    for visit, (g, w) in enumerate(zip(got, want)):
+        assert sorted(g) == sorted(w), (case[0], visit)
+        for key in sorted(w):
+            assert g[key] == w[key], (case[0], visit, key)
