@@ -2853,6 +2853,7 @@ __global__ __launch_bounds__(kThreads) void k_finish_g(int NE, const double* __r
 }
 
 // ww = Minv qv  (Minv symmetric, column-major): one wave per output row, coalesced column reads
+static constexpr int kGemvGroup = 8;      // 16-byte pairs of a row a lane has in flight at once (8 x 128 columns per group)
 __device__ __forceinline__ void gemv_sym_body(const int bid, int n, int ldm, const double* __restrict__ Minv, const double* __restrict__ x,
                                                         double* __restrict__ y) {
   int i = (bid * kThreads + threadIdx.x) >> 6;
@@ -2860,14 +2861,39 @@ __device__ __forceinline__ void gemv_sym_body(const int bid, int n, int ldm, con
   if (i >= n) return;
   const double* col = Minv + (size_t)i * ldm;  // ldm even: 16-byte aligned columns
   double s0 = 0.0, s1 = 0.0;
-  int j = lane * 2;
-  for (; j + 1 < n; j += 128) {
-    double2 m = *reinterpret_cast<const double2*>(col + j);
-    double2 xv = *reinterpret_cast<const double2*>(x + j);
-    s0 += m.x * xv.x;
-    s1 += m.y * xv.y;
+  // A lane's sums run over the pairs (j, j + 1), j = 2 lane + 128 k, in the order of k: s0 over the even elements, s1 over the odd
+  // ones, then the last element of an odd n in the lane whose next pair it would have begun.  The pairs are read kGemvGroup at a time
+  // into registers and multiplied in the same order; how many of a group's 16 loads are issued in front of the first product's wait
+  // is the compiler's choice (DESIGN.md section 5 has what it does and what forcing all of them there costs).  The last group reads
+  // pair 0 in place of a pair past the end and leaves its sums alone.
+  const bool rem = (n & 1) && (((n - 1) >> 1) & 63) == lane;
+  const double mr = rem ? col[n - 1] : 0.0, xr = rem ? x[n - 1] : 0.0;
+  const int j0 = lane * 2;
+  int base = 0;
+  for (; base + 128 * kGemvGroup <= n; base += 128 * kGemvGroup) {      // (every pair of the group inside the row, for all lanes)
+    double2 m[kGemvGroup], xv[kGemvGroup];
+#pragma unroll
+    for (int u = 0; u < kGemvGroup; ++u) m[u] = *reinterpret_cast<const double2*>(col + base + j0 + 128 * u);
+#pragma unroll
+    for (int u = 0; u < kGemvGroup; ++u) xv[u] = *reinterpret_cast<const double2*>(x + base + j0 + 128 * u);
+#pragma unroll
+    for (int u = 0; u < kGemvGroup; ++u) { s0 = fma(m[u].x, xv[u].x, s0); s1 = fma(m[u].y, xv[u].y, s1); }
   }
-  if (j < n) s0 += col[j] * x[j];
+  if (base + 1 < n) {      // (uniform: n >= 2 here, so pair 0 exists)
+    double2 m[kGemvGroup], xv[kGemvGroup];
+#pragma unroll
+    for (int u = 0; u < kGemvGroup; ++u) { const int j = base + j0 + 128 * u; m[u] = *reinterpret_cast<const double2*>(col + (j + 1 < n ? j : 0)); }
+#pragma unroll
+    for (int u = 0; u < kGemvGroup; ++u) { const int j = base + j0 + 128 * u; xv[u] = *reinterpret_cast<const double2*>(x + (j + 1 < n ? j : 0)); }
+#pragma unroll
+    for (int u = 0; u < kGemvGroup; ++u) {
+      const bool in = base + j0 + 128 * u + 1 < n;
+      const double t0 = fma(m[u].x, xv[u].x, s0), t1 = fma(m[u].y, xv[u].y, s1);
+      s0 = in ? t0 : s0;
+      s1 = in ? t1 : s1;
+    }
+  }
+  if (rem) s0 = fma(mr, xr, s0);
   double s = wave_sum(s0 + s1);
   if (lane == 0) y[i] = s;
 }
