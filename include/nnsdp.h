@@ -40,7 +40,7 @@
 extern "C" {
 #endif
 
-#define NNSDP_VERSION 210 /* 0.2.1 */
+#define NNSDP_VERSION 220 /* 0.2.2 */
 
 /* query_kind: Methods.SafetyQuery / Methods.ReachQuery (src/Methods/Methods.jl:22-43) */
 enum { NNSDP_QUERY_SAFETY = 0, NNSDP_QUERY_REACH = 1 };
@@ -375,6 +375,41 @@ int nnsdp_make_intervals_batch_lits(int32_t K, const int32_t* xdims, const doubl
                                     double* acymin, double* acymax, double* acxmin, double* acxmax,
                                     double* ymin, double* ymax, int32_t nlit, const double* normals,
                                     double* smin, double* smax, double* uA, double* ub0, double* kernel_ms);
+
+/* Resident CROWN bounder: nnsdp_make_intervals_batch_lits and nnsdp_eval_network for MANY calls on ONE network, as the split driver
+ * (nnsdp_amd/split.py) makes them level after level.  The handle keeps on the device: xdims, the offsets, the network and the literal
+ * head (uploaded once, at creation), and the box, scratch, output and sample buffers, which grow geometrically when a call exceeds
+ * their capacity and never shrink; it owns pinned host staging, one stream and two events.  A bound call is one asynchronous upload
+ * of the boxes, one launch, one asynchronous download and one stream synchronisation.
+ * ReLU and Tanh networks (the one-shot batched entries stay ReLU-only), every width (xdims[0..K]) <= 64, nlit in 0..64.  The ReLU
+ * kernel is the one-shot entry's arithmetic operation for operation: same bits.  The Tanh kernel restates the host routine's
+ * tanh relaxation (csrc/intervals.hpp, tanh_relax) in fp64; the relaxation of a layer is computed once per box, by the pass that
+ * produces the layer's pre-activation bounds (csrc/crown_batch.hpp).  A box's bits depend neither on nbox, nor on its position, nor
+ * on the other literals, nor on what the handle computed before.  Not thread-safe; distinct handles are independent. */
+typedef struct nnsdp_crown nnsdp_crown;
+
+/* K, xdims, M, activ, nlit, normals as in the one-shot _lits entry (normals: ny x nlit column-major; nlit = 0: no literal pass).
+ * -1 with a message for a null / one-layer network, a width outside 1..64 (the message names the width and 64), an unknown
+ * activation, nlit outside 0..64, normals NULL with nlit > 0, or a non-finite normal entry ("literal i"): all before the GPU is
+ * touched. */
+int nnsdp_crown_create(int32_t K, const int32_t* xdims, const double* M, int32_t activ, int32_t nlit, const double* normals,
+                       nnsdp_crown** out);
+
+/* Bounds of nbox boxes; arguments, layouts and refusals of the boxes as in the one-shot _lits entry (HOST pointers, NULL outputs are
+ * skipped, nbox = 0 returns 0; smin / smax / uA / ub0 are left alone by a handle without literals). */
+int nnsdp_crown_bound(nnsdp_crown* h, int32_t nbox, const double* x1min, const double* x1max,
+                      double* acymin, double* acymax, double* acxmin, double* acxmax, double* ymin, double* ymax,
+                      double* smin, double* smax, double* uA, double* ub0, double* kernel_ms);
+
+/* The sampled forward pass on the resident network: the kernel, launch geometry and bits of the one-shot sampled forward entry. */
+int nnsdp_crown_eval(nnsdp_crown* h, int64_t N, const double* X, double* Y, double* kernel_ms);
+
+/* what: 0 device allocations made so far, 1 network uploads so far, 2 box capacity, 3 sample capacity, 4 bound calls,
+ * 5 device bytes held. */
+int nnsdp_crown_info(nnsdp_crown* h, int32_t what, double* out);
+
+/* NULL is a no-op returning 0. */
+int nnsdp_crown_destroy(nnsdp_crown* h);
 
 /* Batched projection onto the PSD cone, the hot kernel (replaces the cone handling inside MOSEK;
  * reference of the arithmetic: LinearAlgebra.eigen on Symmetric).  mats: `batch` symmetric

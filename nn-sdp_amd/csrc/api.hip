@@ -2427,6 +2427,63 @@ struct nnsdp_batch {
   }
 };
 
+// ---------------------------------------------------------------------------------------------
+// Resident CROWN bounder: the network, the literal head, the box / scratch / output buffers, pinned staging, one stream and two
+// events stay alive across calls, so a level of a split tree pays one upload of its boxes, one launch, one download and one stream
+// synchronisation (the one-shot entries pay the whole set-up per call).  Not thread-safe; distinct handles are independent.
+// ---------------------------------------------------------------------------------------------
+struct nnsdp_crown {
+  int K = 0, activ = 0, nlit = 0, acdim = 0, n0 = 0, ny = 0, wp = 0;
+  std::vector<long long> moff;
+  DBuf<int> dxd, dao;
+  DBuf<long long> dmo;
+  DBuf<double> dM;                       // the network, then the literal head
+  DBuf<double> din, dscr, dout, dX, dY;   // boxes (lo, then hi), per-box scratch, outputs; samples in / out
+  double *hin = nullptr, *hout = nullptr, *hX = nullptr, *hY = nullptr;      // pinned staging of the four transfers
+  size_t box_cap = 0, sample_cap = 0;
+  hipStream_t st = nullptr;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  long long n_alloc = 0, n_upload = 0, n_bound = 0;
+
+  size_t scr_per_box() const { return (size_t)(activ == NNSDP_ACTIV_TANH ? 6 : 2) * acdim; }
+  size_t out_per_box() const { return 4 * (size_t)acdim + 2 * (size_t)ny + 3 * (size_t)nlit + (size_t)nlit * n0; }
+  size_t lds_bytes() const { return activ == NNSDP_ACTIV_TANH ? kCbLdsBytesTanh : kCbLdsBytes; }
+  const void* kernel() const {
+    return activ == NNSDP_ACTIV_TANH ? reinterpret_cast<const void*>(&k_crown_resident<kCbTanh>)
+                                     : reinterpret_cast<const void*>(&k_crown_resident<kCbRelu>);
+  }
+  void dalloc(DBuf<double>& b, size_t count) { b.alloc(count); if (count) ++n_alloc; }
+  static void pinned(double*& h, size_t count) {
+    if (h) { HIPCHK(hipHostFree(h)); h = nullptr; }
+    if (count) HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&h), count * sizeof(double), hipHostMallocDefault));
+  }
+  size_t device_bytes() const {
+    return dxd.bytes() + dao.bytes() + dmo.bytes() + dM.bytes() + din.bytes() + dscr.bytes() + dout.bytes() + dX.bytes() + dY.bytes();
+  }
+  // the capacity grows geometrically and never shrinks
+  void reserve_boxes(size_t nbox) {
+    if (nbox <= box_cap) return;
+    const size_t cap = std::max(nbox, 2 * box_cap);
+    dalloc(din, 2 * cap * n0); dalloc(dscr, cap * scr_per_box()); dalloc(dout, cap * out_per_box());
+    pinned(hin, 2 * cap * n0); pinned(hout, cap * out_per_box());
+    box_cap = cap;
+  }
+  void reserve_samples(size_t N) {
+    if (N <= sample_cap) return;
+    const size_t cap = std::max(N, 2 * sample_cap);
+    dalloc(dX, cap * n0); dalloc(dY, cap * ny);
+    pinned(hX, cap * n0); pinned(hY, cap * ny);
+    sample_cap = cap;
+  }
+  ~nnsdp_crown() {
+    if (st) (void)hipStreamSynchronize(st);
+    for (double* h : {hin, hout, hX, hY}) if (h) (void)hipHostFree(h);
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    if (st) (void)hipStreamDestroy(st);
+  }
+};
+
 #define API_BEGIN try {
 #define API_END                                                                    \
   }                                                                                \
@@ -3016,6 +3073,143 @@ int nnsdp_make_intervals_batch_lits(int32_t K, const int32_t* xdims, const doubl
   for (int o = 0; o < 4; ++o)
     if (lhost[o] && (o < 3 ? nl_all : nA_all))
       HIPCHK(hipMemcpy(lhost[o], ldev[o], (o < 3 ? nl_all : nA_all) * sizeof(double), hipMemcpyDeviceToHost));
+  API_END
+}
+
+int nnsdp_crown_create(int32_t K, const int32_t* xdims, const double* M, int32_t activ, int32_t nlit, const double* normals,
+                       nnsdp_crown** out) {
+  API_BEGIN
+  if (!out) throw std::invalid_argument("null argument");
+  *out = nullptr;
+  if (K < 2 || !xdims || !M) throw std::invalid_argument("null / empty network (K >= 2 layers are needed)");
+  if (activ != NNSDP_ACTIV_RELU && activ != NNSDP_ACTIV_TANH) throw std::invalid_argument("unknown activation");
+  std::vector<int> xd(xdims, xdims + K + 1), acoff(K, 0);
+  std::vector<long long> moff(K + 1, 0);
+  int wp = 0;
+  for (int k = 0; k <= K; ++k) {
+    if (xd[k] < 1) throw std::invalid_argument("layer widths must be >= 1");
+    if (xd[k] > nnsdp::kCbW)
+      throw std::invalid_argument("layer width " + std::to_string(xd[k]) + " is above 64, the widest layer of the batched intervals");
+  }
+  for (int k = 0; k < K; ++k) {
+    moff[k + 1] = moff[k] + (long long)xd[k + 1] * (xd[k] + 1);
+    if (k > 0) acoff[k] = acoff[k - 1] + xd[k];
+    wp = std::max(wp, (xd[k] + 1 + 3) & ~3);
+  }
+  check_literals(xd[K], nlit, normals);
+  require_gpu();
+  std::unique_ptr<nnsdp_crown> h(new nnsdp_crown);
+  h->K = K; h->activ = activ; h->nlit = nlit; h->acdim = acoff[K - 1]; h->n0 = xd[0]; h->ny = xd[K]; h->wp = wp; h->moff = moff;
+  h->dxd.upload(xd); h->dao.upload(acoff); h->dmo.upload(moff);
+  const size_t hlen = nlit > 0 ? (size_t)nlit * (xd[K - 1] + 1) : 0;      // the literal head H sits behind M
+  h->dM.alloc(moff[K] + hlen);
+  h->n_alloc += 4;
+  HIPCHK(hipMemcpy(h->dM.p, M, moff[K] * sizeof(double), hipMemcpyHostToDevice));
+  ++h->n_upload;
+  if (nlit > 0) {
+    const nnsdp::LitHead head = nnsdp::make_lit_head(K, xdims, M, nlit, normals);
+    HIPCHK(hipMemcpy(h->dM.p + moff[K], head.H.data(), hlen * sizeof(double), hipMemcpyHostToDevice));
+  }
+  // (k_forward_mfma needs no attribute here: widths <= 64 keep its LDS at 2 * 68 * 16 doubles)
+  HIPCHK(hipFuncSetAttribute(h->kernel(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes()));
+  HIPCHK(hipStreamCreate(&h->st));
+  HIPCHK(hipEventCreate(&h->e0)); HIPCHK(hipEventCreate(&h->e1));
+  *out = h.release();
+  API_END
+}
+
+int nnsdp_crown_bound(nnsdp_crown* h, int32_t nbox, const double* x1min, const double* x1max,
+                      double* acymin, double* acymax, double* acxmin, double* acxmax, double* ymin, double* ymax,
+                      double* smin, double* smax, double* uA, double* ub0, double* kernel_ms) {
+  API_BEGIN
+  if (!h) throw std::invalid_argument("null handle");
+  if (nbox < 0) throw std::invalid_argument("nbox must be >= 0");
+  if (nbox == 0) return 0;
+  if (!x1min || !x1max) throw std::invalid_argument("null argument");
+  const int n0 = h->n0, acdim = h->acdim, ny = h->ny, nlit = h->nlit;
+  for (long long b = 0; b < nbox; ++b)
+    for (int i = 0; i < n0; ++i)
+      if (!std::isfinite(x1min[b * n0 + i]) || !std::isfinite(x1max[b * n0 + i]) || !(x1min[b * n0 + i] <= x1max[b * n0 + i]))
+        throw std::invalid_argument("box " + std::to_string(b) + ": x1min must be <= x1max and both finite (no NaN, no infinity)");
+  const size_t nb = (size_t)nbox, nin = nb * n0, na = nb * acdim, ny_all = nb * ny, nl_all = nb * (size_t)nlit, nA_all = nl_all * n0;
+  const size_t nout = nb * h->out_per_box();
+  h->reserve_boxes(nb);
+  std::copy(x1min, x1min + nin, h->hin);
+  std::copy(x1max, x1max + nin, h->hin + nin);
+  HIPCHK(hipMemcpyAsync(h->din.p, h->hin, 2 * nin * sizeof(double), hipMemcpyHostToDevice, h->st));
+  // the layouts of nnsdp_make_intervals_batch_lits, packed for nbox boxes so that one copy brings everything back
+  nnsdp::CrownArgs a;
+  a.K = h->K; a.xdims = h->dxd.p; a.moff = h->dmo.p; a.acoff = h->dao.p; a.M = h->dM.p; a.lo = h->din.p; a.hi = h->din.p + nin;
+  a.scratch = h->dscr.p;
+  a.acymin = h->dout.p; a.acymax = a.acymin + na; a.acxmin = a.acymin + 2 * na; a.acxmax = a.acymin + 3 * na;
+  a.ymin = a.acymin + 4 * na; a.ymax = a.ymin + ny_all; a.acdim = acdim;
+  a.nlit = nlit; a.H = h->dM.p + h->moff[h->K];
+  a.smin = a.ymax + ny_all; a.smax = a.smin + nl_all; a.ub0 = a.smax + nl_all; a.uA = a.ub0 + nl_all;
+  HIPCHK(hipEventRecord(h->e0, h->st));
+  if (h->activ == NNSDP_ACTIV_TANH)
+    hipLaunchKernelGGL(nnsdp::k_crown_resident<nnsdp::kCbTanh>, dim3((unsigned)nbox), dim3(256), nnsdp::kCbLdsBytesTanh, h->st, a);
+  else
+    hipLaunchKernelGGL(nnsdp::k_crown_resident<nnsdp::kCbRelu>, dim3((unsigned)nbox), dim3(256), nnsdp::kCbLdsBytes, h->st, a);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(h->e1, h->st));
+  HIPCHK(hipMemcpyAsync(h->hout, h->dout.p, nout * sizeof(double), hipMemcpyDeviceToHost, h->st));
+  HIPCHK(hipStreamSynchronize(h->st));
+  ++h->n_bound;
+  float ms = 0;
+  HIPCHK(hipEventElapsedTime(&ms, h->e0, h->e1));
+  if (kernel_ms) *kernel_ms = ms;
+  double* host[10] = {acymin, acymax, acxmin, acxmax, ymin, ymax, smin, smax, ub0, uA};
+  const size_t len[10] = {na, na, na, na, ny_all, ny_all, nl_all, nl_all, nl_all, nA_all};
+  const double* src = h->hout;
+  for (int o = 0; o < 10; src += len[o], ++o)
+    if (host[o]) std::copy(src, src + len[o], host[o]);
+  API_END
+}
+
+int nnsdp_crown_eval(nnsdp_crown* h, int64_t N, const double* X, double* Y, double* kernel_ms) {
+  API_BEGIN
+  if (!h) throw std::invalid_argument("null handle");
+  if (N < 0) throw std::invalid_argument("N must be >= 0");
+  if (N == 0) return 0;
+  if (!X || !Y) throw std::invalid_argument("null argument");
+  if ((N + 15) / 16 > 0x7fffffffLL) throw std::invalid_argument("too many samples for one launch");
+  const size_t lds = 2 * (size_t)h->wp * 16 * sizeof(double), nx = (size_t)h->n0 * N, nyN = (size_t)h->ny * N;
+  h->reserve_samples((size_t)N);
+  std::copy(X, X + nx, h->hX);
+  HIPCHK(hipMemcpyAsync(h->dX.p, h->hX, nx * sizeof(double), hipMemcpyHostToDevice, h->st));
+  nnsdp::FwdArgs a;
+  a.K = h->K; a.xdims = h->dxd.p; a.moff = h->dmo.p; a.M = h->dM.p; a.X = h->dX.p; a.Y = h->dY.p; a.N = N; a.activ = h->activ; a.wp = h->wp;
+  HIPCHK(hipEventRecord(h->e0, h->st));
+  hipLaunchKernelGGL(nnsdp::k_forward_mfma, dim3((unsigned)((N + 15) / 16)), dim3(64), lds, h->st, a);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(h->e1, h->st));
+  HIPCHK(hipMemcpyAsync(h->hY, h->dY.p, nyN * sizeof(double), hipMemcpyDeviceToHost, h->st));
+  HIPCHK(hipStreamSynchronize(h->st));
+  float ms = 0;
+  HIPCHK(hipEventElapsedTime(&ms, h->e0, h->e1));
+  if (kernel_ms) *kernel_ms = ms;
+  std::copy(h->hY, h->hY + nyN, Y);
+  API_END
+}
+
+int nnsdp_crown_info(nnsdp_crown* h, int32_t what, double* out) {
+  API_BEGIN
+  if (!h || !out) throw std::invalid_argument("null argument");
+  switch (what) {
+    case 0: *out = (double)h->n_alloc; break;
+    case 1: *out = (double)h->n_upload; break;
+    case 2: *out = (double)h->box_cap; break;
+    case 3: *out = (double)h->sample_cap; break;
+    case 4: *out = (double)h->n_bound; break;
+    case 5: *out = (double)h->device_bytes(); break;
+    default: throw std::invalid_argument("nnsdp_crown_info: what must be in 0..5");
+  }
+  API_END
+}
+
+int nnsdp_crown_destroy(nnsdp_crown* h) {
+  API_BEGIN
+  delete h;
   API_END
 }
 

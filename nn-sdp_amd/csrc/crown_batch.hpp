@@ -19,6 +19,15 @@
 // row pass and the same MFMA product with nout = nlit; its results are raw (no post-fix), and the upper bound's linear form
 // uA x + ub0 is written out beside them (smax = uA c + |uA| r + ub0).  Every output element of the product is its own dot product
 // and the row passes are per row, so a literal's bits do not depend on the other literals of the call.
+//
+// Resident kernel (k_crown_resident<ACT>, launched by the nnsdp_crown handle of api.hip on buffers the handle keeps): the same passes
+// as a template on the activation.  ACT = kCbRelu is the arithmetic above, operation for operation.  ACT = kCbTanh restates
+// tanh_relax / crown_backward(..., tanh_act = true) of intervals.hpp in fp64: the relaxation  lw x + lb <= tanh(x) <= uw x + ub  of
+// a layer is computed ONCE, by the pre-activation pass that produces the layer's bounds (threads tid < nout, right after l, u go to
+// the scratch), and its four numbers are stored beside the bounds - the Tanh scratch is 6 acdim doubles per box: l, u, lw, lb, uw, ub.
+// Every later pass reads them (the tangent-point bisection is a chain of ~200 dependent tanh / cosh evaluations; 2K - 1 passes visit
+// every layer below them).  The row pass gains the lower relaxation's bias, one more 64-double vector: 70 144 B of LDS
+// (kCbLdsBytesTanh), still two workgroups per CU.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -32,7 +41,7 @@ struct CrownArgs {
   const double* M;
   const double* lo;         // xdims[0] x nbox, column-major
   const double* hi;
-  double* scratch;          // 2 acdim per box: CROWN pre-activation bounds (lower, then upper)
+  double* scratch;          // 2 acdim per box: CROWN pre-activation bounds (lower, then upper); Tanh: 6 acdim, + lw, lb, uw, ub
   double *acymin, *acymax, *acxmin, *acxmax;   // acdim x nbox
   double *ymin, *ymax;      // xdims[K] x nbox
   int acdim;
@@ -47,15 +56,68 @@ struct CrownArgs {
 static constexpr int kCbW = 64;        // widest layer
 static constexpr int kCbChunk = 8;     // k-steps whose weight operands are in flight together
 static constexpr size_t kCbLdsBytes = (2 * kCbW * kCbW + 8 * kCbW) * sizeof(double);
+static constexpr size_t kCbLdsBytesTanh = kCbLdsBytes + kCbW * sizeof(double);      // + the lower relaxation's bias
+static constexpr int kCbRelu = 0, kCbTanh = 1;      // the values of NNSDP_ACTIV_RELU / NNSDP_ACTIV_TANH
 
 __device__ __forceinline__ int cb_idx(int t, int i) { return t * kCbW + (i ^ ((t & 1) << 4)); }
+
+// ---- tanh relaxation in fp64: tanh_relax of intervals.hpp line by line, with the host's constants (clamps at +-500, derivative
+// mask at |x| < 25, the 1e-6 width switch, the 0.01 grid of the tangent-point look-up, the doubling search then 100 halvings)
+__device__ inline double cb_dtanh(double x) {
+  if (!(fabs(x) < 25.0)) return 0.0;
+  const double c = cosh(x);
+  return 1.0 / (c * c);
+}
+__device__ inline double cb_tanh_d_lower(double upper) {
+  const long iu = (long)(upper / 0.01), idx = (iu > 0 ? iu : 0) + 1;
+  const double U = 0.01 * (double)idx, fU = tanh(U);
+  auto ok = [&](double d) { return cb_dtanh(d) * (U - d) + tanh(d) <= fU; };
+  double l = -1.0, r = 0.0;
+  for (int it = 0; it < 64 && !ok(l); ++it) l *= 2.0;
+  for (int it = 0; it < 100; ++it) { const double m = (l + r) / 2.0; if (ok(m)) l = m; else r = m; }
+  return l;
+}
+__device__ inline double cb_tanh_d_upper(double lower) {
+  const long il = (long)(lower / -0.01), idx = (il > 0 ? il : 0) + 1;
+  const double Lw = -0.01 * (double)idx, fL = tanh(Lw);
+  auto ok = [&](double d) { return cb_dtanh(d) * (Lw - d) + tanh(d) >= fL; };
+  double l = 0.0, r = 1.0;
+  for (int it = 0; it < 64 && !ok(r); ++it) r *= 2.0;
+  for (int it = 0; it < 100; ++it) { const double m = (l + r) / 2.0; if (ok(m)) r = m; else l = m; }
+  return r;
+}
+// lw x + lb <= tanh(x) <= uw x + ub on [l, u]; only a neuron whose mask_both = 1 - pos - neg is not zero (l < 0 < u, and the
+// library's l = u = 0 with both masks) enters the bisections
+__device__ inline void cb_tanh_relax(double l, double u, double& lw, double& lb, double& uw, double& ub) {
+  const double lower = l > -500.0 ? l : -500.0, upper = u < 500.0 ? u : 500.0;
+  const double yl = tanh(lower), yu = tanh(upper);
+  const double wd = upper - lower;
+  const double kd = wd < 1e-6 ? cb_dtanh(upper) : (yu - yl) / (wd > 1e-6 ? wd : 1e-6);
+  const bool pos = l >= 0.0, neg = u <= 0.0;
+  const double m = (lower + upper) / 2.0, ym = tanh(m), km = cb_dtanh(m);
+  lw = lb = uw = ub = 0.0;
+  auto line = [](double k, double x0, double y0, double& w, double& b) { w += k; b += -x0 * k + y0; };
+  const double fboth = 1.0 - (pos ? 1.0 : 0.0) - (neg ? 1.0 : 0.0);
+  if (neg) { line(kd, lower, yl, uw, ub); line(km, m, ym, lw, lb); }
+  if (pos) { line(kd, lower, yl, lw, lb); line(km, m, ym, uw, ub); }
+  if (fboth != 0.0) {
+    const double dl = cb_tanh_d_lower(upper), du = cb_tanh_d_upper(lower);
+    double w = 0.0, b = 0.0;
+    if (kd < cb_dtanh(lower)) line(kd, lower, yl, w, b); else line(cb_dtanh(dl), dl, tanh(dl), w, b);
+    lw += fboth * w; lb += fboth * b;
+    w = b = 0.0;
+    if (kd < cb_dtanh(upper)) line(kd, lower, yl, w, b); else line(cb_dtanh(du), du, tanh(du), w, b);
+    uw += fboth * w; ub += fboth * b;
+  }
+}
 
 // One backward pass for box `box`.  head_identity == 0: bounds of W_{k-1} relu(... ) + b_{k-1}, i.e. the pre-activation of hidden
 // layer k (k < K, raw, to the scratch) or the network output (k == K, post-fixed, to ymin / ymax).  head_identity == 1: the
 // post-activation of hidden layer k through an identity head (post-fixed, to acymin / acymax).
 // LIT: the literal pass (k == K, head_identity == 0): the head is a.H instead of M_{K-1}, nout = nlit, the results go raw to smin /
 // smax with the upper bound's coefficients and constant to uA / ub0.
-template <bool LIT>
+// ACT: the activation (kCbRelu / kCbTanh); the ReLU instance is what this function was before it had the parameter.
+template <bool LIT, int ACT = kCbRelu>
 __device__ void crown_pass(const CrownArgs& a, double* lds, long long box, int k, int head_identity) {
   double* A[2] = {lds, lds + kCbW * kCbW};
   double* v_du = lds + 2 * kCbW * kCbW;
@@ -65,6 +127,8 @@ __device__ void crown_pass(const CrownArgs& a, double* lds, long long box, int k
   double* v_c = v_bj + kCbW;      // box centre
   double* v_r = v_c + kCbW;       // box radius
   double* v_res = v_r + kCbW;     // 2 x 64: a pass's lower / upper results, for the post-fix
+  double* v_bl = v_res + 2 * kCbW;   // Tanh only (kCbLdsBytesTanh): the lower relaxation's bias
+  constexpr int kScr = ACT == kCbTanh ? 6 : 2;      // doubles of scratch per hidden neuron
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, lr = lane & 15, lc = lane >> 4;
   const int mat = tid >> 6, row = tid & 63;      // the (matrix, row) a thread owns in the row passes (threads 0..127)
   const int nout = LIT ? a.nlit : a.xdims[k];
@@ -90,7 +154,16 @@ __device__ void crown_pass(const CrownArgs& a, double* lds, long long box, int k
   for (int j = jtop; j >= 0; --j) {
     const int in = a.xdims[j];
     const double* Mj = a.M + a.moff[j];       // d x (in + 1), column-major
-    if (tid < d) {
+    if (ACT == kCbTanh) {
+      if (tid < d) {
+        const double* pre = a.scratch + (size_t)box * kScr * a.acdim + a.acoff[j] + tid;
+        v_dl[tid] = pre[2 * (size_t)a.acdim];
+        v_bl[tid] = pre[3 * (size_t)a.acdim];
+        v_du[tid] = pre[4 * (size_t)a.acdim];
+        v_bu[tid] = pre[5 * (size_t)a.acdim];
+        v_bj[tid] = Mj[(size_t)in * d + tid];
+      }
+    } else if (tid < d) {
       const double* pre = a.scratch + (size_t)box * 2 * a.acdim + a.acoff[j];
       const double l = pre[tid], u = pre[a.acdim + tid];
       const double lrx = l < 0.0 ? l : 0.0;
@@ -110,7 +183,8 @@ __device__ void crown_pass(const CrownArgs& a, double* lds, long long box, int k
         const double x = Am[cb_idx(t, row)];
         const double xp = x > 0.0 ? x : 0.0, xn = x < 0.0 ? x : 0.0;
         const double du = v_du[t], dl = v_dl[t];
-        s += (mat ? xp : xn) * v_bu[t];
+        if (ACT == kCbTanh) s += mat ? xp * v_bu[t] + xn * v_bl[t] : xn * v_bu[t] + xp * v_bl[t];
+        else s += (mat ? xp : xn) * v_bu[t];
         const double y = mat ? xp * du + xn * dl : xp * dl + xn * du;
         Am[cb_idx(t, row)] = y;
         tl += y * v_bj[t];
@@ -199,9 +273,17 @@ __device__ void crown_pass(const CrownArgs& a, double* lds, long long box, int k
   } else if (tid < nout) {
     const double l = v_res[tid], u = v_res[kCbW + tid];
     if (!head_identity && k < a.K) {
-      double* pre = a.scratch + (size_t)box * 2 * a.acdim + a.acoff[k - 1];
+      double* pre = a.scratch + (size_t)box * kScr * a.acdim + a.acoff[k - 1];
       pre[tid] = l;
       pre[a.acdim + tid] = u;
+      if (ACT == kCbTanh) {      // the layer's relaxation, once: every later pass reads it
+        double lw, lb, uw, ub;
+        cb_tanh_relax(l, u, lw, lb, uw, ub);
+        pre[2 * (size_t)a.acdim + tid] = lw;
+        pre[3 * (size_t)a.acdim + tid] = lb;
+        pre[4 * (size_t)a.acdim + tid] = uw;
+        pre[5 * (size_t)a.acdim + tid] = ub;
+      }
     } else {
       const double fl = l < u ? l : u, fu = fl > u ? fl : u;     // lb = min(lb, ub), ub = max(lb, ub)
       if (head_identity) {
@@ -219,15 +301,8 @@ __device__ void crown_pass(const CrownArgs& a, double* lds, long long box, int k
   __syncthreads();
 }
 
-__global__ __launch_bounds__(256) void k_crown_batch(CrownArgs a) {
-  extern __shared__ double cb_lds[];
-  const long long box = blockIdx.x;
-  for (int k = 1; k <= a.K; ++k) {
-    crown_pass<false>(a, cb_lds, box, k, 0);
-    if (k < a.K) crown_pass<false>(a, cb_lds, box, k, 1);
-  }
-  if (a.nlit > 0) crown_pass<true>(a, cb_lds, box, a.K, 0);
-  // one interval step per layer for the pre-activations, from the post-fixed bounds of the layer below
+// one interval step per layer for the pre-activations, from the post-fixed bounds of the layer below
+__device__ __forceinline__ void crown_interval_step(const CrownArgs& a, long long box) {
   const int n0 = a.xdims[0];
   for (int idx = threadIdx.x; idx < a.acdim; idx += 256) {
     int k = 0;
@@ -245,6 +320,31 @@ __global__ __launch_bounds__(256) void k_crown_batch(CrownArgs a) {
     a.acxmin[(size_t)box * a.acdim + idx] = sl;
     a.acxmax[(size_t)box * a.acdim + idx] = su;
   }
+}
+
+__global__ __launch_bounds__(256) void k_crown_batch(CrownArgs a) {
+  extern __shared__ double cb_lds[];
+  const long long box = blockIdx.x;
+  for (int k = 1; k <= a.K; ++k) {
+    crown_pass<false>(a, cb_lds, box, k, 0);
+    if (k < a.K) crown_pass<false>(a, cb_lds, box, k, 1);
+  }
+  if (a.nlit > 0) crown_pass<true>(a, cb_lds, box, a.K, 0);
+  crown_interval_step(a, box);
+}
+
+// The kernel of the resident bounder (nnsdp_crown): every buffer of `a` belongs to the handle; LDS kCbLdsBytes (ReLU) /
+// kCbLdsBytesTanh (Tanh).
+template <int ACT>
+__global__ __launch_bounds__(256) void k_crown_resident(CrownArgs a) {
+  extern __shared__ double cb_lds[];
+  const long long box = blockIdx.x;
+  for (int k = 1; k <= a.K; ++k) {
+    crown_pass<false, ACT>(a, cb_lds, box, k, 0);
+    if (k < a.K) crown_pass<false, ACT>(a, cb_lds, box, k, 1);
+  }
+  if (a.nlit > 0) crown_pass<true, ACT>(a, cb_lds, box, a.K, 0);
+  crown_interval_step(a, box);
 }
 
 }  // namespace nnsdp

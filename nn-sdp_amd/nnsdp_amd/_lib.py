@@ -100,6 +100,11 @@ SYMBOLS = [
      + [C.c_int32, c_double_p] + [c_double_p] * 5),
     ("nnsdp_make_intervals_lits", C.c_int, [C.c_int32, c_int32_p, c_double_p, C.c_int32, c_double_p, c_double_p] + [c_double_p] * 8
      + [C.c_int32, c_double_p] + [c_double_p] * 4),
+    ("nnsdp_crown_create", C.c_int, [C.c_int32, c_int32_p, c_double_p, C.c_int32, C.c_int32, c_double_p, C.POINTER(C.c_void_p)]),
+    ("nnsdp_crown_bound", C.c_int, [C.c_void_p, C.c_int32, c_double_p, c_double_p] + [c_double_p] * 11),
+    ("nnsdp_crown_eval", C.c_int, [C.c_void_p, C.c_int64, c_double_p, c_double_p, c_double_p]),
+    ("nnsdp_crown_info", C.c_int, [C.c_void_p, C.c_int32, c_double_p]),
+    ("nnsdp_crown_destroy", C.c_int, [C.c_void_p]),
     ("nnsdp_project_psd_batched", C.c_int, [C.c_int32, c_int32_p, c_double_p, c_double_p, c_double_p, c_double_p]),
     ("nnsdp_project_psd_warm", C.c_int, [C.c_int32, c_int32_p, c_double_p, c_double_p, C.c_double, C.c_int32, c_double_p, c_int32_p, c_double_p]),
     ("nnsdp_project_psd_warm_state", C.c_int, [C.c_int32, c_int32_p, c_double_p, c_double_p, C.c_double, C.c_int32, c_double_p, c_int32_p, c_double_p, c_int32_p]),

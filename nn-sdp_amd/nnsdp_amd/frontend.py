@@ -220,8 +220,9 @@ def makeIntervalsBatch(net: M.FeedFwdNet, lo, hi, backend: str = "host", workers
     backend="gpu":  nnsdp_make_intervals_batch (csrc/crown_batch.hpp), one launch, fp64; ReLU networks with every width <= 64,
                     anything else raises (no fall-back to the host).
     backend="host": nnsdp_make_intervals_activ (csrc/intervals.hpp, float32 arithmetic by design) once per box on a thread pool
-                    of at most 16 workers (ctypes releases the GIL); the only route for Tanh networks and wider layers, and the
-                    default until the kernel has been timed against it (tools/split_timing.py)."""
+                    of at most 16 workers (ctypes releases the GIL); the only one-shot route for Tanh networks (CrownBounder below
+                    bounds them on the GPU) and the only route for wider layers, and the default until the kernel has been timed
+                    against it (tools/split_timing.py)."""
     lib = _lib.load()
     xd, Mp = _net_arrays(net)
     lo = np.asarray(lo, dtype=np.float64)
@@ -299,6 +300,97 @@ def evalFeedFwdNetBatch(net: M.FeedFwdNet, X, return_ms: bool = False):
     _lib.check(lib.nnsdp_eval_network(net.K, xd.ctypes.data_as(_lib.c_int32_p), Mp.ctypes.data_as(dp), M._activ_code(net.activ), N,
                                       Xc.ctypes.data_as(dp), Y.ctypes.data_as(dp), C.byref(ms)))
     return (Y.T, ms.value) if return_ms else Y.T
+
+
+class CrownBounder:
+    """makeIntervalsBatch(backend="gpu") and evalFeedFwdNetBatch for many calls on one network (the nnsdp_crown handle of include/nnsdp.h):
+    the network, the literal head of `normals` (nlit x xdims[K], nlit <= 64) and every device buffer stay on the GPU until close().
+    ReLU and Tanh networks with every width <= 64; anything else raises (no fall-back to the host).  The ReLU results have the bits of
+    makeIntervalsBatch(backend="gpu"); the Tanh kernel exists only here.  A context manager; not thread-safe."""
+
+    _INFO = ("device_allocations", "network_uploads", "box_capacity", "sample_capacity", "bound_calls", "device_bytes")
+
+    def __init__(self, net: M.FeedFwdNet, normals=None):
+        self._h = None
+        self._lib = _lib.load()
+        self.net = net
+        xd, Mp = _net_arrays(net)
+        self._n0, self._acdim, self._ny = int(xd[0]), int(xd[1:-1].sum()), int(xd[-1])
+        self._nlit, nrp = None, None
+        if normals is not None:
+            nrm = np.ascontiguousarray(normals, dtype=np.float64)               # nlit x ny row-major = ny x nlit column-major
+            if nrm.ndim != 2 or nrm.shape[1] != self._ny:
+                raise ValueError("normals must be nlit x xdims[K]")
+            self._nlit, nrp = nrm.shape[0], nrm.ctypes.data_as(_lib.c_double_p)
+        h = C.c_void_p()
+        _lib.check(self._lib.nnsdp_crown_create(net.K, xd.ctypes.data_as(_lib.c_int32_p), Mp.ctypes.data_as(_lib.c_double_p),
+                                                M._activ_code(net.activ), self._nlit or 0, nrp, C.byref(h)))
+        self._h = h
+
+    def _handle(self):
+        if self._h is None:
+            raise ValueError("the CrownBounder is closed")
+        return self._h
+
+    def bound(self, lo, hi, return_ms: bool = False):
+        """what makeIntervalsBatch(net, lo, hi, backend="gpu"[, normals=...]) returns: the six arrays, then a LiteralBounds when the
+        bounder has normals, then the kernel's event time with return_ms"""
+        h = self._handle()
+        lo = np.asarray(lo, dtype=np.float64)
+        hi = np.asarray(hi, dtype=np.float64)
+        if lo.ndim != 2 or lo.shape[0] != self._n0 or hi.shape != lo.shape:
+            raise ValueError("lo / hi must be xdims[0] x nbox")
+        nbox, dp = lo.shape[1], _lib.c_double_p
+        loc, hic = np.ascontiguousarray(lo.T), np.ascontiguousarray(hi.T)      # column-major xdims[0] x nbox
+        outs = [np.zeros((nbox, self._acdim)) for _ in range(4)] + [np.zeros((nbox, self._ny)) for _ in range(2)]
+        louts = []
+        if self._nlit is not None:
+            nl = self._nlit
+            louts = [np.zeros((nbox, nl)), np.zeros((nbox, nl)), np.zeros((nbox, nl, self._n0)), np.zeros((nbox, nl))]    # smin, smax, uA, ub0
+        ms = C.c_double(0.0)
+        _lib.check(self._lib.nnsdp_crown_bound(h, nbox, loc.ctypes.data_as(dp), hic.ctypes.data_as(dp), *[o.ctypes.data_as(dp) for o in outs],
+                                               *([o.ctypes.data_as(dp) for o in louts] or [None] * 4), C.byref(ms)))
+        res = tuple(o.T for o in outs)
+        if self._nlit is not None:
+            res += (LiteralBounds(louts[0].T, louts[1].T, louts[2].transpose(1, 2, 0), louts[3].T),)
+        return res + (ms.value,) if return_ms else res
+
+    def eval(self, X, return_ms: bool = False):
+        """what evalFeedFwdNetBatch(net, X) returns, from the resident network"""
+        h = self._handle()
+        X = np.asarray(X, dtype=np.float64)
+        if X.ndim != 2 or X.shape[0] != self._n0:
+            raise ValueError("X must be xdims[0] x N")
+        N, dp = X.shape[1], _lib.c_double_p
+        Xc = np.ascontiguousarray(X.T)                      # column-major xdims[0] x N
+        Y = np.empty((N, self._ny), dtype=np.float64)
+        ms = C.c_double(0.0)
+        _lib.check(self._lib.nnsdp_crown_eval(h, N, Xc.ctypes.data_as(dp), Y.ctypes.data_as(dp), C.byref(ms)))
+        return (Y.T, ms.value) if return_ms else Y.T
+
+    def info(self) -> dict:
+        h, v, out = self._handle(), C.c_double(0.0), {}
+        for what, name in enumerate(self._INFO):
+            _lib.check(self._lib.nnsdp_crown_info(h, what, C.byref(v)))
+            out[name] = int(v.value)
+        return out
+
+    def close(self):
+        h, self._h = self._h, None
+        if h is not None:
+            _lib.check(self._lib.nnsdp_crown_destroy(h))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def sampleTrajs(net: M.FeedFwdNet, x1min, x1max, N: int = 100000, seed: int = 1234):

@@ -3,7 +3,8 @@
 A relaxation over a whole input box is often too loose to decide a literal, and TARGET_UNREACHABLE / ITERATION_LIMIT are final
 answers of a single solve.  verifySplit works level by level on the frontier of open sub-boxes:
 
-  bound    one makeIntervalsBatch call for the whole frontier (csrc/crown_batch.hpp on the GPU, or the host routine per box);
+  bound    one makeIntervalsBatch call for the whole frontier (csrc/crown_batch.hpp on the GPU, or the host routine per box), or
+           with crown_backend = "resident" one call of a CrownBounder that keeps the network on the GPU for the whole verifySplit;
            a literal  normal' f(x) <= h  is proved on a box when  sum_j max(n_j ymin_j, n_j ymax_j) <= h.  With literal_bounds the
            same call also back-propagates every normal folded into the last affine layer (the literal pass of the kernel /
            nnsdp_make_intervals_lits), which keeps the correlation between the outputs; the smaller of the two bounds is used
@@ -42,8 +43,10 @@ class SplitOptions:
     max_depth: int = 24           # bisections of one box before the driver gives up
     sdp_per_level: int = 26       # open boxes per level that get SDPs (0: bounds only)
     batch: int = 13               # SDPs advanced in lockstep in one batch handle
-    # makeIntervalsBatch backend and where the refutation points are evaluated: "gpu" (csrc/crown_batch.hpp, fp64) or "host".  "host" is
-    # the default until the kernel has been timed against 16 host workers (tools/split_timing.py)
+    # makeIntervalsBatch backend and where the refutation points are evaluated: "gpu" (csrc/crown_batch.hpp, fp64), "host", or
+    # "resident": one frontend.CrownBounder for the whole call (the network uploaded once; the same bits as "gpu" on a ReLU network,
+    # and the only GPU route for a Tanh network).  "host" is the default until the kernel has been timed against 16 host workers
+    # (tools/split_timing.py)
     crown_backend: str = "host"
     samples: int = 0              # extra uniform points per open box in the refutation step, seeded from the box index
     # bound the literals themselves in the bound step (makeIntervalsBatch(normals=...)) and use min(that bound, the per-output one)
@@ -153,8 +156,8 @@ def verifySplit(net: M.FeedFwdNet, x1min, x1max, literals: Sequence[Tuple[Any, f
     one literal proved on all of it, "violated" with a witness x at which every literal is false, "unknown" when max_boxes or
     max_depth ends the search (the open leaves are returned as they are)."""
     split = split or SplitOptions()
-    if split.crown_backend not in ("gpu", "host"):
-        raise ValueError("crown_backend must be 'gpu' or 'host'")
+    if split.crown_backend not in ("gpu", "host", "resident"):
+        raise ValueError("crown_backend must be 'gpu', 'host' or 'resident'")
     t_start = time.perf_counter()
     root_lo, root_hi = np.array(x1min, dtype=np.float64), np.array(x1max, dtype=np.float64)
     n0, ny = net.xdims[0], net.xdims[-1]
@@ -167,10 +170,22 @@ def verifySplit(net: M.FeedFwdNet, x1min, x1max, literals: Sequence[Tuple[Any, f
     if normals.shape != (len(literals), ny):
         raise ValueError("every normal must have xdims[K] entries")
     seconds = {"crown": 0.0, "setup": 0.0, "solve": 0.0, "finish": 0.0, "total": 0.0}
+    frontier = [_Box(root_lo, root_hi, np.zeros(n0, dtype=np.int64))]
+    want_lits = split.literal_bounds or split.corner_points
+    bounder = F.CrownBounder(net, normals if want_lits else None) if split.crown_backend == "resident" else None
+    try:
+        return _split_levels(net, frontier, root_lo, root_hi, normals, hs, beta, opts, split, bounder, seconds, t_start)
+    finally:
+        if bounder is not None:
+            bounder.close()
+
+
+def _split_levels(net, frontier, root_lo, root_hi, normals, hs, beta, opts, split, bounder, seconds, t_start) -> SplitResult:
+    """the levels of verifySplit; bounder: the CrownBounder of crown_backend = "resident" (the caller closes it), else None"""
+    n0 = net.xdims[0]
     leaves: List[Leaf] = []
     visited = sdp_solves = depth = 0
     splittable = root_hi > root_lo
-    frontier = [_Box(root_lo, root_hi, np.zeros(n0, dtype=np.int64))]
 
     def done(verdict, witness=None):
         seconds["total"] = time.perf_counter() - t_start
@@ -190,11 +205,15 @@ def verifySplit(net: M.FeedFwdNet, x1min, x1max, literals: Sequence[Tuple[Any, f
         t0 = time.perf_counter()
         lo, hi = np.stack([b.lo for b in frontier], axis=1), np.stack([b.hi for b in frontier], axis=1)
         lits = None
-        if split.literal_bounds or split.corner_points:
-            *iv, lits = F.makeIntervalsBatch(net, lo, hi, backend=split.crown_backend, normals=normals)
-            iv = tuple(iv)
+        if bounder is not None:
+            iv = bounder.bound(lo, hi)
+        elif split.literal_bounds or split.corner_points:
+            iv = F.makeIntervalsBatch(net, lo, hi, backend=split.crown_backend, normals=normals)
         else:
             iv = F.makeIntervalsBatch(net, lo, hi, backend=split.crown_backend)
+        if split.literal_bounds or split.corner_points:
+            *iv, lits = iv
+            iv = tuple(iv)
         seconds["crown"] += time.perf_counter() - t0
         ymin, ymax = iv[4], iv[5]
         cheap = np.stack([np.maximum(nrm[:, None] * ymin, nrm[:, None] * ymax).sum(axis=0) for nrm in normals])   # literal x box
@@ -218,7 +237,10 @@ def verifySplit(net: M.FeedFwdNet, x1min, x1max, literals: Sequence[Tuple[Any, f
                     rng = np.random.default_rng(frontier[b].index)
                     pts.append(lo[:, [b]] + rng.random((n0, int(split.samples))) * (hi[:, [b]] - lo[:, [b]]))
             X = np.concatenate(pts, axis=1)
-            Y = F.evalFeedFwdNetBatch(net, X) if split.crown_backend == "gpu" else F.evalFeedFwdNet(net, X)
+            if bounder is not None:
+                Y = bounder.eval(X)
+            else:
+                Y = F.evalFeedFwdNetBatch(net, X) if split.crown_backend == "gpu" else F.evalFeedFwdNet(net, X)
             for c in np.flatnonzero(_violates_all(Y, normals, hs)):
                 x = X[:, c].copy()
                 if bool(_violates_all(F.evalFeedFwdNet(net, x)[:, None], normals, hs)[0]):     # confirmed in fp64 on the host

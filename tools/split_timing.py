@@ -1,6 +1,11 @@
 #!/usr/bin/env python3
 """Batched CROWN bounds: the GPU kernel against the host routine, and where one verifySplit spends its time.
-usage: python tools/split_timing.py [--nlit] [case ...]   cases: W10-D5 W40-D20 acas-shape   (default: all)
+usage: python tools/split_timing.py [--nlit | --resident] [case ...]   cases: W10-D5 W40-D20 acas-shape   (default: all)
+With --resident only the resident leg runs and profiles/split_timing_resident_<case>.json is written:
+  bound    CrownBounder.bound beside makeIntervalsBatch(backend="gpu") at nbox = 1, 16, 256: wall-clock of the call and HIP-event time
+           of the launch, median of 7 after 2 warm calls - what keeping the network on the device saves per level of a split tree
+  eval     CrownBounder.eval beside evalFeedFwdNetBatch at N = 1, 16, 256, the same way
+  split    one verifySplit (bounds only, at most 256 boxes) with crown_backend "gpu" and with "resident": verdict, visited, `seconds`
 With --nlit only the literal leg runs and profiles/split_timing_nlit_<case>.json is written:
   nlit     nnsdp_make_intervals_batch_lits at nbox = 256 with 0, 1 and 10 literals (y_0 - y_last, then seeded Gaussian normals): HIP-event
            time of the launch and wall-clock of the call, median of 7 after 2 warm launches - what the literal pass adds to a launch
@@ -75,6 +80,48 @@ def nlit_rows(net, lo, hi, nbox=256):
     return rows
 
 
+def _timed(call):
+    """call() -> (..., kernel ms): medians of the wall-clock and of the kernel time over 7 calls after 2 warm ones"""
+    ker, wall = [], []
+    for i in range(9):
+        t = time.perf_counter()
+        *_, ms = call()
+        if i >= 2:
+            ker.append(ms); wall.append(1e3 * (time.perf_counter() - t))
+    return statistics.median(wall), statistics.median(ker)
+
+
+def resident_rows(net, lo, hi):
+    bound, ev = [], []
+    with na.CrownBounder(net) as bd:
+        for n in (1, 16, 256):
+            blo, bhi = sub_boxes(lo, hi, n)
+            ow, ok = _timed(lambda: na.makeIntervalsBatch(net, blo, bhi, backend="gpu", return_ms=True))
+            rw, rk = _timed(lambda: bd.bound(blo, bhi, return_ms=True))
+            bound.append(dict(nbox=n, one_shot_call_ms_median=ow, one_shot_kernel_ms_median=ok, resident_call_ms_median=rw,
+                              resident_kernel_ms_median=rk, resident_call_over_one_shot=rw / ow))
+            print(bound[-1], flush=True)
+            X = 0.5 * (blo + bhi)
+            ow, ok = _timed(lambda: na.evalFeedFwdNetBatch(net, X, return_ms=True))
+            rw, rk = _timed(lambda: bd.eval(X, return_ms=True))
+            ev.append(dict(N=n, one_shot_call_ms_median=ow, one_shot_kernel_ms_median=ok, resident_call_ms_median=rw,
+                           resident_kernel_ms_median=rk, resident_call_over_one_shot=rw / ow))
+            print(ev[-1], flush=True)
+        info = bd.info()
+    nrm = np.zeros(net.xdims[-1]); nrm[0] = 1.0
+    X = lo[:, None] + np.random.default_rng(0).random((len(lo), 20000)) * (hi - lo)[:, None]
+    s = float((nrm @ na.evalFeedFwdNetBatch(net, X)).max())
+    iv = na.makeIntervalsBatch(net, lo[:, None], hi[:, None], backend="gpu")
+    c0 = float(np.maximum(nrm * iv[4][:, 0], nrm * iv[5][:, 0]).sum())
+    h = s + 0.25 * (c0 - s)
+    split = {}
+    for backend in ("gpu", "resident"):
+        r = na.verifySplit(net, lo, hi, [(nrm, h)], 0, na.AdmmSdpOptions(), na.SplitOptions(max_boxes=256, sdp_per_level=0, crown_backend=backend))
+        split[backend] = dict(verdict=r.verdict, visited=r.visited, leaves=len(r.leaves), seconds=r.seconds)
+        print(backend, split[backend], flush=True)
+    return dict(bound=bound, eval=ev, handle=info, h=h, split=split)
+
+
 def split_row(net, lo, hi):
     nrm = np.zeros(net.xdims[-1]); nrm[0] = 1.0
     X = lo[:, None] + np.random.default_rng(0).random((len(lo), 20000)) * (hi - lo)[:, None]
@@ -95,12 +142,16 @@ def split_row(net, lo, hi):
 
 if __name__ == "__main__":
     args = sys.argv[1:]
-    lit_leg = "--nlit" in args
-    names = [a for a in args if a != "--nlit"] or ["W10-D5", "W40-D20", "acas-shape"]
+    lit_leg, res_leg = "--nlit" in args, "--resident" in args
+    names = [a for a in args if a not in ("--nlit", "--resident")] or ["W10-D5", "W40-D20", "acas-shape"]
     out_dir = os.environ.get("SPLIT_TIMING_OUT", os.path.join(ROOT, "profiles"))
     os.makedirs(out_dir, exist_ok=True)
     for name in names:
         net, lo, hi = case(name)
+        if res_leg:
+            with open(os.path.join(out_dir, f"split_timing_resident_{name}.json"), "w") as fh:
+                json.dump(dict(case=name, xdims=net.xdims, **resident_rows(net, lo, hi)), fh, indent=1)
+            continue
         if lit_leg:
             with open(os.path.join(out_dir, f"split_timing_nlit_{name}.json"), "w") as fh:
                 json.dump(dict(case=name, xdims=net.xdims, nlit=nlit_rows(net, lo, hi)), fh, indent=1)
