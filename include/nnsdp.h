@@ -339,6 +339,23 @@ int nnsdp_make_intervals_lits(int32_t K, const int32_t* xdims, const double* M, 
                               double* ymin, double* ymax, int32_t nlit, const double* normals, double* lit_smin, double* lit_smax,
                               double* uA, double* ub0);
 
+/* nnsdp_make_intervals_lits plus optimised lower slopes of the unstable ReLUs for the literals' UPPER bounds (alpha-CROWN, DESIGN.md
+ * section 5).  Plain CROWN gives a neuron with l < 0 < u the lower slope 1 if u / (u - l) > 0.5 else 0; any alpha in [0, 1] is sound.
+ * Per literal, `steps` projected-gradient steps  alpha <- clip(alpha - eta0 decay^s g / max|g|, 0, 1)  on the literal's smax, g the
+ * analytic gradient (one forward pass through the relaxed network at the maximiser of the linear bound); the result is the first
+ * iterate with the smallest smax.  The hidden layers' pre-activation bounds stay plain CROWN; float32 like the rest of the routine.
+ * The arguments of nnsdp_make_intervals_lits receive the bits that entry writes.  Then: steps in 0..64, eta0 > 0, decay in (0, 1];
+ * alpha0 NULL (start from the plain rule) or [acdim x nlit], neuron index fastest, clipped to [0, 1], entries at neurons that are not
+ * unstable ignored.  Outputs (any may be NULL): a_smax [nlit], a_uA [xdims[0] x nlit] column-major, a_ub0 [nlit] as lit_smax / uA /
+ * ub0; alpha [acdim x nlit] the slopes of the result (the plain rule at neurons that are not unstable); best_step [nlit] the iterate
+ * it came from.  steps = 0 without alpha0 returns the plain pass's bits.  -1 with a message for a Tanh network, nlit = 0, steps, eta0
+ * or decay out of range, or a non-finite alpha0 entry.  ReLU only, any width.  No GPU needed. */
+int nnsdp_make_intervals_lits_alpha(int32_t K, const int32_t* xdims, const double* M, int32_t activ, const double* x1min,
+                                    const double* x1max, double* acymin, double* acymax, double* acxmin, double* acxmax, double* smin,
+                                    double* smax, double* ymin, double* ymax, int32_t nlit, const double* normals, double* lit_smin,
+                                    double* lit_smax, double* uA, double* ub0, int32_t steps, double eta0, double decay,
+                                    const double* alpha0, double* a_smax, double* a_uA, double* a_ub0, double* alpha, int32_t* best_step);
+
 /* Sampled forward pass on the GPU: Y[:, s] = ffnet(X[:, s]) for N points in fp64.  Replaces the
  * N = 1e5 calls of evalFeedFwdNet (src/MyNeuralNetwork/MyNeuralNetwork.jl:40-48) inside Utils.sampleTrajs (src/Utils/qc.jl:40-47),
  * whose outputs shape the ellipsoid of NnSdp.findEllipsoid (approxEllipsoid, src/Utils/qc.jl:50-67).  K, xdims, M as in
@@ -400,6 +417,23 @@ int nnsdp_crown_create(int32_t K, const int32_t* xdims, const double* M, int32_t
 int nnsdp_crown_bound(nnsdp_crown* h, int32_t nbox, const double* x1min, const double* x1max,
                       double* acymin, double* acymax, double* acxmin, double* acxmax, double* ymin, double* ymax,
                       double* smin, double* smax, double* uA, double* ub0, double* kernel_ms);
+
+/* nnsdp_crown_bound plus optimised lower slopes of the unstable ReLUs for the literals' upper bounds: the iteration of
+ * nnsdp_make_intervals_lits_alpha in fp64, in a second kernel (csrc/crown_alpha.hpp, one workgroup per box, both products of a step on
+ * fp64 MFMA) launched behind the plain one on the handle's stream.  The arguments of nnsdp_crown_bound receive exactly what that entry
+ * writes.  steps, eta0, decay as there; alpha0 NULL or [acdim x nlit x nbox] (neuron index fastest, then the literal, then the box).
+ * Outputs (HOST pointers, any may be NULL): a_smax [nlit x nbox], a_uA [xdims[0] x nlit x nbox], a_ub0 [nlit x nbox], alpha
+ * [acdim x nlit x nbox], best_step [nlit x nbox].  One upload (the boxes and alpha0), two launches, one download, one synchronisation.
+ * The per-(literal, neuron) state lives in buffers of the handle that are allocated at the first call of this entry, grow like the
+ * others and are counted by nnsdp_crown_info; a handle that never calls it holds what it held without it.  No atomics: a literal's
+ * bits depend neither on nbox, nor on the box's position, nor on the other literals, nor on earlier calls.
+ * -1 with a message, before the GPU is touched, for a Tanh handle, a handle without literals, steps outside 0..64, eta0 not positive
+ * and finite, decay outside (0, 1], or a non-finite alpha0 entry. */
+int nnsdp_crown_bound_alpha(nnsdp_crown* h, int32_t nbox, const double* x1min, const double* x1max,
+                            double* acymin, double* acymax, double* acxmin, double* acxmax, double* ymin, double* ymax,
+                            double* smin, double* smax, double* uA, double* ub0, double* kernel_ms,
+                            int32_t steps, double eta0, double decay, const double* alpha0,
+                            double* a_smax, double* a_uA, double* a_ub0, double* alpha, int32_t* best_step);
 
 /* The sampled forward pass on the resident network: the kernel, launch geometry and bits of the one-shot sampled forward entry. */
 int nnsdp_crown_eval(nnsdp_crown* h, int64_t N, const double* X, double* Y, double* kernel_ms);

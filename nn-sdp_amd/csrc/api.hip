@@ -25,6 +25,7 @@
 #include "intervals.hpp"
 #include "forward.hpp"
 #include "crown_batch.hpp"
+#include "crown_alpha.hpp"
 
 namespace nnsdp {
 
@@ -2440,13 +2441,19 @@ struct nnsdp_crown {
   DBuf<double> dM;                       // the network, then the literal head
   DBuf<double> din, dscr, dout, dX, dY;   // boxes (lo, then hi), per-box scratch, outputs; samples in / out
   double *hin = nullptr, *hout = nullptr, *hX = nullptr, *hY = nullptr;      // pinned staging of the four transfers
-  size_t box_cap = 0, sample_cap = 0;
+  // nnsdp_crown_bound_alpha only (nothing before its first call): boxes then alpha0; the plain outputs then the alpha outputs; the state
+  DBuf<double> dain, daout, dast;
+  double *hain = nullptr, *haout = nullptr;
+  size_t box_cap = 0, sample_cap = 0, alpha_cap = 0;
   hipStream_t st = nullptr;
   hipEvent_t e0 = nullptr, e1 = nullptr;
   long long n_alloc = 0, n_upload = 0, n_bound = 0;
 
   size_t scr_per_box() const { return (size_t)(activ == NNSDP_ACTIV_TANH ? 6 : 2) * acdim; }
   size_t out_per_box() const { return 4 * (size_t)acdim + 2 * (size_t)ny + 3 * (size_t)nlit + (size_t)nlit * n0; }
+  size_t ain_per_box() const { return 2 * (size_t)n0 + (size_t)nlit * acdim; }
+  size_t aout_per_box() const { return out_per_box() + (size_t)nlit * (3 + (size_t)n0 + (size_t)acdim); }
+  size_t ast_per_box() const { return 3 * (size_t)nlit * acdim; }
   size_t lds_bytes() const { return activ == NNSDP_ACTIV_TANH ? kCbLdsBytesTanh : kCbLdsBytes; }
   const void* kernel() const {
     return activ == NNSDP_ACTIV_TANH ? reinterpret_cast<const void*>(&k_crown_resident<kCbTanh>)
@@ -2458,7 +2465,8 @@ struct nnsdp_crown {
     if (count) HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&h), count * sizeof(double), hipHostMallocDefault));
   }
   size_t device_bytes() const {
-    return dxd.bytes() + dao.bytes() + dmo.bytes() + dM.bytes() + din.bytes() + dscr.bytes() + dout.bytes() + dX.bytes() + dY.bytes();
+    return dxd.bytes() + dao.bytes() + dmo.bytes() + dM.bytes() + din.bytes() + dscr.bytes() + dout.bytes() + dX.bytes() + dY.bytes() +
+           dain.bytes() + daout.bytes() + dast.bytes();
   }
   // the capacity grows geometrically and never shrinks
   void reserve_boxes(size_t nbox) {
@@ -2467,6 +2475,17 @@ struct nnsdp_crown {
     dalloc(din, 2 * cap * n0); dalloc(dscr, cap * scr_per_box()); dalloc(dout, cap * out_per_box());
     pinned(hin, 2 * cap * n0); pinned(hout, cap * out_per_box());
     box_cap = cap;
+  }
+  // the buffers of the alpha calls; the scratch is the plain calls' (reserve_boxes)
+  void reserve_alpha(size_t nbox) {
+    reserve_boxes(nbox);
+    if (nbox <= alpha_cap) return;
+    if (!alpha_cap)
+      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_crown_alpha), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kCaLdsBytes));
+    const size_t cap = std::max(nbox, 2 * alpha_cap);
+    dalloc(dain, cap * ain_per_box()); dalloc(daout, cap * aout_per_box()); dalloc(dast, cap * ast_per_box());
+    pinned(hain, cap * ain_per_box()); pinned(haout, cap * aout_per_box());
+    alpha_cap = cap;
   }
   void reserve_samples(size_t N) {
     if (N <= sample_cap) return;
@@ -2477,7 +2496,7 @@ struct nnsdp_crown {
   }
   ~nnsdp_crown() {
     if (st) (void)hipStreamSynchronize(st);
-    for (double* h : {hin, hout, hX, hY}) if (h) (void)hipHostFree(h);
+    for (double* h : {hin, hout, hX, hY, hain, haout}) if (h) (void)hipHostFree(h);
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
     if (st) (void)hipStreamDestroy(st);
@@ -2878,12 +2897,35 @@ static void check_literals(int32_t ny, int32_t nlit, const double* normals) {
         throw std::invalid_argument("literal " + std::to_string(i) + ": the normal has a non-finite entry (NaN or infinity)");
 }
 
+// the options and outputs that the two _alpha entries add to their plain counterparts
+struct AlphaReq {
+  int32_t steps;
+  double eta0, decay;
+  const double* alpha0;
+  double *a_smax, *a_uA, *a_ub0, *alpha;
+  int32_t* best_step;
+};
+static void check_alpha_options(int32_t steps, double eta0, double decay) {
+  if (steps < 0 || steps > 64) throw std::invalid_argument("alpha: steps must be in 0..64, got " + std::to_string(steps));
+  if (!std::isfinite(eta0) || !(eta0 > 0.0)) throw std::invalid_argument("alpha: eta0 must be positive and finite");
+  if (!(decay > 0.0 && decay <= 1.0)) throw std::invalid_argument("alpha: decay must be in (0, 1]");
+}
+static void check_alpha0(const double* alpha0, size_t count) {
+  for (size_t k = 0; k < count; ++k)
+    if (!std::isfinite(alpha0[k])) throw std::invalid_argument("alpha0 has a non-finite entry (NaN or infinity) at index " + std::to_string(k));
+}
+
 static int make_intervals_impl(int32_t K, const int32_t* xdims, const double* M, int32_t activ, const double* x1min, const double* x1max,
                          double* acymin, double* acymax, double* acxmin, double* acxmax, double* smin, double* smax,
                          double* ymin, double* ymax, int32_t nlit = 0, const double* normals = nullptr, double* lit_smin = nullptr,
-                         double* lit_smax = nullptr, double* uA = nullptr, double* ub0 = nullptr) {
+                         double* lit_smax = nullptr, double* uA = nullptr, double* ub0 = nullptr, const AlphaReq* ar = nullptr) {
   API_BEGIN
   if (activ != NNSDP_ACTIV_RELU && activ != NNSDP_ACTIV_TANH) throw std::invalid_argument("unknown activation");
+  if (ar) {
+    if (activ != NNSDP_ACTIV_RELU) throw std::invalid_argument("optimised slopes (alpha) are for ReLU networks, not Tanh");
+    if (nlit < 1) throw std::invalid_argument("optimised slopes (alpha) need literals: nlit must be in 1..64");
+    check_alpha_options(ar->steps, ar->eta0, ar->decay);
+  }
   nnsdp::LitHead head;
   if (nlit != 0) {
     if (K < 2 || !xdims || !M) throw std::invalid_argument("make_intervals: bad arguments");
@@ -2892,6 +2934,11 @@ static int make_intervals_impl(int32_t K, const int32_t* xdims, const double* M,
     check_literals(xdims[K], nlit, normals);
     head = nnsdp::make_lit_head(K, xdims, M, nlit, normals);
   }
+  if (ar && ar->alpha0) {
+    size_t acd = 0;
+    for (int k = 1; k < K; ++k) acd += (size_t)xdims[k];
+    check_alpha0(ar->alpha0, (size_t)nlit * acd);
+  }
   nnsdp::IntervalsOut iv = nnsdp::make_intervals(K, xdims, M, x1min, x1max, activ == NNSDP_ACTIV_TANH, nlit > 0 ? &head : nullptr);
   for (int i = 0; i < nlit; ++i) {
     if (lit_smin) lit_smin[i] = iv.smin[i];
@@ -2899,6 +2946,14 @@ static int make_intervals_impl(int32_t K, const int32_t* xdims, const double* M,
     if (ub0) ub0[i] = iv.ub0[i];
   }
   if (uA && nlit > 0) std::copy(iv.uA.begin(), iv.uA.end(), uA);
+  if (ar) {
+    const nnsdp::AlphaOut ao = nnsdp::lits_alpha(K, xdims, M, head, iv.prel, iv.preu, x1min, x1max, ar->steps, ar->eta0, ar->decay, ar->alpha0);
+    if (ar->a_smax) std::copy(ao.smax.begin(), ao.smax.end(), ar->a_smax);
+    if (ar->a_uA) std::copy(ao.uA.begin(), ao.uA.end(), ar->a_uA);
+    if (ar->a_ub0) std::copy(ao.ub0.begin(), ao.ub0.end(), ar->a_ub0);
+    if (ar->alpha) std::copy(ao.alpha.begin(), ao.alpha.end(), ar->alpha);
+    if (ar->best_step) std::copy(ao.best_step.begin(), ao.best_step.end(), ar->best_step);
+  }
   const double eps = 1e-4;   // src/Qc/activ_sector.jl:65
   size_t o = 0;
   for (int k = 1; k < K; ++k)
@@ -2943,6 +2998,16 @@ int nnsdp_make_intervals_lits(int32_t K, const int32_t* xdims, const double* M, 
                               double* uA, double* ub0) {
   return make_intervals_impl(K, xdims, M, activ, x1min, x1max, acymin, acymax, acxmin, acxmax, smin, smax, ymin, ymax, nlit, normals,
                              lit_smin, lit_smax, uA, ub0);
+}
+
+int nnsdp_make_intervals_lits_alpha(int32_t K, const int32_t* xdims, const double* M, int32_t activ, const double* x1min,
+                                    const double* x1max, double* acymin, double* acymax, double* acxmin, double* acxmax, double* smin,
+                                    double* smax, double* ymin, double* ymax, int32_t nlit, const double* normals, double* lit_smin,
+                                    double* lit_smax, double* uA, double* ub0, int32_t steps, double eta0, double decay,
+                                    const double* alpha0, double* a_smax, double* a_uA, double* a_ub0, double* alpha, int32_t* best_step) {
+  const AlphaReq ar{steps, eta0, decay, alpha0, a_smax, a_uA, a_ub0, alpha, best_step};
+  return make_intervals_impl(K, xdims, M, activ, x1min, x1max, acymin, acymax, acxmin, acxmax, smin, smax, ymin, ymax, nlit, normals,
+                             lit_smin, lit_smax, uA, ub0, &ar);
 }
 
 int nnsdp_eval_network(int32_t K, const int32_t* xdims, const double* M, int32_t activ, int64_t N, const double* X, double* Y,
@@ -3163,6 +3228,68 @@ int nnsdp_crown_bound(nnsdp_crown* h, int32_t nbox, const double* x1min, const d
   const double* src = h->hout;
   for (int o = 0; o < 10; src += len[o], ++o)
     if (host[o]) std::copy(src, src + len[o], host[o]);
+  API_END
+}
+
+int nnsdp_crown_bound_alpha(nnsdp_crown* h, int32_t nbox, const double* x1min, const double* x1max,
+                            double* acymin, double* acymax, double* acxmin, double* acxmax, double* ymin, double* ymax,
+                            double* smin, double* smax, double* uA, double* ub0, double* kernel_ms,
+                            int32_t steps, double eta0, double decay, const double* alpha0,
+                            double* a_smax, double* a_uA, double* a_ub0, double* alpha, int32_t* best_step) {
+  API_BEGIN
+  if (!h) throw std::invalid_argument("null handle");
+  if (h->activ != NNSDP_ACTIV_RELU) throw std::invalid_argument("optimised slopes (alpha) are for ReLU networks, not Tanh");
+  if (h->nlit < 1) throw std::invalid_argument("optimised slopes (alpha) need literals: the handle was created without normals");
+  check_alpha_options(steps, eta0, decay);
+  if (nbox < 0) throw std::invalid_argument("nbox must be >= 0");
+  if (nbox == 0) return 0;
+  if (!x1min || !x1max) throw std::invalid_argument("null argument");
+  const int n0 = h->n0, acdim = h->acdim, ny = h->ny, nlit = h->nlit;
+  for (long long b = 0; b < nbox; ++b)
+    for (int i = 0; i < n0; ++i)
+      if (!std::isfinite(x1min[b * n0 + i]) || !std::isfinite(x1max[b * n0 + i]) || !(x1min[b * n0 + i] <= x1max[b * n0 + i]))
+        throw std::invalid_argument("box " + std::to_string(b) + ": x1min must be <= x1max and both finite (no NaN, no infinity)");
+  const size_t nb = (size_t)nbox, nin = nb * n0, na = nb * acdim, ny_all = nb * ny, nl_all = nb * (size_t)nlit, nA_all = nl_all * n0;
+  const size_t nst_all = nl_all * acdim, nplain = nb * h->out_per_box(), nout = nb * h->aout_per_box();
+  if (alpha0) check_alpha0(alpha0, nst_all);
+  h->reserve_alpha(nb);
+  // one upload: the boxes, then alpha0 when there is one
+  std::copy(x1min, x1min + nin, h->hain);
+  std::copy(x1max, x1max + nin, h->hain + nin);
+  if (alpha0) std::copy(alpha0, alpha0 + nst_all, h->hain + 2 * nin);
+  HIPCHK(hipMemcpyAsync(h->dain.p, h->hain, (2 * nin + (alpha0 ? nst_all : 0)) * sizeof(double), hipMemcpyHostToDevice, h->st));
+  nnsdp::CrownAlphaArgs p;
+  nnsdp::CrownArgs& a = p.c;
+  a.K = h->K; a.xdims = h->dxd.p; a.moff = h->dmo.p; a.acoff = h->dao.p; a.M = h->dM.p; a.lo = h->dain.p; a.hi = h->dain.p + nin;
+  a.scratch = h->dscr.p;
+  a.acymin = h->daout.p; a.acymax = a.acymin + na; a.acxmin = a.acymin + 2 * na; a.acxmax = a.acymin + 3 * na;
+  a.ymin = a.acymin + 4 * na; a.ymax = a.ymin + ny_all; a.acdim = acdim;
+  a.nlit = nlit; a.H = h->dM.p + h->moff[h->K];
+  a.smin = a.ymax + ny_all; a.smax = a.smin + nl_all; a.ub0 = a.smax + nl_all; a.uA = a.ub0 + nl_all;
+  p.steps = steps; p.eta0 = eta0; p.decay = decay; p.alpha0 = alpha0 ? h->dain.p + 2 * nin : nullptr;
+  p.cur = h->dast.p; p.lam = p.cur + nst_all; p.best = p.lam + nst_all;
+  p.a_smax = h->daout.p + nplain; p.a_ub0 = p.a_smax + nl_all; p.a_step = p.a_ub0 + nl_all; p.a_uA = p.a_step + nl_all; p.alpha = p.a_uA + nA_all;
+  HIPCHK(hipEventRecord(h->e0, h->st));
+  hipLaunchKernelGGL(nnsdp::k_crown_resident<nnsdp::kCbRelu>, dim3((unsigned)nbox), dim3(256), nnsdp::kCbLdsBytes, h->st, a);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(nnsdp::k_crown_alpha, dim3((unsigned)nbox), dim3(256), nnsdp::kCaLdsBytes, h->st, p);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(h->e1, h->st));
+  HIPCHK(hipMemcpyAsync(h->haout, h->daout.p, nout * sizeof(double), hipMemcpyDeviceToHost, h->st));
+  HIPCHK(hipStreamSynchronize(h->st));
+  ++h->n_bound;
+  float ms = 0;
+  HIPCHK(hipEventElapsedTime(&ms, h->e0, h->e1));
+  if (kernel_ms) *kernel_ms = ms;
+  double* host[14] = {acymin, acymax, acxmin, acxmax, ymin, ymax, smin, smax, ub0, uA, a_smax, a_ub0, nullptr, a_uA};
+  const size_t len[14] = {na, na, na, na, ny_all, ny_all, nl_all, nl_all, nl_all, nA_all, nl_all, nl_all, nl_all, nA_all};
+  const double* src = h->haout;
+  for (int o = 0; o < 14; src += len[o], ++o) {
+    if (host[o]) std::copy(src, src + len[o], host[o]);
+    if (o == 12 && best_step)
+      for (size_t k = 0; k < nl_all; ++k) best_step[k] = (int32_t)src[k];
+  }
+  if (alpha) std::copy(src, src + nst_all, alpha);
   API_END
 }
 

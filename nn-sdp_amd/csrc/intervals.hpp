@@ -31,6 +31,7 @@ struct IntervalsOut {
   std::vector<std::vector<double>> plo, phi;      // K-1 pre-activation intervals (float64 interval step)
   // with a literal head (LitHead): raw bounds of the literals, and the upper bound's linear form  uA x + ub0  (uA row-major nlit x n0)
   std::vector<double> smin, smax, uA, ub0;
+  std::vector<std::vector<float>> prel, preu;     // the raw float32 pre-activation bounds the backward passes used (lits_alpha reads them)
 };
 
 // The head of a literal pass: H = [C W_{K-1} | C b_{K-1}] for the nlit x ny matrix C of literal normals (normals: ny x nlit,
@@ -258,6 +259,122 @@ inline IntervalsOut make_intervals(int K, const int32_t* xdims, const double* M,
       l[i] = sl; u[i] = su;
     }
     out.plo.push_back(std::move(l)); out.phi.push_back(std::move(u));
+  }
+  out.prel = std::move(prel); out.preu = std::move(preu);
+  return out;
+}
+
+// ---- optimised ReLU slopes for the literal pass (alpha-CROWN): per literal, projected-gradient steps on the
+// lower slope alpha in [0, 1] of every unstable neuron (l < 0 < u) of the upper bound's backward pass.  float32 like the passes above;
+// iterate 0 without alpha0 is crown_backward's upper matrix operation for operation.  The hidden layers' bounds stay plain CROWN.
+struct AlphaOut {
+  std::vector<double> smax, uA, ub0, alpha;      // nlit, nlit x n0 (row-major), nlit, nlit x acdim (row-major)
+  std::vector<int32_t> best_step;                // nlit
+};
+// prel / preu: IntervalsOut::prel / preu of the same network and box; alpha0: null or nlit x acdim (row-major)
+inline AlphaOut lits_alpha(int K, const int32_t* xdims, const double* M, const LitHead& head, const std::vector<std::vector<float>>& prel,
+                           const std::vector<std::vector<float>>& preu, const double* x1min, const double* x1max, int steps, double eta0,
+                           double decay, const double* alpha0) {
+  const int nlit = head.nlit, n0 = xdims[0];
+  std::vector<DenseF> W(K - 1);
+  std::vector<std::vector<float>> bs(K - 1);
+  std::vector<int> aoff(K, 0);
+  size_t off = 0;
+  for (int k = 0; k + 1 < K; ++k) {
+    const int r = xdims[k + 1], c = xdims[k];
+    W[k] = DenseF(r, c); bs[k].resize(r);
+    for (int j = 0; j < c; ++j)
+      for (int i = 0; i < r; ++i) W[k].at(i, j) = (float)M[off + (size_t)j * r + i];
+    for (int i = 0; i < r; ++i) bs[k][i] = (float)M[off + (size_t)c * r + i];
+    off += (size_t)r * (c + 1);
+    aoff[k + 1] = aoff[k] + r;
+  }
+  const int acdim = aoff[K - 1];
+  std::vector<float> du(acdim), dl(acdim), bu(acdim), c0(n0), r0(n0);
+  std::vector<char> uns(acdim);
+  for (int j = 0; j + 1 < K; ++j)
+    for (int t = 0; t < xdims[j + 1]; ++t) {
+      const int n = aoff[j] + t;
+      const float lr = std::min(prel[j][t], 0.0f), ur = std::max(std::max(preu[j][t], 0.0f), lr + 1e-8f);
+      du[n] = ur / (ur - lr);
+      dl[n] = du[n] > 0.5f ? 1.0f : 0.0f;
+      bu[n] = -lr * du[n];
+      uns[n] = prel[j][t] < 0.0f && preu[j][t] > 0.0f;
+    }
+  for (int q = 0; q < n0; ++q) {
+    const float lo = (float)x1min[q], hi = (float)x1max[q];
+    c0[q] = (hi + lo) / 2.0f; r0[q] = (hi - lo) / 2.0f;
+  }
+  AlphaOut out;
+  out.smax.assign(nlit, 0.0); out.uA.assign((size_t)nlit * n0, 0.0); out.ub0.assign(nlit, 0.0);
+  out.alpha.assign((size_t)nlit * acdim, 0.0); out.best_step.assign(nlit, 0);
+  const int dtop = xdims[K - 1];
+  std::vector<float> al(acdim), lam(acdim), g(acdim), row, nxt, z;
+  for (int i = 0; i < nlit; ++i) {
+    for (int n = 0; n < acdim; ++n) {
+      al[n] = dl[n];
+      if (alpha0 && uns[n]) al[n] = (float)std::min(std::max(alpha0[(size_t)i * acdim + n], 0.0), 1.0);
+    }
+    float best = 0.0f, eta = (float)eta0;
+    for (int s = 0; s <= steps; ++s) {
+      // backward pass of row i at al (crown_backward's upper matrix)
+      row.assign(dtop, 0.0f);
+      for (int t = 0; t < dtop; ++t) row[t] = (float)head.H[(size_t)t * nlit + i];
+      float ub = (float)head.H[(size_t)dtop * nlit + i];
+      for (int j = K - 2; j >= 0; --j) {
+        const int d = xdims[j + 1], in = xdims[j], o = aoff[j];
+        float su = 0.0f;
+        for (int t = 0; t < d; ++t) {
+          const float b = row[t];
+          lam[o + t] = b;
+          su += std::max(b, 0.0f) * bu[o + t] + std::min(b, 0.0f) * 0.0f;
+          row[t] = std::max(b, 0.0f) * du[o + t] + std::min(b, 0.0f) * al[o + t];
+        }
+        ub += su;
+        float tu = 0.0f;
+        for (int t = 0; t < d; ++t) tu += row[t] * bs[j][t];
+        ub += tu;
+        nxt.assign(in, 0.0f);
+        for (int t = 0; t < d; ++t) {
+          const float b = row[t];
+          if (b == 0.0f) continue;
+          const float* w = &W[j].a[(size_t)t * in];
+          for (int q = 0; q < in; ++q) nxt[q] += b * w[q];
+        }
+        row.swap(nxt);
+      }
+      float su = 0.0f, ru = 0.0f;
+      for (int q = 0; q < n0; ++q) { su += row[q] * c0[q]; ru += std::fabs(row[q]) * r0[q]; }
+      const float smax = su + ru + ub;
+      if (s == 0 || smax < best) {
+        best = smax;
+        out.smax[i] = smax; out.ub0[i] = ub; out.best_step[i] = s;
+        for (int q = 0; q < n0; ++q) out.uA[(size_t)i * n0 + q] = row[q];
+        for (int n = 0; n < acdim; ++n) out.alpha[(size_t)i * acdim + n] = al[n];
+      }
+      if (s == steps) break;
+      // gradient: the relaxed network the pass chose, at the maximiser x* = c + sgn(uA) r
+      z.assign(n0, 0.0f);
+      for (int q = 0; q < n0; ++q) z[q] = c0[q] + (row[q] > 0.0f ? r0[q] : row[q] < 0.0f ? -r0[q] : 0.0f);
+      float gmax = 0.0f;
+      for (int j = 0; j + 1 < K; ++j) {
+        const int d = xdims[j + 1], in = xdims[j], o = aoff[j];
+        nxt.assign(d, 0.0f);
+        for (int t = 0; t < d; ++t) {
+          float v = 0.0f;
+          for (int q = 0; q < in; ++q) v += W[j].at(t, q) * z[q];
+          v += bs[j][t];
+          const float lm = lam[o + t];
+          g[o + t] = uns[o + t] ? std::min(lm, 0.0f) * v : 0.0f;
+          gmax = std::max(gmax, std::fabs(g[o + t]));
+          nxt[t] = lm > 0.0f ? du[o + t] * v + bu[o + t] : al[o + t] * v;
+        }
+        z.swap(nxt);
+      }
+      if (!(gmax > 0.0f)) break;          // stationary
+      for (int n = 0; n < acdim; ++n) al[n] = std::min(std::max(al[n] - eta * g[n] / gmax, 0.0f), 1.0f);
+      eta *= (float)decay;
+    }
   }
   return out;
 }

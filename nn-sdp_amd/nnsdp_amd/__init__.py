@@ -9,7 +9,7 @@ from .methods import (  # noqa: F401
 )
 from .frontend import (  # noqa: F401
     read_nnet, evalFeedFwdNet, evalFeedFwdNetBatch, sampleTrajs, randomNetwork, makeIntervalsInfo, makeQcActivs, approxEllipsoid,
-    findEllipsoid, findCircle, findReach2Dpoly, write_scale_csv, runScale, ellipsoidQuery, makeIntervalsBatch, LiteralBounds, CrownBounder,
+    findEllipsoid, findCircle, findReach2Dpoly, write_scale_csv, runScale, ellipsoidQuery, makeIntervalsBatch, LiteralBounds, LiteralBoundsAlpha, CrownBounder,
 )
 from . import _lib  # noqa: F401
 from . import vnnlib  # noqa: F401

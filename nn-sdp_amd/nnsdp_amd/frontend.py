@@ -196,6 +196,45 @@ class LiteralBounds(NamedTuple):
     smax: np.ndarray      # nlit x nbox
     A: np.ndarray         # nlit x n0 x nbox
     b0: np.ndarray        # nlit x nbox
+    # set by a call with optimised slopes (LiteralBoundsAlpha); a plain call's result has the four fields above and nothing else
+    smax_plain = None
+    alpha = None
+    best_step = None
+
+
+class LiteralBoundsAlpha(LiteralBounds):
+    """LiteralBounds of a call with optimised ReLU slopes (alpha_steps > 0 or alpha0): smax / A / b0 are, per box and literal, those of
+    whichever of the plain pass and the alpha iteration has the smaller smax; smax_plain (nlit x nbox) is the plain pass's smax, alpha
+    (nlit x acdim x nbox) the slopes the iteration ended with (the plain rule at neurons that are not unstable) and best_step
+    (nlit x nbox, int32) the iterate they came from.  As a tuple it is the four fields of LiteralBounds."""
+
+    def __new__(cls, smin, smax, A, b0, a_smax, a_A, a_b0, alpha, best_step):
+        take = a_smax < smax
+        self = super().__new__(cls, smin, np.where(take, a_smax, smax), np.where(take[:, None, :], a_A, A), np.where(take, a_b0, b0))
+        self.smax_plain, self.alpha, self.best_step = smax, alpha, best_step
+        return self
+
+
+def _alpha_args(alpha_steps, alpha0, eta0, decay, nlit, acdim, nbox):
+    """the checked alpha options of makeIntervalsBatch / CrownBounder.bound: alpha0 as nbox x nlit x acdim (C order) or None"""
+    if nlit is None:
+        raise ValueError("optimised slopes (alpha_steps / alpha0) need literal normals")
+    if alpha0 is not None:
+        alpha0 = np.asarray(alpha0, dtype=np.float64)
+        if alpha0.shape != (nlit, acdim, nbox):
+            raise ValueError("alpha0 must be nlit x acdim x nbox")
+        alpha0 = np.ascontiguousarray(alpha0.transpose(2, 0, 1))
+    return int(alpha_steps), float(eta0), float(decay), alpha0
+
+
+def _alpha_outs(nbox, nlit, n0, acdim):
+    return [np.zeros((nbox, nlit)), np.zeros((nbox, nlit, n0)), np.zeros((nbox, nlit)), np.zeros((nbox, nlit, acdim))], \
+        np.zeros((nbox, nlit), dtype=np.int32)
+
+
+def _alpha_lits(louts, aouts, step):
+    return LiteralBoundsAlpha(louts[0].T, louts[1].T, louts[2].transpose(1, 2, 0), louts[3].T, aouts[0].T, aouts[1].transpose(1, 2, 0),
+                              aouts[2].T, aouts[3].transpose(1, 2, 0), step.T)
 
 
 def _host_pool(one, nbox: int, workers: int, entry: str):
@@ -212,7 +251,8 @@ def _host_pool(one, nbox: int, workers: int, entry: str):
             raise _lib.NnsdpError(next(c for c in codes if c), f"{entry} failed for a box of the batch")
 
 
-def makeIntervalsBatch(net: M.FeedFwdNet, lo, hi, backend: str = "host", workers: int = 16, return_ms: bool = False, normals=None):
+def makeIntervalsBatch(net: M.FeedFwdNet, lo, hi, backend: str = "host", workers: int = 16, return_ms: bool = False, normals=None,
+                       alpha_steps: int = 0, alpha0=None, eta0: float = 0.5, decay: float = 0.9):
     """CROWN-sliced bounds of many input boxes of one network: lo / hi are xdims[0] x nbox, one column per box.
     -> (acymin, acymax, acxmin, acxmax, ymin, ymax), one column per box.
     normals (nlit x xdims[K], nlit <= 64): the literals  normal_i' f(x)  are bounded in the same call by one more backward pass whose
@@ -222,8 +262,14 @@ def makeIntervalsBatch(net: M.FeedFwdNet, lo, hi, backend: str = "host", workers
     backend="host": nnsdp_make_intervals_activ (csrc/intervals.hpp, float32 arithmetic by design) once per box on a thread pool
                     of at most 16 workers (ctypes releases the GIL); the only one-shot route for Tanh networks (CrownBounder below
                     bounds them on the GPU) and the only route for wider layers, and the default until the kernel has been timed
-                    against it (tools/split_timing.py)."""
+                    against it (tools/split_timing.py).
+    alpha_steps > 0 or alpha0 (nlit x acdim x nbox), backend="host" with normals, ReLU: the literals' upper bounds with optimised
+    lower slopes of the unstable ReLUs (nnsdp_make_intervals_lits_alpha); the last element is then a LiteralBoundsAlpha.  On the
+    GPU this is CrownBounder.bound (crown_backend "resident" of the split driver)."""
     lib = _lib.load()
+    want_alpha = alpha_steps != 0 or alpha0 is not None
+    if want_alpha and backend == "gpu":
+        raise ValueError('optimised slopes (alpha) are not part of backend="gpu": use backend="host", or a CrownBounder ("resident")')
     xd, Mp = _net_arrays(net)
     lo = np.asarray(lo, dtype=np.float64)
     hi = np.asarray(hi, dtype=np.float64)
@@ -242,6 +288,22 @@ def makeIntervalsBatch(net: M.FeedFwdNet, lo, hi, backend: str = "host", workers
         nlit, n0 = nrm.shape[0], int(xd[0])
         louts = [np.zeros((nbox, nlit)), np.zeros((nbox, nlit)), np.zeros((nbox, nlit, n0)), np.zeros((nbox, nlit))]    # smin, smax, uA, ub0
         xdp, Mpp, nrp = xd.ctypes.data_as(_lib.c_int32_p), Mp.ctypes.data_as(dp), nrm.ctypes.data_as(dp)
+        if want_alpha and backend == "host":
+            steps, eta0, decay, a0 = _alpha_args(alpha_steps, alpha0, eta0, decay, nlit, acdim, nbox)
+            aouts, step = _alpha_outs(nbox, nlit, n0, acdim)
+            activ = M._activ_code(net.activ)
+
+            def one_alpha(b):
+                rows = [o[b].ctypes.data_as(dp) for o in outs]
+                return lib.nnsdp_make_intervals_lits_alpha(net.K, xdp, Mpp, activ, loc[b].ctypes.data_as(dp), hic[b].ctypes.data_as(dp),
+                                                           rows[0], rows[1], rows[2], rows[3], None, None, rows[4], rows[5], nlit, nrp,
+                                                           *[o[b].ctypes.data_as(dp) for o in louts], steps, eta0, decay,
+                                                           None if a0 is None else a0[b].ctypes.data_as(dp),
+                                                           *[o[b].ctypes.data_as(dp) for o in aouts], step[b].ctypes.data_as(_lib.c_int32_p))
+
+            _host_pool(one_alpha, nbox, workers, "nnsdp_make_intervals_lits_alpha")
+            res = tuple(o.T for o in outs) + (_alpha_lits(louts, aouts, step),)
+            return res + (ms.value,) if return_ms else res
         if backend == "gpu":
             _lib.check(lib.nnsdp_make_intervals_batch_lits(net.K, xdp, Mpp, M._activ_code(net.activ), nbox, loc.ctypes.data_as(dp),
                                                            hic.ctypes.data_as(dp), *[o.ctypes.data_as(dp) for o in outs], nlit, nrp,
@@ -278,6 +340,8 @@ def makeIntervalsBatch(net: M.FeedFwdNet, lo, hi, backend: str = "host", workers
         _host_pool(one, nbox, workers, "nnsdp_make_intervals_activ")
     else:
         raise ValueError("backend must be 'gpu' or 'host'")
+    if want_alpha:
+        raise ValueError("optimised slopes (alpha_steps / alpha0) need literal normals")
     res = tuple(o.T for o in outs)
     return res + (ms.value,) if return_ms else res
 
@@ -332,9 +396,12 @@ class CrownBounder:
             raise ValueError("the CrownBounder is closed")
         return self._h
 
-    def bound(self, lo, hi, return_ms: bool = False):
+    def bound(self, lo, hi, return_ms: bool = False, alpha_steps: int = 0, alpha0=None, eta0: float = 0.5, decay: float = 0.9):
         """what makeIntervalsBatch(net, lo, hi, backend="gpu"[, normals=...]) returns: the six arrays, then a LiteralBounds when the
-        bounder has normals, then the kernel's event time with return_ms"""
+        bounder has normals, then the kernel's event time with return_ms.
+        alpha_steps > 0 or alpha0 (nlit x acdim x nbox): nnsdp_crown_bound_alpha, a second kernel behind the plain one that optimises the
+        lower slopes of the unstable ReLUs for the literals' upper bounds (csrc/crown_alpha.hpp); the LiteralBounds is then a
+        LiteralBoundsAlpha, never looser than the plain one, and the event time covers both kernels.  ReLU bounders with normals."""
         h = self._handle()
         lo = np.asarray(lo, dtype=np.float64)
         hi = np.asarray(hi, dtype=np.float64)
@@ -348,6 +415,15 @@ class CrownBounder:
             nl = self._nlit
             louts = [np.zeros((nbox, nl)), np.zeros((nbox, nl)), np.zeros((nbox, nl, self._n0)), np.zeros((nbox, nl))]    # smin, smax, uA, ub0
         ms = C.c_double(0.0)
+        if alpha_steps != 0 or alpha0 is not None:
+            steps, eta0, decay, a0 = _alpha_args(alpha_steps, alpha0, eta0, decay, self._nlit, self._acdim, nbox)
+            aouts, step = _alpha_outs(nbox, self._nlit, self._n0, self._acdim)
+            _lib.check(self._lib.nnsdp_crown_bound_alpha(h, nbox, loc.ctypes.data_as(dp), hic.ctypes.data_as(dp),
+                                                         *[o.ctypes.data_as(dp) for o in outs + louts], C.byref(ms), steps, eta0, decay,
+                                                         None if a0 is None else a0.ctypes.data_as(dp),
+                                                         *[o.ctypes.data_as(dp) for o in aouts], step.ctypes.data_as(_lib.c_int32_p)))
+            res = tuple(o.T for o in outs) + (_alpha_lits(louts, aouts, step),)
+            return res + (ms.value,) if return_ms else res
         _lib.check(self._lib.nnsdp_crown_bound(h, nbox, loc.ctypes.data_as(dp), hic.ctypes.data_as(dp), *[o.ctypes.data_as(dp) for o in outs],
                                                *([o.ctypes.data_as(dp) for o in louts] or [None] * 4), C.byref(ms)))
         res = tuple(o.T for o in outs)

@@ -55,6 +55,13 @@ class SplitOptions:
     # the refutation step also tries, per open box, the corner  where(A >= 0, hi, lo)  of its best literal's linear upper bound
     # A' x + b0 (requests the literal bounds whatever literal_bounds says)
     corner_points: bool = False
+    # optimised lower slopes of the unstable ReLUs for the literal bounds (alpha-CROWN): projected-gradient steps
+    # per box and literal, their step size and its decay per step; needs literal_bounds and crown_backend "host" or "resident", ReLU.
+    # alpha_inherit: a child box starts from its parent's best slopes instead of the plain rule
+    alpha_steps: int = 0
+    alpha_eta0: float = 0.5
+    alpha_decay: float = 0.9
+    alpha_inherit: bool = False
 
 
 @dataclass
@@ -84,6 +91,7 @@ class _Box:
     hi: np.ndarray
     cuts: np.ndarray              # bisections per coordinate: the width is the root's times 2^-cuts, exactly comparable
     index: int = -1
+    alpha0: Optional[np.ndarray] = None      # nlit x acdim: the parent's best slopes (alpha_inherit)
 
 
 def _violates_all(Y, normals, hs) -> np.ndarray:
@@ -158,6 +166,15 @@ def verifySplit(net: M.FeedFwdNet, x1min, x1max, literals: Sequence[Tuple[Any, f
     split = split or SplitOptions()
     if split.crown_backend not in ("gpu", "host", "resident"):
         raise ValueError("crown_backend must be 'gpu', 'host' or 'resident'")
+    if split.alpha_steps < 0:
+        raise ValueError("alpha_steps must be >= 0")
+    if split.alpha_steps > 0:
+        if not split.literal_bounds:
+            raise ValueError("alpha_steps > 0 tightens the literal bounds: it needs literal_bounds=True")
+        if split.crown_backend not in ("host", "resident"):
+            raise ValueError("alpha_steps > 0 needs crown_backend 'host' or 'resident'")
+        if M._activ_code(net.activ) != M.ACTIV_RELU:
+            raise ValueError("alpha_steps > 0 is for ReLU networks")
     t_start = time.perf_counter()
     root_lo, root_hi = np.array(x1min, dtype=np.float64), np.array(x1max, dtype=np.float64)
     n0, ny = net.xdims[0], net.xdims[-1]
@@ -204,11 +221,15 @@ def _split_levels(net, frontier, root_lo, root_hi, normals, hs, beta, opts, spli
         # 1. bound
         t0 = time.perf_counter()
         lo, hi = np.stack([b.lo for b in frontier], axis=1), np.stack([b.hi for b in frontier], axis=1)
-        lits = None
+        lits, ak = None, {}
+        if split.alpha_steps > 0:
+            ak = dict(alpha_steps=int(split.alpha_steps), eta0=split.alpha_eta0, decay=split.alpha_decay)
+            if split.alpha_inherit and frontier[0].alpha0 is not None:
+                ak["alpha0"] = np.stack([b.alpha0 for b in frontier], axis=2)
         if bounder is not None:
-            iv = bounder.bound(lo, hi)
+            iv = bounder.bound(lo, hi, **ak)
         elif split.literal_bounds or split.corner_points:
-            iv = F.makeIntervalsBatch(net, lo, hi, backend=split.crown_backend, normals=normals)
+            iv = F.makeIntervalsBatch(net, lo, hi, backend=split.crown_backend, normals=normals, **ak)
         else:
             iv = F.makeIntervalsBatch(net, lo, hi, backend=split.crown_backend)
         if split.literal_bounds or split.corner_points:
@@ -277,8 +298,9 @@ def _split_levels(net, frontier, root_lo, root_hi, normals, hs, beta, opts, spli
             left_hi, right_lo = box.hi.copy(), box.lo.copy()
             left_hi[j] = mid
             right_lo[j] = mid
-            nxt.append(_Box(box.lo, left_hi, cuts))
-            nxt.append(_Box(right_lo, box.hi, cuts.copy()))
+            a0 = lits.alpha[:, :, b] if split.alpha_steps > 0 and split.alpha_inherit else None
+            nxt.append(_Box(box.lo, left_hi, cuts, alpha0=a0))
+            nxt.append(_Box(right_lo, box.hi, cuts.copy(), alpha0=a0))
         frontier = nxt
         depth += 1
     # every box of the last level was proved; boxes that the budget kept from being bounded are open leaves, and one open leaf is

@@ -1,6 +1,12 @@
 #!/usr/bin/env python3
 """Batched CROWN bounds: the GPU kernel against the host routine, and where one verifySplit spends its time.
-usage: python tools/split_timing.py [--nlit | --resident] [case ...]   cases: W10-D5 W40-D20 acas-shape   (default: all)
+usage: python tools/split_timing.py [--nlit | --resident | --alpha] [case ...]   cases: W10-D5 W40-D20 acas-shape   (default: all)
+With --alpha only the optimised-slope leg runs and profiles/split_timing_alpha_<case>.json is written:
+  bound    CrownBounder.bound at nbox = 256 with alpha_steps 0, 4 and 8 and 1 and 10 literals: wall-clock of the call and HIP-event time of
+           its kernels (the plain one, and k_crown_alpha behind it when alpha_steps > 0), median of 7 after 2 warm calls
+  host     makeIntervalsBatch(backend="host", workers=16) on the same boxes with the same settings, wall-clock, one run
+  split    one verifySplit (bounds only, literal_bounds, crown_backend "resident", at most 512 boxes) of the literal y_0 - y_last per
+           alpha_steps 0, 4, 8 and 4 with alpha_inherit: verdict, visited, `seconds`
 With --resident only the resident leg runs and profiles/split_timing_resident_<case>.json is written:
   bound    CrownBounder.bound beside makeIntervalsBatch(backend="gpu") at nbox = 1, 16, 256: wall-clock of the call and HIP-event time
            of the launch, median of 7 after 2 warm calls - what keeping the network on the device saves per level of a split tree
@@ -122,6 +128,41 @@ def resident_rows(net, lo, hi):
     return dict(bound=bound, eval=ev, handle=info, h=h, split=split)
 
 
+def alpha_rows(net, lo, hi, nbox=256):
+    blo, bhi = sub_boxes(lo, hi, nbox)
+    ny = net.xdims[-1]
+    Cm = np.random.default_rng(1).normal(size=(10, ny))
+    Cm[0] = 0.0; Cm[0, 0] = 1.0; Cm[0, ny - 1] -= 1.0
+    bound, host = [], []
+    for nlit in (1, 10):
+        with na.CrownBounder(net, Cm[:nlit]) as bd:
+            for steps in (0, 4, 8):
+                w, k = _timed(lambda: bd.bound(blo, bhi, return_ms=True, alpha_steps=steps))
+                *_, lits, _ = bd.bound(blo, bhi, return_ms=True, alpha_steps=steps)
+                gain = float(np.mean(lits.smax_plain - lits.smax)) if steps else 0.0
+                bound.append(dict(nbox=nbox, nlit=nlit, alpha_steps=steps, call_ms_median=w, kernel_ms_median=k, mean_smax_gain=gain,
+                                  device_bytes=bd.info()["device_bytes"]))
+                print(bound[-1], flush=True)
+        for steps in (0, 4, 8):
+            t = time.perf_counter()
+            na.makeIntervalsBatch(net, blo, bhi, backend="host", workers=16, normals=Cm[:nlit], alpha_steps=steps)
+            host.append(dict(nbox=nbox, nlit=nlit, alpha_steps=steps, host_16_workers_ms=1e3 * (time.perf_counter() - t)))
+            print(host[-1], flush=True)
+    nrm = Cm[0]
+    X = lo[:, None] + np.random.default_rng(0).random((len(lo), 20000)) * (hi - lo)[:, None]
+    s = float((nrm @ na.evalFeedFwdNetBatch(net, X)).max())
+    *_, lits = na.makeIntervalsBatch(net, lo[:, None], hi[:, None], backend="gpu", normals=nrm[None])
+    c0 = float(lits.smax[0, 0])
+    h = s + 0.25 * (c0 - s)
+    split = {}
+    for key, kw in (("0", {}), ("4", dict(alpha_steps=4)), ("8", dict(alpha_steps=8)), ("4+inherit", dict(alpha_steps=4, alpha_inherit=True))):
+        r = na.verifySplit(net, lo, hi, [(nrm, h)], 0, na.AdmmSdpOptions(),
+                           na.SplitOptions(max_boxes=512, sdp_per_level=0, crown_backend="resident", literal_bounds=True, **kw))
+        split[key] = dict(verdict=r.verdict, visited=r.visited, leaves=len(r.leaves), seconds=r.seconds)
+        print(key, split[key], flush=True)
+    return dict(bound=bound, host=host, sampled_max=s, root_plain_smax=c0, h=h, split=split)
+
+
 def split_row(net, lo, hi):
     nrm = np.zeros(net.xdims[-1]); nrm[0] = 1.0
     X = lo[:, None] + np.random.default_rng(0).random((len(lo), 20000)) * (hi - lo)[:, None]
@@ -142,12 +183,16 @@ def split_row(net, lo, hi):
 
 if __name__ == "__main__":
     args = sys.argv[1:]
-    lit_leg, res_leg = "--nlit" in args, "--resident" in args
-    names = [a for a in args if a not in ("--nlit", "--resident")] or ["W10-D5", "W40-D20", "acas-shape"]
+    lit_leg, res_leg, alpha_leg = "--nlit" in args, "--resident" in args, "--alpha" in args
+    names = [a for a in args if a not in ("--nlit", "--resident", "--alpha")] or ["W10-D5", "W40-D20", "acas-shape"]
     out_dir = os.environ.get("SPLIT_TIMING_OUT", os.path.join(ROOT, "profiles"))
     os.makedirs(out_dir, exist_ok=True)
     for name in names:
         net, lo, hi = case(name)
+        if alpha_leg:
+            with open(os.path.join(out_dir, f"split_timing_alpha_{name}.json"), "w") as fh:
+                json.dump(dict(case=name, xdims=net.xdims, **alpha_rows(net, lo, hi)), fh, indent=1)
+            continue
         if res_leg:
             with open(os.path.join(out_dir, f"split_timing_resident_{name}.json"), "w") as fh:
                 json.dump(dict(case=name, xdims=net.xdims, **resident_rows(net, lo, hi)), fh, indent=1)
