@@ -40,7 +40,7 @@
 extern "C" {
 #endif
 
-#define NNSDP_VERSION 220 /* 0.2.2 */
+#define NNSDP_VERSION 230 /* 0.2.3 */
 
 /* query_kind: Methods.SafetyQuery / Methods.ReachQuery (src/Methods/Methods.jl:22-43) */
 enum { NNSDP_QUERY_SAFETY = 0, NNSDP_QUERY_REACH = 1 };
@@ -438,8 +438,47 @@ int nnsdp_crown_bound_alpha(nnsdp_crown* h, int32_t nbox, const double* x1min, c
 /* The sampled forward pass on the resident network: the kernel, launch geometry and bits of the one-shot sampled forward entry. */
 int nnsdp_crown_eval(nnsdp_crown* h, int64_t N, const double* X, double* Y, double* kernel_ms);
 
-/* what: 0 device allocations made so far, 1 network uploads so far, 2 box capacity, 3 sample capacity, 4 bound calls,
- * 5 device bytes held. */
+/* The bounds-only input-splitting search of nnsdp_amd/split.py (_split_levels with sdp_per_level = 0, samples = 0) with the frontier
+ * kept on the device (csrc/crown_search.hpp): decides the clause  OR_i normal_i' f(x) <= hs[i]  on the root box x1min / x1max
+ * (xdims[0] each) by bisection along the coordinate that is widest relative to the root.  Per level: the handle's bound kernel on
+ * chunks of at most `chunk` boxes read directly from the frontier, the proof test (sum_j max(n_ij ymin_j, n_ij ymax_j), with
+ * literal_bounds the smaller of that and the literal pass's smax, minus hs[i]; the first minimum over i is the box's best literal; proved
+ * when it is <= 0), the forward pass on the open boxes' centres and (corner_points) the corners where(uA[best] >= 0, hi, lo), the
+ * bisection of the open boxes into the second frontier and the proved boxes' rows of a leaf log, all in device memory; the host reads
+ * back four integers per level (boxes bounded, proved, open, candidate points).  The tree, the order of the leaves and every number
+ * are those of the Python loop, bit for bit: the sum of the proof test has the order of numpy's pairwise reduction as split.py reaches
+ * it (plain ascending below 8 outputs, eight interleaved partial sums from 8 on; csrc/crown_search.hpp, search_cheap).
+ * The clause: a handle created with literals uses them (normals NULL, nlit the handle's); a handle without takes normals (ny x nlit
+ * column-major, nlit in 1..64) and can neither use literal_bounds nor corner_points.
+ * confirm: called on the host, only on a level that has candidate points, for each candidate in the order centres then corners, each
+ * in box order, with `user` and the point (xdims[0] doubles); a return value other than 0 makes the point the witness and ends the
+ * search (the split driver evaluates the network in fp64 there).  NULL accepts the first candidate as the device flagged it.
+ * The search ends "holds" (verdict 0) when no box is open, "violated" (1) with the witness, "unknown" (2) when max_boxes boxes were
+ * bounded, a level deeper than max_depth would be needed or no coordinate can be split.  Outputs: verdict, visited (boxes bounded),
+ * depth_reached (the last level), nleaves (for nnsdp_crown_search_leaves), witness (xdims[0], written when violated), kernel_ms (may be
+ * NULL: event time of all launches).
+ * Device memory: 80 xdims[0] max_boxes bytes of frontiers (two of 2 max_boxes boxes) and, per box of max_boxes,
+ * 8 (4 + (2 + p) xdims[0] + p xdims[K]) + 4 (4 + p) bytes of records, points and leaf log (p = 2 with corner_points, else 1), allocated at
+ * the first search and reused by a later one that needs no more; the bound kernel's buffers grow with the
+ * levels and stop at one chunk (min(chunk, max_boxes) boxes), unless an earlier bound call made them larger.  Counted by
+ * nnsdp_crown_info.  On the host the handle keeps a pinned status record of four integers, a copy of its normals and the leaves of
+ * the last search.
+ * -1 with a message, before the GPU is touched and before anything is allocated: max_boxes < 1, chunk < 1, max_depth < 0, a null
+ * handle or argument, literal_bounds / corner_points on a handle without literals, normals given to a handle with literals, nlit that
+ * does not fit, a non-finite normal, threshold or box entry, x1min > x1max, frontiers above 2^31 bytes.  Not thread-safe. */
+typedef int32_t (*nnsdp_confirm_fn)(void* user, const double* x);
+int nnsdp_crown_search(nnsdp_crown* h, const double* x1min, const double* x1max, int32_t nlit, const double* normals, const double* hs,
+                       int32_t literal_bounds, int32_t corner_points, int32_t max_boxes, int32_t max_depth, int32_t chunk,
+                       nnsdp_confirm_fn confirm, void* user, int32_t* verdict, int32_t* visited, int32_t* depth_reached,
+                       int32_t* nleaves, double* witness, double* kernel_ms);
+
+/* The leaves of the handle's last search, in the order of the Python loop (HOST arrays of nleaves entries; lo / hi xdims[0] x nleaves
+ * column-major): proved 1 ("crown") or 0 (open); literal -1 for a box that the budget kept from being bounded (its bound is then
+ * meaningless), else the proved literal, or the best literal of an open box, with its bound. */
+int nnsdp_crown_search_leaves(nnsdp_crown* h, double* lo, double* hi, int32_t* depth, int32_t* proved, int32_t* literal, double* bound);
+
+/* what: 0 device allocations made so far, 1 network uploads so far, 2 box capacity, 3 sample capacity, 4 bound calls (a search counts
+ * one per chunk), 5 device bytes held. */
 int nnsdp_crown_info(nnsdp_crown* h, int32_t what, double* out);
 
 /* NULL is a no-op returning 0. */

@@ -26,6 +26,7 @@
 #include "forward.hpp"
 #include "crown_batch.hpp"
 #include "crown_alpha.hpp"
+#include "crown_search.hpp"
 
 namespace nnsdp {
 
@@ -2444,10 +2445,21 @@ struct nnsdp_crown {
   // nnsdp_crown_bound_alpha only (nothing before its first call): boxes then alpha0; the plain outputs then the alpha outputs; the state
   DBuf<double> dain, daout, dast;
   double *hain = nullptr, *haout = nullptr;
-  size_t box_cap = 0, sample_cap = 0, alpha_cap = 0;
+  size_t box_cap = 0, pin_cap = 0, sample_cap = 0, alpha_cap = 0;
   hipStream_t st = nullptr;
   hipEvent_t e0 = nullptr, e1 = nullptr;
   long long n_alloc = 0, n_upload = 0, n_bound = 0;
+  // nnsdp_crown_search only (nothing before its first call): the two frontiers (lo and hi of both, then the cuts of both), the
+  // per-level records / points / leaf log / clause, the status record's pinned copy; the result of the last search
+  std::vector<double> normals;           // the literals of the handle (ny x nlit), kept for the proof test of the search
+  DBuf<double> sfr, sdb;
+  DBuf<int> scu, sib;
+  int* hstatus = nullptr;
+  struct SearchLeaves {                  // flat, in the order of the Python loop; lo / hi n0 x nleaves column-major
+    std::vector<double> lo, hi, bound;
+    std::vector<int32_t> depth, proved, literal;
+    void clear() { lo.clear(); hi.clear(); bound.clear(); depth.clear(); proved.clear(); literal.clear(); }
+  } leaves;
 
   size_t scr_per_box() const { return (size_t)(activ == NNSDP_ACTIV_TANH ? 6 : 2) * acdim; }
   size_t out_per_box() const { return 4 * (size_t)acdim + 2 * (size_t)ny + 3 * (size_t)nlit + (size_t)nlit * n0; }
@@ -2466,15 +2478,21 @@ struct nnsdp_crown {
   }
   size_t device_bytes() const {
     return dxd.bytes() + dao.bytes() + dmo.bytes() + dM.bytes() + din.bytes() + dscr.bytes() + dout.bytes() + dX.bytes() + dY.bytes() +
-           dain.bytes() + daout.bytes() + dast.bytes();
+           dain.bytes() + daout.bytes() + dast.bytes() + sfr.bytes() + sdb.bytes() + scu.bytes() + sib.bytes();
   }
   // the capacity grows geometrically and never shrinks
-  void reserve_boxes(size_t nbox) {
-    if (nbox <= box_cap) return;
-    const size_t cap = std::max(nbox, 2 * box_cap);
-    dalloc(din, 2 * cap * n0); dalloc(dscr, cap * scr_per_box()); dalloc(dout, cap * out_per_box());
-    pinned(hin, 2 * cap * n0); pinned(hout, cap * out_per_box());
-    box_cap = cap;
+  // staging = false (a search: nothing of a box crosses the bus): the pinned copies wait for the next bound call
+  // limit: the geometric growth stops there (a search: one chunk); a call that needs more still gets it
+  void reserve_boxes(size_t nbox, bool staging = true, size_t limit = (size_t)-1) {
+    if (nbox > box_cap) {
+      const size_t cap = std::max(nbox, std::min(2 * box_cap, limit));
+      dalloc(din, 2 * cap * n0); dalloc(dscr, cap * scr_per_box()); dalloc(dout, cap * out_per_box());
+      box_cap = cap;
+    }
+    if (staging && pin_cap < box_cap) {
+      pinned(hin, 2 * box_cap * n0); pinned(hout, box_cap * out_per_box());
+      pin_cap = box_cap;
+    }
   }
   // the buffers of the alpha calls; the scratch is the plain calls' (reserve_boxes)
   void reserve_alpha(size_t nbox) {
@@ -2487,6 +2505,13 @@ struct nnsdp_crown {
     pinned(hain, cap * ain_per_box()); pinned(haout, cap * aout_per_box());
     alpha_cap = cap;
   }
+  // the buffers of a search: frontiers of `cap` boxes each, `nd` doubles and `ni` ints of records; they only grow
+  void reserve_search(size_t cap, size_t nd, size_t ni) {
+    if (4 * cap * n0 > sfr.n) { dalloc(sfr, 4 * cap * n0); scu.alloc(2 * cap * n0); ++n_alloc; }
+    if (nd > sdb.n) dalloc(sdb, nd);
+    if (ni > sib.n) { sib.alloc(ni); ++n_alloc; }
+    if (!hstatus) HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&hstatus), 4 * sizeof(int), hipHostMallocDefault));
+  }
   void reserve_samples(size_t N) {
     if (N <= sample_cap) return;
     const size_t cap = std::max(N, 2 * sample_cap);
@@ -2497,6 +2522,7 @@ struct nnsdp_crown {
   ~nnsdp_crown() {
     if (st) (void)hipStreamSynchronize(st);
     for (double* h : {hin, hout, hX, hY, hain, haout}) if (h) (void)hipHostFree(h);
+    if (hstatus) (void)hipHostFree(hstatus);
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
     if (st) (void)hipStreamDestroy(st);
@@ -3165,6 +3191,7 @@ int nnsdp_crown_create(int32_t K, const int32_t* xdims, const double* M, int32_t
   require_gpu();
   std::unique_ptr<nnsdp_crown> h(new nnsdp_crown);
   h->K = K; h->activ = activ; h->nlit = nlit; h->acdim = acoff[K - 1]; h->n0 = xd[0]; h->ny = xd[K]; h->wp = wp; h->moff = moff;
+  if (nlit > 0) h->normals.assign(normals, normals + (size_t)nlit * xd[K]);
   h->dxd.upload(xd); h->dao.upload(acoff); h->dmo.upload(moff);
   const size_t hlen = nlit > 0 ? (size_t)nlit * (xd[K - 1] + 1) : 0;      // the literal head H sits behind M
   h->dM.alloc(moff[K] + hlen);
@@ -3316,6 +3343,183 @@ int nnsdp_crown_eval(nnsdp_crown* h, int64_t N, const double* X, double* Y, doub
   HIPCHK(hipEventElapsedTime(&ms, h->e0, h->e1));
   if (kernel_ms) *kernel_ms = ms;
   std::copy(h->hY, h->hY + nyN, Y);
+  API_END
+}
+
+int nnsdp_crown_search(nnsdp_crown* h, const double* x1min, const double* x1max, int32_t nlit, const double* normals, const double* hs,
+                       int32_t literal_bounds, int32_t corner_points, int32_t max_boxes, int32_t max_depth, int32_t chunk,
+                       nnsdp_confirm_fn confirm, void* user, int32_t* verdict, int32_t* visited, int32_t* depth_reached,
+                       int32_t* nleaves, double* witness, double* kernel_ms) {
+  API_BEGIN
+  // (the scalar options come before the handle so that their refusals can be tested on a machine without a GPU, where no handle exists)
+  if (max_boxes < 1) throw std::invalid_argument("max_boxes must be >= 1, got " + std::to_string(max_boxes));
+  if (chunk < 1) throw std::invalid_argument("chunk must be >= 1, got " + std::to_string(chunk));
+  if (max_depth < 0) throw std::invalid_argument("max_depth must be >= 0, got " + std::to_string(max_depth));
+  if (!h) throw std::invalid_argument("null handle");
+  if (!x1min || !x1max || !hs || !verdict || !visited || !depth_reached || !nleaves || !witness) throw std::invalid_argument("null argument");
+  const int n0 = h->n0, ny = h->ny;
+  if (h->nlit > 0) {
+    if (normals) throw std::invalid_argument("the handle has literals of its own: normals must be NULL");
+    if (nlit != h->nlit) throw std::invalid_argument("nlit must be the handle's " + std::to_string(h->nlit) + ", got " + std::to_string(nlit));
+    normals = h->normals.data();
+  } else {
+    if (literal_bounds) throw std::invalid_argument("literal_bounds needs literals: the handle was created without normals");
+    if (corner_points) throw std::invalid_argument("corner_points needs literals: the handle was created without normals");
+    if (nlit < 1) throw std::invalid_argument("a clause needs at least one literal (nlit >= 1)");
+    check_literals(ny, nlit, normals);
+  }
+  for (int i = 0; i < nlit; ++i)
+    if (!std::isfinite(hs[i])) throw std::invalid_argument("literal " + std::to_string(i) + ": the threshold hs is not finite (NaN or infinity)");
+  unsigned long long splitmask = 0;
+  for (int t = 0; t < n0; ++t) {
+    if (!std::isfinite(x1min[t]) || !std::isfinite(x1max[t]) || !(x1min[t] <= x1max[t]))
+      throw std::invalid_argument("the root box: x1min must be <= x1max and both finite (no NaN, no infinity)");
+    if (x1max[t] > x1min[t]) splitmask |= 1ull << t;
+  }
+  // a level bounds at most max_boxes boxes and its children number at most twice that
+  const size_t mb = (size_t)max_boxes, cap = 2 * mb, npmax = corner_points ? 2 * mb : mb, logw = 2 * (size_t)n0 + 3;
+  const size_t frontier_bytes = 2 * cap * n0 * (2 * sizeof(double) + sizeof(int));
+  if (frontier_bytes > nnsdp::kSearchFrontierCap)
+    throw std::invalid_argument("max_boxes = " + std::to_string(max_boxes) + " needs " + std::to_string(frontier_bytes) +
+                                " bytes of frontier buffers, above the cap of 2^31 bytes");
+  // doubles: bound, points in, points out, leaf log, normals, hs;  ints: open, best, coord, slot, point flags, status
+  const size_t o_bound = 0, o_X = o_bound + mb, o_Y = o_X + npmax * n0, o_log = o_Y + npmax * ny, o_nrm = o_log + mb * logw,
+               o_hs = o_nrm + (size_t)nlit * ny, nd = o_hs + nlit;
+  const size_t ni = 4 * mb + npmax + 4;
+  const size_t cb = std::min((size_t)chunk, mb);
+  h->leaves.clear();
+  h->reserve_search(cap, nd, ni);
+  hipStream_t st = h->st;
+  double* D = h->sdb.p;
+  int* I = h->sib.p;
+  double *flo[2] = {h->sfr.p, h->sfr.p + 2 * cap * n0}, *fhi[2] = {flo[0] + cap * n0, flo[1] + cap * n0};
+  int* fcu[2] = {h->scu.p, h->scu.p + cap * n0};
+  HIPCHK(hipMemcpyAsync(flo[0], x1min, n0 * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(fhi[0], x1max, n0 * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemsetAsync(fcu[0], 0, n0 * sizeof(int), st));
+  HIPCHK(hipMemcpyAsync(D + o_nrm, normals, (size_t)nlit * ny * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(D + o_hs, hs, nlit * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPCHK(hipStreamSynchronize(st));      // (the sources are the caller's pageable arrays)
+
+  nnsdp::SearchArgs s;
+  s.n0 = n0; s.ny = ny; s.nlit = nlit; s.literal_bounds = literal_bounds != 0; s.corner_points = corner_points != 0;
+  s.splitmask = splitmask; s.normals = D + o_nrm; s.hs = D + o_hs;
+  s.open = I; s.best = I + mb; s.coord = I + 2 * mb; s.slot = I + 3 * mb; s.pflag = I + 4 * mb; s.status = I + 4 * mb + npmax;
+  s.bound = D + o_bound; s.X = D + o_X; s.Y = D + o_Y; s.log = D + o_log;
+  nnsdp::CrownArgs a;
+  a.K = h->K; a.xdims = h->dxd.p; a.moff = h->dmo.p; a.acoff = h->dao.p; a.M = h->dM.p; a.acdim = h->acdim;
+  a.nlit = h->nlit; a.H = h->dM.p + h->moff[h->K];      // (scratch and outputs: per level, reserve_boxes may move them)
+  nnsdp::FwdArgs f;
+  f.K = h->K; f.xdims = h->dxd.p; f.moff = h->dmo.p; f.M = h->dM.p; f.X = s.X; f.Y = D + o_Y; f.activ = h->activ; f.wp = h->wp;
+  const size_t fwd_lds = 2 * (size_t)h->wp * 16 * sizeof(double);
+
+  int cur = 0, nlevel = 1, nb = 0, vis = 0, depth = 0, verd = -1;
+  long long log_n = 0, log_before = 0;
+  double ms_all = 0.0;
+  std::vector<double> wit;
+  for (;;) {
+    nb = std::min(nlevel, max_boxes - vis);      // (>= 1: a level that uses the budget up is the last one)
+    vis += nb;
+    log_before = log_n;
+    h->reserve_boxes(std::min(cb, (size_t)nb), false, cb);      // (the stream is idle here: the bound kernel's buffers grow with the levels)
+    a.scratch = h->dscr.p;
+    s.nb = nb; s.depth = depth; s.lo = flo[cur]; s.hi = fhi[cur]; s.cuts = fcu[cur];
+    s.nlo = flo[cur ^ 1]; s.nhi = fhi[cur ^ 1]; s.ncuts = fcu[cur ^ 1]; s.log_base = log_n;
+    HIPCHK(hipEventRecord(h->e0, st));
+    for (int off = 0; off < nb; off += (int)cb) {
+      const size_t nc = std::min(cb, (size_t)(nb - off)), na = nc * h->acdim, ny_all = nc * ny, nl_all = nc * (size_t)h->nlit;
+      // the layout of nnsdp_crown_bound for nc boxes
+      a.lo = flo[cur] + (size_t)off * n0; a.hi = fhi[cur] + (size_t)off * n0;
+      a.acymin = h->dout.p; a.acymax = a.acymin + na; a.acxmin = a.acymin + 2 * na; a.acxmax = a.acymin + 3 * na;
+      a.ymin = a.acymin + 4 * na; a.ymax = a.ymin + ny_all;
+      a.smin = a.ymax + ny_all; a.smax = a.smin + nl_all; a.ub0 = a.smax + nl_all; a.uA = a.ub0 + nl_all;
+      if (h->activ == NNSDP_ACTIV_TANH)
+        hipLaunchKernelGGL(nnsdp::k_crown_resident<nnsdp::kCbTanh>, dim3((unsigned)nc), dim3(256), nnsdp::kCbLdsBytesTanh, st, a);
+      else
+        hipLaunchKernelGGL(nnsdp::k_crown_resident<nnsdp::kCbRelu>, dim3((unsigned)nc), dim3(256), nnsdp::kCbLdsBytes, st, a);
+      HIPCHK(hipGetLastError());
+      hipLaunchKernelGGL(nnsdp::k_search_classify, dim3((unsigned)cdiv((long long)nc, 256)), dim3(256), 0, st, s, off, (int)nc,
+                         (const double*)a.ymin, (const double*)a.ymax, (const double*)a.smax, (const double*)a.uA);
+      HIPCHK(hipGetLastError());
+      ++h->n_bound;
+    }
+    const long long npts = (long long)nb * (corner_points ? 2 : 1);
+    f.N = npts;
+    hipLaunchKernelGGL(nnsdp::k_forward_mfma, dim3((unsigned)((npts + 15) / 16)), dim3(64), fwd_lds, st, f);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(nnsdp::k_search_refute, dim3((unsigned)cdiv(npts, 256)), dim3(256), 0, st, s, npts);
+    HIPCHK(hipGetLastError());
+    const bool stop = vis >= max_boxes || depth >= max_depth || splitmask == 0;
+    hipLaunchKernelGGL(nnsdp::k_search_scan, dim3(1), dim3(256), 0, st, s, npts);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(nnsdp::k_search_scatter, dim3((unsigned)cdiv(nb, 256)), dim3(256), 0, st, s, stop ? 0 : 1);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(h->e1, st));
+    HIPCHK(hipMemcpyAsync(h->hstatus, s.status, 4 * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, h->e0, h->e1));
+    ms_all += ms;
+    const int nproved = h->hstatus[1], nopen = h->hstatus[2], ncand = h->hstatus[3];
+    if (h->hstatus[0] != nb || nproved + nopen != nb) throw std::runtime_error("nnsdp_crown_search: inconsistent status record");
+    log_n += nproved;
+    if (ncand > 0) {      // the level's flags and points, walked in the Python driver's order: the centres in box order, then the corners
+      std::vector<int> pf((size_t)npts);
+      std::vector<double> X((size_t)npts * n0);
+      HIPCHK(hipMemcpy(pf.data(), s.pflag, pf.size() * sizeof(int), hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(X.data(), s.X, X.size() * sizeof(double), hipMemcpyDeviceToHost));
+      for (long long p = 0; p < npts && wit.empty(); ++p)
+        if (pf[(size_t)p] && (!confirm || confirm(user, X.data() + (size_t)p * n0) != 0)) wit.assign(X.begin() + (size_t)p * n0, X.begin() + (size_t)(p + 1) * n0);
+    }
+    if (!wit.empty()) { verd = 1; break; }
+    if (nopen == 0) { verd = nb < nlevel ? 2 : 0; break; }
+    if (stop) { verd = 2; break; }
+    cur ^= 1; nlevel = 2 * nopen; ++depth;
+  }
+  // the leaves in the order of the Python loop: the log up to the last level, the boxes of the last level that the budget kept from
+  // being bounded, the last level's proved boxes, its open boxes
+  std::vector<double> log((size_t)log_n * logw), lo((size_t)nlevel * n0), hi((size_t)nlevel * n0), bnd((size_t)nb);
+  std::vector<int> open((size_t)nb), best((size_t)nb);
+  if (log_n) HIPCHK(hipMemcpy(log.data(), s.log, log.size() * sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(lo.data(), flo[cur], lo.size() * sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(hi.data(), fhi[cur], hi.size() * sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(bnd.data(), s.bound, bnd.size() * sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(open.data(), s.open, open.size() * sizeof(int), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(best.data(), s.best, best.size() * sizeof(int), hipMemcpyDeviceToHost));
+  nnsdp_crown::SearchLeaves& L = h->leaves;
+  const size_t nleaf = (size_t)log_n + (size_t)(nlevel - nb) + (size_t)h->hstatus[2];
+  L.lo.reserve(nleaf * n0); L.hi.reserve(nleaf * n0); L.depth.reserve(nleaf); L.proved.reserve(nleaf); L.literal.reserve(nleaf); L.bound.reserve(nleaf);
+  auto leaf = [&](const double* blo, const double* bhi, int d, int proved, int literal, double bound) {
+    L.lo.insert(L.lo.end(), blo, blo + n0); L.hi.insert(L.hi.end(), bhi, bhi + n0);
+    L.depth.push_back(d); L.proved.push_back(proved); L.literal.push_back(literal); L.bound.push_back(bound);
+  };
+  auto from_log = [&](long long r) {
+    const double* row = log.data() + (size_t)r * logw;
+    leaf(row, row + n0, (int)row[2 * n0], 1, (int)row[2 * n0 + 1], row[2 * n0 + 2]);
+  };
+  auto from_frontier = [&](int b, int literal, double bound) { leaf(lo.data() + (size_t)b * n0, hi.data() + (size_t)b * n0, depth, 0, literal, bound); };
+  for (long long r = 0; r < log_before; ++r) from_log(r);
+  for (int b = nb; b < nlevel; ++b) from_frontier(b, -1, 0.0);
+  for (long long r = log_before; r < log_n; ++r) from_log(r);
+  for (int b = 0; b < nb; ++b)
+    if (open[b]) from_frontier(b, best[b], bnd[b]);
+  *verdict = verd; *visited = vis; *depth_reached = depth; *nleaves = (int32_t)L.depth.size();
+  if (verd == 1) std::copy(wit.begin(), wit.end(), witness);
+  if (kernel_ms) *kernel_ms = ms_all;
+  API_END
+}
+
+int nnsdp_crown_search_leaves(nnsdp_crown* h, double* lo, double* hi, int32_t* depth, int32_t* proved, int32_t* literal, double* bound) {
+  API_BEGIN
+  if (!h) throw std::invalid_argument("null handle");
+  const nnsdp_crown::SearchLeaves& L = h->leaves;
+  if (!L.depth.empty() && (!lo || !hi || !depth || !proved || !literal || !bound)) throw std::invalid_argument("null argument");
+  std::copy(L.lo.begin(), L.lo.end(), lo);
+  std::copy(L.hi.begin(), L.hi.end(), hi);
+  std::copy(L.depth.begin(), L.depth.end(), depth);
+  std::copy(L.proved.begin(), L.proved.end(), proved);
+  std::copy(L.literal.begin(), L.literal.end(), literal);
+  std::copy(L.bound.begin(), L.bound.end(), bound);
   API_END
 }
 

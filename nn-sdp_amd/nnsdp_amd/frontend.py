@@ -366,6 +366,9 @@ def evalFeedFwdNetBatch(net: M.FeedFwdNet, X, return_ms: bool = False):
     return (Y.T, ms.value) if return_ms else Y.T
 
 
+_CONFIRM = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.POINTER(C.c_double))      # nnsdp_confirm_fn
+
+
 class CrownBounder:
     """makeIntervalsBatch(backend="gpu") and evalFeedFwdNetBatch for many calls on one network (the nnsdp_crown handle of include/nnsdp.h):
     the network, the literal head of `normals` (nlit x xdims[K], nlit <= 64) and every device buffer stay on the GPU until close().
@@ -443,6 +446,56 @@ class CrownBounder:
         ms = C.c_double(0.0)
         _lib.check(self._lib.nnsdp_crown_eval(h, N, Xc.ctypes.data_as(dp), Y.ctypes.data_as(dp), C.byref(ms)))
         return (Y.T, ms.value) if return_ms else Y.T
+
+    def search(self, lo, hi, hs, *, normals=None, literal_bounds: bool = False, corner_points: bool = False, max_boxes: int = 512,
+               max_depth: int = 24, chunk: int = 4096, confirm=None) -> dict:
+        """nnsdp_crown_search: the bounds-only bisection search of split.verifySplit on the root box lo / hi (xdims[0] each) for the clause
+        OR_i normal_i' f(x) <= hs[i], with the frontier kept on the GPU (csrc/crown_search.hpp).  The normals are the bounder's; a bounder
+        without normals takes `normals` (nlit x xdims[K]) and has neither literal_bounds nor corner_points.  confirm(x) -> bool decides
+        whether a point that the device flagged is a witness (None: the first flagged point is).  Returns the pieces of a SplitResult:
+        verdict, visited, depth, witness (or None), kernel_ms, and the leaves as arrays in the Python loop's order: lo, hi (nleaves x
+        xdims[0]), depth, proved (1 "crown", 0 open), literal (-1: never bounded), bound."""
+        h, dp, ip = self._handle(), _lib.c_double_p, _lib.c_int32_p
+        lo = np.ascontiguousarray(lo, dtype=np.float64)
+        hi = np.ascontiguousarray(hi, dtype=np.float64)
+        if lo.shape != (self._n0,) or hi.shape != (self._n0,):
+            raise ValueError("lo / hi must have xdims[0] entries")
+        hs = np.ascontiguousarray(hs, dtype=np.float64)
+        nrp = None
+        if normals is not None:
+            nrm = np.ascontiguousarray(normals, dtype=np.float64)               # nlit x ny row-major = ny x nlit column-major
+            if nrm.ndim != 2 or nrm.shape != (hs.size, self._ny):
+                raise ValueError("normals must be len(hs) x xdims[K]")
+            nrp = nrm.ctypes.data_as(dp)
+        if hs.ndim != 1 or hs.size < 1:
+            raise ValueError("hs must have one threshold per literal")
+        failed = []
+
+        def call(_user, x):
+            try:
+                return 1 if confirm(np.ctypeslib.as_array(x, shape=(self._n0,)).copy()) else 0
+            except BaseException as e:       # an exception cannot cross the C frames: the search ends at this level, it is raised again below
+                failed.append(e)
+                return 1
+
+        keep = _CONFIRM(call) if confirm is not None else None
+        cb = C.cast(keep, C.c_void_p) if keep is not None else None
+        out = (C.c_int32 * 4)()
+        wit, ms = np.zeros(self._n0), C.c_double(0.0)
+        _lib.check(self._lib.nnsdp_crown_search(h, lo.ctypes.data_as(dp), hi.ctypes.data_as(dp), hs.size, nrp, hs.ctypes.data_as(dp),
+                                                int(bool(literal_bounds)), int(bool(corner_points)), int(max_boxes), int(max_depth), int(chunk),
+                                                cb, None, *[C.cast(C.byref(out, 4 * k), ip) for k in range(4)],
+                                                wit.ctypes.data_as(dp), C.byref(ms)))
+        if failed:
+            raise failed[0]
+        verdict, visited, depth, n = (int(v) for v in out)
+        llo, lhi = np.zeros((n, self._n0)), np.zeros((n, self._n0))
+        ldepth, lproved, llit = (np.zeros(n, dtype=np.int32) for _ in range(3))
+        lbound = np.zeros(n)
+        _lib.check(self._lib.nnsdp_crown_search_leaves(h, llo.ctypes.data_as(dp), lhi.ctypes.data_as(dp), ldepth.ctypes.data_as(ip),
+                                                       lproved.ctypes.data_as(ip), llit.ctypes.data_as(ip), lbound.ctypes.data_as(dp)))
+        return dict(verdict=("holds", "violated", "unknown")[verdict], visited=visited, depth=depth, witness=wit if verdict == 1 else None,
+                    kernel_ms=ms.value, lo=llo, hi=lhi, leaf_depth=ldepth, proved=lproved, literal=llit, bound=lbound)
 
     def info(self) -> dict:
         h, v, out = self._handle(), C.c_double(0.0), {}

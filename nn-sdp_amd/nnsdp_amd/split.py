@@ -62,6 +62,14 @@ class SplitOptions:
     alpha_eta0: float = 0.5
     alpha_decay: float = 0.9
     alpha_inherit: bool = False
+    # where the frontier of open boxes lives: "host" (the Python loop below), or "device": the level loop of a bounds-only search runs on
+    # the CrownBounder's stream with the boxes, the proof test, the refutation points, the bisection and the leaf log in device memory
+    # (CrownBounder.search, csrc/crown_search.hpp); the same SplitResult bit for bit.  Needs crown_backend "resident", samples = 0 and
+    # alpha_steps = 0.  With sdp_per_level > 0 the SDPs run once, on the open leaves of a search that ended "unknown".
+    # SplitResult.seconds then has one more key, "kernel": the HIP-event time of the search's launches (tools/split_timing.py reads it).
+    # chunk: boxes per launch of the bound kernel, which bounds the device memory of a level's interval arrays
+    frontier: str = "host"
+    chunk: int = 4096
 
 
 @dataclass
@@ -175,6 +183,15 @@ def verifySplit(net: M.FeedFwdNet, x1min, x1max, literals: Sequence[Tuple[Any, f
             raise ValueError("alpha_steps > 0 needs crown_backend 'host' or 'resident'")
         if M._activ_code(net.activ) != M.ACTIV_RELU:
             raise ValueError("alpha_steps > 0 is for ReLU networks")
+    if split.frontier not in ("host", "device"):
+        raise ValueError("frontier must be 'host' or 'device'")
+    if split.frontier == "device":
+        if split.crown_backend != "resident":
+            raise ValueError("frontier 'device' needs crown_backend 'resident'")
+        if split.samples != 0:
+            raise ValueError("frontier 'device' needs samples == 0")
+        if split.alpha_steps != 0:
+            raise ValueError("frontier 'device' needs alpha_steps == 0")
     t_start = time.perf_counter()
     root_lo, root_hi = np.array(x1min, dtype=np.float64), np.array(x1max, dtype=np.float64)
     n0, ny = net.xdims[0], net.xdims[-1]
@@ -191,10 +208,53 @@ def verifySplit(net: M.FeedFwdNet, x1min, x1max, literals: Sequence[Tuple[Any, f
     want_lits = split.literal_bounds or split.corner_points
     bounder = F.CrownBounder(net, normals if want_lits else None) if split.crown_backend == "resident" else None
     try:
+        if split.frontier == "device":
+            return _split_device(net, root_lo, root_hi, normals, hs, beta, opts, split, bounder, want_lits, seconds, t_start)
         return _split_levels(net, frontier, root_lo, root_hi, normals, hs, beta, opts, split, bounder, seconds, t_start)
     finally:
         if bounder is not None:
             bounder.close()
+
+
+def _split_device(net, root_lo, root_hi, normals, hs, beta, opts, split, bounder, want_lits, seconds, t_start) -> SplitResult:
+    """verifySplit with frontier = "device": one CrownBounder.search, then (sdp_per_level > 0 and the search ended "unknown") one SDP
+    stage on its bounded open leaves, as step 3 of _split_levels does on a level"""
+    t0 = time.perf_counter()
+    r = bounder.search(root_lo, root_hi, hs, normals=None if want_lits else normals, literal_bounds=split.literal_bounds,
+                       corner_points=split.corner_points, max_boxes=int(split.max_boxes), max_depth=int(split.max_depth),
+                       chunk=int(split.chunk), confirm=lambda x: bool(_violates_all(F.evalFeedFwdNet(net, x)[:, None], normals, hs)[0]))
+    seconds["crown"] += time.perf_counter() - t0
+    seconds["kernel"] = 1e-3 * r["kernel_ms"]
+    leaves = []
+    for k in range(len(r["proved"])):
+        lit = int(r["literal"][k])
+        leaves.append(Leaf(r["lo"][k].copy(), r["hi"][k].copy(), int(r["leaf_depth"][k]), "crown" if r["proved"][k] else None,
+                           lit if lit >= 0 else None, float(r["bound"][k]) if lit >= 0 else None))
+    verdict, sdp_solves = r["verdict"], 0
+    todo = [k for k, lf in enumerate(leaves) if lf.proved_by is None and lf.literal is not None]
+    if verdict == "unknown" and split.sdp_per_level > 0 and todo:
+        t0 = time.perf_counter()
+        lo, hi = np.stack([leaves[k].lo for k in todo], axis=1), np.stack([leaves[k].hi for k in todo], axis=1)
+        iv = bounder.bound(lo, hi)
+        if want_lits:
+            iv = tuple(iv[:-1])
+        seconds["crown"] += time.perf_counter() - t0
+        order = sorted(range(len(todo)), key=lambda b: (leaves[todo[b]].bound - hs[leaves[todo[b]].literal], b))[:int(split.sdp_per_level)]
+        # (_solve_boxes reads lo and hi of a box, never its cuts)
+        boxes = [(_Box(leaves[todo[b]].lo, leaves[todo[b]].hi, None), tuple(a[:, b] for a in iv)) for b in order]
+        got = _solve_boxes(net, boxes, normals, hs, beta, opts, split.batch, seconds)
+        sdp_solves = len(order) * len(hs)
+        for b, res in zip(order, got):
+            for li, (s, h0) in enumerate(res):
+                rho = float(s.objective_value) + h0
+                if s.termination_status == "TARGET_CERTIFIED" and V.isSolutionGood(s) and rho <= hs[li]:
+                    lf = leaves[todo[b]]
+                    leaves[todo[b]] = Leaf(lf.lo, lf.hi, lf.depth, "sdp", li, rho, s)
+                    break
+        if all(lf.proved_by is not None for lf in leaves):
+            verdict = "holds"
+    seconds["total"] = time.perf_counter() - t_start
+    return SplitResult(verdict, leaves, r["witness"], r["visited"], sdp_solves, seconds)
 
 
 def _split_levels(net, frontier, root_lo, root_hi, normals, hs, beta, opts, split, bounder, seconds, t_start) -> SplitResult:

@@ -1,6 +1,11 @@
 #!/usr/bin/env python3
 """Batched CROWN bounds: the GPU kernel against the host routine, and where one verifySplit spends its time.
-usage: python tools/split_timing.py [--nlit | --resident | --alpha] [case ...]   cases: W10-D5 W40-D20 acas-shape   (default: all)
+usage: python tools/split_timing.py [--nlit | --resident | --alpha | --frontier] [case ...]   cases: W10-D5 W40-D20 acas-shape   (default: all)
+With --frontier only the frontier leg runs and profiles/split_timing_frontier_<case>.json is written:
+  split    one bounds-only verifySplit (crown_backend "resident", literal_bounds, max_boxes 16384) of the literal
+           y_0 - y_last <= s + f (c0 - s) with frontier "host" and then "device" in this process; f is the first of 0.25, 0.1, 0.05, 0.02 at
+           which the host frontier visits at least 1 000 boxes, else the one with the most boxes visited.  Median of 5 runs after 1 warm
+           run: total seconds, seconds["crown"], and for the device frontier the HIP-event time of its kernels; visited and levels
 With --alpha only the optimised-slope leg runs and profiles/split_timing_alpha_<case>.json is written:
   bound    CrownBounder.bound at nbox = 256 with alpha_steps 0, 4 and 8 and 1 and 10 literals: wall-clock of the call and HIP-event time of
            its kernels (the plain one, and k_crown_alpha behind it when alpha_steps > 0), median of 7 after 2 warm calls
@@ -163,6 +168,37 @@ def alpha_rows(net, lo, hi, nbox=256):
     return dict(bound=bound, host=host, sampled_max=s, root_plain_smax=c0, h=h, split=split)
 
 
+def frontier_rows(net, lo, hi, max_boxes=16384):
+    nrm = np.zeros(net.xdims[-1]); nrm[0] = 1.0; nrm[-1] -= 1.0
+    X = lo[:, None] + np.random.default_rng(0).random((len(lo), 20000)) * (hi - lo)[:, None]
+    s = float((nrm @ na.evalFeedFwdNetBatch(net, X)).max())
+    iv = na.makeIntervalsBatch(net, lo[:, None], hi[:, None], backend="gpu")
+    c0 = float(np.maximum(nrm * iv[4][:, 0], nrm * iv[5][:, 0]).sum())
+
+    def run(f, frontier):
+        return na.verifySplit(net, lo, hi, [(nrm, s + f * (c0 - s))], 0, na.AdmmSdpOptions(),
+                              na.SplitOptions(max_boxes=max_boxes, sdp_per_level=0, crown_backend="resident", literal_bounds=True, frontier=frontier))
+
+    tried = {}
+    for f in (0.25, 0.1, 0.05, 0.02):
+        tried[f] = run(f, "host").visited
+        if tried[f] >= 1000:
+            break
+    f = f if tried[f] >= 1000 else max(tried, key=tried.get)
+    out = dict(sampled_max=s, root_cheap_bound=c0, f=f, h=s + f * (c0 - s), max_boxes=max_boxes, host_visited_per_f={str(k): v for k, v in tried.items()})
+    for frontier in ("host", "device"):
+        runs = [run(f, frontier) for _ in range(6)][1:]
+        r = runs[0]
+        row = dict(verdict=r.verdict, visited=r.visited, leaves=len(r.leaves), levels=1 + max(lf.depth for lf in r.leaves),
+                   total_s_median=statistics.median(q.seconds["total"] for q in runs), crown_s_median=statistics.median(q.seconds["crown"] for q in runs))
+        if frontier == "device":
+            row["kernel_s_median"] = statistics.median(q.seconds["kernel"] for q in runs)
+        out[frontier] = row
+        print(frontier, row, flush=True)
+    out["host_over_device_total"] = out["host"]["total_s_median"] / out["device"]["total_s_median"]
+    return out
+
+
 def split_row(net, lo, hi):
     nrm = np.zeros(net.xdims[-1]); nrm[0] = 1.0
     X = lo[:, None] + np.random.default_rng(0).random((len(lo), 20000)) * (hi - lo)[:, None]
@@ -183,12 +219,16 @@ def split_row(net, lo, hi):
 
 if __name__ == "__main__":
     args = sys.argv[1:]
-    lit_leg, res_leg, alpha_leg = "--nlit" in args, "--resident" in args, "--alpha" in args
-    names = [a for a in args if a not in ("--nlit", "--resident", "--alpha")] or ["W10-D5", "W40-D20", "acas-shape"]
+    lit_leg, res_leg, alpha_leg, frontier_leg = "--nlit" in args, "--resident" in args, "--alpha" in args, "--frontier" in args
+    names = [a for a in args if a not in ("--nlit", "--resident", "--alpha", "--frontier")] or ["W10-D5", "W40-D20", "acas-shape"]
     out_dir = os.environ.get("SPLIT_TIMING_OUT", os.path.join(ROOT, "profiles"))
     os.makedirs(out_dir, exist_ok=True)
     for name in names:
         net, lo, hi = case(name)
+        if frontier_leg:
+            with open(os.path.join(out_dir, f"split_timing_frontier_{name}.json"), "w") as fh:
+                json.dump(dict(case=name, xdims=net.xdims, **frontier_rows(net, lo, hi)), fh, indent=1)
+            continue
         if alpha_leg:
             with open(os.path.join(out_dir, f"split_timing_alpha_{name}.json"), "w") as fh:
                 json.dump(dict(case=name, xdims=net.xdims, **alpha_rows(net, lo, hi)), fh, indent=1)
