@@ -20,7 +20,7 @@
 // uA x + ub0 is written out beside them (smax = uA c + |uA| r + ub0).  Every output element of the product is its own dot product
 // and the row passes are per row, so a literal's bits do not depend on the other literals of the call.
 //
-// Resident kernel (k_crown_resident<ACT>, launched by the nnsdp_crown handle of api.hip on buffers the handle keeps): the same passes
+// Resident kernel (k_crown_resident<ACT>, launched by the nnsdp_crown handle of crown_handle.hpp on its own buffers): the same passes
 // as a template on the activation.  ACT = kCbRelu is the arithmetic above, operation for operation.  ACT = kCbTanh restates
 // tanh_relax / crown_backward(..., tanh_act = true) of intervals.hpp in fp64: the relaxation  lw x + lb <= tanh(x) <= uw x + ub  of
 // a layer is computed ONCE, by the pre-activation pass that produces the layer's bounds (threads tid < nout, right after l, u go to
@@ -30,6 +30,13 @@
 // (kCbLdsBytesTanh), still two workgroups per CU.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <stdexcept>
+#include <string>
+#include <vector>
 
 namespace nnsdp {
 
@@ -58,6 +65,70 @@ static constexpr int kCbChunk = 8;     // k-steps whose weight operands are in f
 static constexpr size_t kCbLdsBytes = (2 * kCbW * kCbW + 8 * kCbW) * sizeof(double);
 static constexpr size_t kCbLdsBytesTanh = kCbLdsBytes + kCbW * sizeof(double);      // + the lower relaxation's bias
 static constexpr int kCbRelu = 0, kCbTanh = 1;      // the values of NNSDP_ACTIV_RELU / NNSDP_ACTIV_TANH
+
+// ---- host side: the layouts the kernels of this file and of forward.hpp are launched on, each stated once ----
+
+// A network given as (K, xdims): what CrownArgs / FwdArgs call xdims, moff, acoff and wp.  Arithmetic only - the entries refuse K, null
+// pointers and widths themselves, before they build this (their messages and the order of their refusals differ).
+struct NetLayout {
+  std::vector<int> xd, acoff;
+  std::vector<long long> moff;
+  int wp = 0;               // FwdArgs::wp
+  NetLayout(int K, const int32_t* xdims) : xd(xdims, xdims + K + 1), acoff(K, 0), moff(K + 1, 0) {
+    for (int k = 0; k < K; ++k) {
+      moff[k + 1] = moff[k] + (long long)xd[k + 1] * (xd[k] + 1);
+      if (k > 0) acoff[k] = acoff[k - 1] + xd[k];
+      wp = std::max(wp, (xd[k] + 1 + 3) & ~3);
+    }
+  }
+  int K() const { return (int)acoff.size(); }
+  int n0() const { return xd.front(); }
+  int ny() const { return xd.back(); }
+  int acdim() const { return acoff.back(); }
+  size_t mlen() const { return (size_t)moff.back(); }
+  // the literal head H = [C W_{K-1} | C b_{K-1}] sits behind M
+  size_t head_len(int nlit) const { return nlit > 0 ? (size_t)nlit * (xd[K() - 1] + 1) : 0; }
+};
+
+// the refusal of a box that is empty or not finite, shared by the entries that bound many boxes (lo, hi: n0 x nbox, column-major)
+inline void check_boxes(long long nbox, int n0, const double* lo, const double* hi) {
+  for (long long b = 0; b < nbox; ++b)
+    for (int i = 0; i < n0; ++i)
+      if (!std::isfinite(lo[b * n0 + i]) || !std::isfinite(hi[b * n0 + i]) || !(lo[b * n0 + i] <= hi[b * n0 + i]))
+        throw std::invalid_argument("box " + std::to_string(b) + ": x1min must be <= x1max and both finite (no NaN, no infinity)");
+}
+
+// The kernel's outputs for nbox boxes, packed so that one copy brings everything back: ten segments in the order
+//   acymin | acymax | acxmin | acxmax | ymin | ymax | smin | smax | ub0 | uA
+// The alpha kernel (crown_alpha.hpp) appends  a_smax | a_ub0 | a_step | a_uA | alpha  and keeps three nst()-long state arrays.
+struct CrownLayout {
+  size_t nbox, n0, acdim, ny, nlit;
+  static constexpr int kSegs = 10;
+  size_t na() const { return nbox * acdim; }
+  size_t ny_all() const { return nbox * ny; }
+  size_t nl() const { return nbox * nlit; }
+  size_t nA() const { return nl() * n0; }
+  size_t nst() const { return nl() * acdim; }
+  void lens(size_t* len) const {
+    const size_t l[kSegs] = {na(), na(), na(), na(), ny_all(), ny_all(), nl(), nl(), nl(), nA()};
+    std::copy(l, l + kSegs, len);
+  }
+  size_t total() const { return 4 * na() + 2 * ny_all() + 3 * nl() + nA(); }
+  size_t alpha_total() const { return total() + 3 * nl() + nA() + nst(); }
+  // the output pointers of `a` into a buffer of total() doubles, with the two counts the kernel reads of the layout
+  void point(CrownArgs& a, double* base) const {
+    a.acdim = (int)acdim; a.nlit = (int)nlit;
+    a.acymin = base; a.acymax = a.acymin + na(); a.acxmin = a.acymax + na(); a.acxmax = a.acxmin + na();
+    a.ymin = a.acxmax + na(); a.ymax = a.ymin + ny_all();
+    a.smin = a.ymax + ny_all(); a.smax = a.smin + nl(); a.ub0 = a.smax + nl(); a.uA = a.ub0 + nl();
+  }
+  // n consecutive segments of a host copy `src` to the caller's arrays; a null pointer skips its segment.  Returns the end in src.
+  static const double* copy_segments(const double* src, int n, const size_t* len, double* const* host) {
+    for (int o = 0; o < n; src += len[o], ++o)
+      if (host[o]) std::copy(src, src + len[o], host[o]);
+    return src;
+  }
+};
 
 __device__ __forceinline__ int cb_idx(int t, int i) { return t * kCbW + (i ^ ((t & 1) << 4)); }
 

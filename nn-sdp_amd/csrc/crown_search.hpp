@@ -1,4 +1,4 @@
-// Device-resident frontier of the bounds-only split search (nnsdp_crown_search of api.hip; nnsdp_amd/split.py with frontier = "device").
+// Device-resident frontier of the bounds-only split search (nnsdp_crown::search of crown_handle.hpp; nnsdp_amd/split.py with frontier = "device").
 // The level loop of split.py (_split_levels) with the boxes kept in device memory: per level the host launches, per chunk of the
 // level, the handle's bound kernel (k_crown_resident, csrc/crown_batch.hpp, its lo / hi pointers offset into the frontier) and
 // k_search_classify on the chunk's outputs; then k_forward_mfma on the level's points, k_search_refute, k_search_scan and

@@ -92,4 +92,14 @@ __global__ __launch_bounds__(64) void k_forward_mfma(FwdArgs a) {
   }
 }
 
+// ---- host side: the one launch of the kernel (the caller checks hipGetLastError) ----
+// LDS: two buffers of wp x 16 doubles; above 64 KB the caller raises the kernel's dynamic limit first
+inline size_t fwd_lds_bytes(int wp) { return 2 * (size_t)wp * 16 * sizeof(double); }
+inline void launch_forward(int K, const int* xdims, const long long* moff, const double* M, const double* X, double* Y, long long N,
+                           int activ, int wp, hipStream_t st) {
+  FwdArgs a;
+  a.K = K; a.xdims = xdims; a.moff = moff; a.M = M; a.X = X; a.Y = Y; a.N = N; a.activ = activ; a.wp = wp;
+  hipLaunchKernelGGL(k_forward_mfma, dim3((unsigned)((N + 15) / 16)), dim3(64), fwd_lds_bytes(wp), st, a);
+}
+
 }  // namespace nnsdp

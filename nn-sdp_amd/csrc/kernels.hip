@@ -112,7 +112,7 @@ struct ProjArgs {
   int gram_credit;        // visits a block may run without the Gram product after a visit that measured it (0 .. 15)
   int refine_pivots;      // exact rotations of the dominant pair first order cannot resolve, per visit (0 = off)
   double refine_loose;    // >= 1: the one-off acceptance level of an isolated near miss, as a multiple of refine_acc (1 = off)
-  double refine_k2cap;    // a step is only taken when |K|_F^2 is below this (0.09: |K|_F <= 0.3; see api.hip, refine_k2cap)
+  double refine_k2cap;    // a step is only taken when |K|_F^2 is below this (0.09: |K|_F <= 0.3; see RefineTuning of solver.hpp)
   int max_sweeps;
   double tol;             // stop after a sweep that started with off(A)/|A|_F <= tol (quadratic convergence: it ends near tol^2)
   const int* pmode;       // per block, may be null: != 0 = the tile-parallel pipeline launched in front (refine_pipe.hpp) has already

@@ -200,7 +200,7 @@ def build_operator(q: Query, mode: str = "single", normalize: bool = False, merg
     normalize=True : the solver's internal coordinates (Congruence above); generators whose
     image vanishes (e.g. gac1 of an eliminated neuron) become zero columns.
     merge_identical: keep one block per distinct index set (first occurrence), as the library does
-    (csrc/api.hip reduced_cliques: a sum of NSD matrices on one index set is NSD)."""
+    (csrc/solver.hpp reduced_cliques: a sum of NSD matrices on one index set is NSD)."""
     net = q.net
     Zdim = net.Zdim
     a = Zdim - 1

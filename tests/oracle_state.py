@@ -154,7 +154,7 @@ def case_query(key: str):
 
 @functools.lru_cache(maxsize=None)
 def case_operator(key: str):
-    """the library merges identical index sets into one block (csrc/api.hip reduced_cliques); so does the harness"""
+    """the library merges identical index sets into one block (csrc/solver.hpp reduced_cliques); so does the harness"""
     return oop.build_operator(mirror_query(case_query(key)), CASES[key][1], normalize=True, merge_identical=True)
 
 

@@ -32,6 +32,9 @@ def test_create_refuses_bad_arguments_before_the_gpu():
     assert rc == -1 and "K >= 2" in msg
     rc, msg = _create([2, 65, 2], np.zeros(65 * 3 + 2 * 66), 1)
     assert rc == -1 and "65" in msg and "64" in msg
+    for widths in ([2, 0, 2], [0, 65, 2]):             # an empty layer; the first bad width is the one named
+        rc, msg = _create(widths, M3, 0)
+        assert rc == -1 and "layer widths must be >= 1" in msg
     rc, msg = _create([2, 3, 2], M3, 7)
     assert rc == -1 and "activation" in msg
     rc, msg = _create([2, 3, 2], M3, 1, 65, np.zeros((65, 2)))

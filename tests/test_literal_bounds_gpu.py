@@ -195,6 +195,9 @@ def _refusals():
     assert rc < 0 and "Tanh" in msg
     rc, msg = _raw([2, 65, 2], np.zeros(65 * 3 + 2 * 66), 0, 4, lo, hi, 3, nrm)
     assert rc < 0 and "65" in msg and "64" in msg
+    for widths in ([2, 0, 2], [0, 65, 2]):             # an empty layer; the first bad width is the one named
+        rc, msg = _raw(widths, M3, 0, 4, lo, hi, 3, nrm)
+        assert rc < 0 and "layer widths must be >= 1" in msg
     bad = hi.copy()
     bad[2, 1] = -1.0
     rc, msg = _raw([2, 3, 2], M3, 0, 4, lo, bad, 3, nrm)

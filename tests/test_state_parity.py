@@ -143,7 +143,7 @@ def test_full_loop_with_sigma_adaptation_tracks_oracle(key):
     gam = np.concatenate([s.values[k] for k in ("γin", "γout", "γac1", "γac2")])
     keep = ost.trajectory(key).P.keep
     # the box multipliers of coordinates the normalisation eliminated have no column in the solver; the library raises them to
-    # 100^t max(1, max gamma) in the returned certificate (csrc/api.hip certificate(), "large enough"), the oracle leaves them 0
+    # 100^t max(1, max gamma) in the returned certificate (csrc/solver.hpp certificate(), "large enough"), the oracle leaves them 0
     dropped = np.setdiff1d(np.arange(len(gam)), keep)
     assert np.all((gam[dropped] == 0.0) | (gam[dropped] >= 100.0 * max(1.0, gam[keep].max()))), key
     tol = 1e-8 * np.abs(r.gamma).max()
