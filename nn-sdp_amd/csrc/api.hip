@@ -807,8 +807,11 @@ int nnsdp_project_psd_warm_state(int32_t batch, const int32_t* n, const double* 
   a.refine = refine; a.rstate = drs.p;
   RefineTuning::from_env().bind(a);
   SplitScratch split;
-  // (test hook) two workgroups per block, as a solver's warm launches run
-  if (env_flag("NNSDP_SPLIT_WARM") && plan.split_ok() && batch <= 120) { split.alloc(batch); split.bind(a, batch); }
+  // (test hook) NNSDP_SPLIT_WARM=<H>: H helper workgroups per block, as a solver's warm launches run
+  if (plan.split_ok() && batch <= 120) {
+    const int helpers = split_cap((int)env_int("NNSDP_SPLIT_WARM", 0), batch);
+    if (helpers > 0) { split.alloc(batch, helpers); split.bind(a, batch); }
+  }
   EventPair ev;
   ev.create();
   HIPCHK(hipEventRecord(ev.e0, nullptr));
@@ -830,7 +833,7 @@ int nnsdp_project_psd_warm_state(int32_t batch, const int32_t* n, const double* 
   float ms = 0;
   HIPCHK(hipEventElapsedTime(&ms, ev.e0, ev.e1));
   if (kernel_ms) *kernel_ms = ms;
-  if (split.failed()) throw HipError("projection kernel, two workgroups per block: a helper workgroup did not deliver its tiles in time");
+  if (split.failed()) throw HipError("projection kernel, helper workgroup(s): a helper did not deliver its tiles in time");
   {
     std::vector<unsigned char> gb(kGuard * sizeof(double));
     const char* names[] = {"nu", "w", "V", "T scratch", "U scratch"};

@@ -16,7 +16,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include <algorithm>
 #include <type_traits>
+#include "split_deal.hpp"
 
 namespace nnsdp {
 
@@ -117,21 +119,20 @@ struct ProjArgs {
   double tol;             // stop after a sweep that started with off(A)/|A|_F <= tol (quadratic convergence: it ends near tol^2)
   const int* pmode;       // per block, may be null: != 0 = the tile-parallel pipeline launched in front (refine_pipe.hpp) has already
                           // projected this block in this iteration; the workgroup returns at once
-  // two workgroups per block for the warm-start congruence (ping-pong variant, warm launches of one SDP; launch_proj): the grid is
-  // 2 x nblk - workgroups [0, nblk) are HELPERS (they never wait: dispatched first, they always finish), [nblk, 2 nblk) LEADERS.  Both
-  // load the block; each computes the tile columns of T = A V and of B = V'T it owns (same instruction sequence per tile as the
-  // one-workgroup form: identical bits); the helper leaves its tiles of B in `sB` behind a release of `sack[k]` and exits, the leader
-  // takes them after its own and goes on alone.  sack / sseen count the exchanges per block (device-resident: replayed graphs need no
+  // 1 + split workgroups per block for the warm-start congruence (ping-pong variant, warm launches of one SDP; launch_proj): with
+  // nb8 = nblk rounded up to 8 the grid is split x nb8 + nblk - helper h = 1 .. split of block k runs at workgroup (h - 1) nb8 + k (the
+  // HELPERS never wait: dispatched first, they always finish), its LEADER at split x nb8 + k.  All load the block; each computes the tile
+  // columns of T = A V and of B = V'T it owns (split_cols of split_deal.hpp; same instruction sequence per tile as the one-workgroup
+  // form: identical bits); a helper leaves its tiles of B in `sB` behind a release of `sack[k]` and exits, the leader takes them after
+  // its own and goes on alone.  sack / sseen count the helpers' hand-overs per block (device-resident: replayed graphs need no
   // per-launch argument); a wait that runs out sets *serr (the solve ends with NUMERICAL_ERROR at its next check).
-  int split, nblk;
+  int split, nblk;        // split: helpers per block (0: one workgroup per block; a block of nt tile columns uses split_helpers(nt, split))
   double* sB;             // nblk x kSplitTileDoubles
-  unsigned* sack;         // per block: exchanges completed by the helper
-  unsigned* sseen;        // per block: exchanges consumed by the leader
-  unsigned* sxcc;         // per block: the XCD the helper ran on (diagnostic)
+  unsigned* sack;         // per block: hand-overs completed by its helpers (one atomic add each)
+  unsigned* sseen;        // per block: hand-overs consumed by the leader
   int* serr;
   long long spin_limit;
 };
-static constexpr int kHwRegXccId = (3 << 11) | 20;     // s_getreg: 4 bits at offset 0 of HW_REG_XCC_ID (20): the XCD a wave runs on
 static constexpr int kSplitTileDoubles = 96 * 96;      // tile-ordered storage of one block's B (6 x 6 tiles of 256 doubles)
 
 // element (i,j) of the symmetric LDS matrix, lower triangle is the only copy that is kept current
@@ -290,9 +291,10 @@ __device__ __forceinline__ void proj_lower_tile(const int t, const int ntl, int&
   if (t < ntl) { ti = 0; while ((ti + 1) * (ti + 2) / 2 <= t) ++ti; tj = t - ti * (ti + 1) / 2; }
 }
 
-// leader of a split block: waits (thread 0 polls) until the helper has released the block's next exchange; returns its number
-__device__ __forceinline__ unsigned proj_await_helper(const ProjArgs& a, const int k, const int tid) {
-  const unsigned want = a.sseen[k] + 1u;
+// leader of a split block: waits (thread 0 polls) until all `nhelp` helpers with a share of the block (split_helpers) have released
+// their hand-over; returns the count the leader records in sseen afterwards.  ONE acquire, however many helpers
+__device__ __forceinline__ unsigned proj_await_helper(const ProjArgs& a, const int k, const int tid, const int nhelp) {
+  const unsigned want = a.sseen[k] + (unsigned)nhelp;
   if (tid == 0) {
     long long spins = 0;
     while (__hip_atomic_load(a.sack + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < want) {
@@ -590,7 +592,7 @@ __device__ __forceinline__ void proj_rescale_store(const ProjBlock& b, const Pro
 // ALG = 2: register-resident systolic sweeps (below).  SPW = pair slots (2 matrix rows each) per wave, RPW = eigenvector
 // rows per wave; NT/64 * SPW >= ceil(n/2) and NT/64 * RPW >= n + 1 for every block of the launch.
 template <bool V_LDS, int NT, int ALG = 0, int SPW = 1, int RPW = 1>
-__device__ __forceinline__ void proj_body(const ProjArgs& a, const int k, const int role = 0) {      // role: 0 alone, 1 leader, 2 helper (ProjArgs::split)
+__device__ __forceinline__ void proj_body(const ProjArgs& a, const int k, const int role = 0, const int hidx = 0) {      // role: 0 alone, 1 leader, 2 helper number hidx (ProjArgs::split)
   constexpr bool SYS = ALG == 2;
   constexpr bool PP = ALG == 3;
   // ALG = 4: blocks 129 .. 160 (the reference's 151-wide cliques of width-50 networks, chordal_cliques.jl:33-36).  The full matrix does
@@ -606,6 +608,9 @@ __device__ __forceinline__ void proj_body(const ProjArgs& a, const int k, const 
   const int np = (n + 1) & ~1;   // Jacobi dimension (even)
   const int npg = (n + 15) & ~15;  // storage / MFMA dimension (multiple of 16; zero rows, identity in V)
   const int half = np >> 1;
+  // split block: a helper without a share returns in front of the load.  (The deal - split_cols, split_helpers - is worked out again
+  // where it is used, not kept: the 1024-thread variants have no register to spare for a value that lives through the sweeps)
+  if (role == 2 && split_cols(npg >> 4, a.split, hidx) == 0u) return;
   // (ping-pong sweeps keep a one-cell border around the matrix: 2 more rows / columns of storage)
   const int lda = PP ? kPpLda : npg + 1;    // odd stride (in doubles): column walks hit distinct banks; a constant for the ping-pong variant (immediate LDS offsets)
   const int nrow = PP ? npg + 2 : npg;      // rows of LDS storage per matrix
@@ -712,16 +717,16 @@ __device__ __forceinline__ void proj_body(const ProjArgs& a, const int k, const 
     // A <- V' A V with v_mfma_f64_16x16x4_f64: T = A V (all 16x16 tiles), then A' = V' T (lower tiles; the
     // Jacobi sweeps read the lower triangle only).  Operand maps (verified on gfx950): lane l holds
     // A[l&15][l>>4], B[l>>4][l&15]; result reg r of lane l is C[(l>>4) + 4r][l&15].
-    // part: 0 = the whole product; 1 / 2 = the leader's / the helper's tile columns of a split block (helper: columns 1 .. hc,
-    // leader: 0 and hc + 1 .. nt - 1; nt = 6: helper 12 tiles of T and 9 of B, leader 24 and 12)
+    // part: 0 = the whole product; 1 / 2 = the leader's / a helper's tile columns of a split block (scols, the deal of split_deal.hpp;
+    // nt = 6 with one helper: helper 12 tiles of T and 9 of B, leader 24 and 12)
     constexpr int NW = NT / 64;
     constexpr int MAXT = (NT == 512) ? 5 : 3;  // ceil(36 tiles / 16 waves), ceil(36 / 8), ceil(9 / 4)
     const int nt = npg >> 4, ks = (np + 3) >> 2;   // rows / columns past np are zero (identity in V): the K loop stops at np
     const int lane = tid & 63, wv = tid >> 6;
     const int lr = lane & 15, lc = lane >> 4;
-    const int hc = nt >= 6 ? nt / 3 : 1;        // (the helper gets LESS than half: its hand-over - stores, count, the leader's reads - runs while the leader still computes)
-    const int ncol = part == 0 ? nt : part == 2 ? hc : nt - hc;
-    auto colof = [&](int c) { return part == 0 ? c : part == 2 ? c + 1 : (c == 0 ? 0 : hc + c); };
+    const unsigned scols = part == 0 ? 0u : split_cols(nt, a.split, part == 2 ? hidx : 0), clist = split_col_list(scols);
+    const int ncol = part == 0 ? nt : split_col_count(scols);
+    auto colof = [&](int c) { return part == 0 ? c : split_col_at(clist, c); };
     // lower tile number t of this part -> (ti, tj); false past the end
     auto lower_tile = [&](int t, int& ti, int& tj) {
       if (part == 0) { proj_lower_tile(t, nt * (nt + 1) / 2, ti, tj); return ti >= 0; }
@@ -786,7 +791,6 @@ __device__ __forceinline__ void proj_body(const ProjArgs& a, const int k, const 
         }
       // (every element is an agent-scope store of its own - coherent at the device's memory side without an L2 write-back - so the
       // hand-over only has to ORDER them in front of the count: wait for this wave's stores, meet the other waves, then count)
-      if (tid == 0) __hip_atomic_store(a.sxcc + k, (unsigned)__builtin_amdgcn_s_getreg(kHwRegXccId), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       // every wave drains its OWN stores before the barrier: the workgroup-scope release below emits no vmcnt wait (not tgsplit
       // mode), and the agent-scope release of tid 0 waits on wave 0's counter only - without this, tiles of waves 1 .. NW-1 could
       // still be in flight when a leader on another CU sees the count advance
@@ -794,8 +798,9 @@ __device__ __forceinline__ void proj_body(const ProjArgs& a, const int k, const 
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
       __syncthreads();
       // ONE agent-scope release for the whole workgroup (the barrier orders every wave's stores in front of it): the L2 write-back it
-      // implies is what a leader on ANOTHER XCD needs - under multi-process contention the pair does not always stay on one XCD
-      if (tid == 0) __hip_atomic_store(a.sack + k, a.sack[k] + 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+      // implies is what a leader on ANOTHER XCD needs - under multi-process contention the workgroups of a block do not always stay on
+      // one XCD.  An atomic add: the block's other helpers count on the same word
+      if (tid == 0) __hip_atomic_fetch_add(a.sack + k, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
       return;
     }
     __syncthreads();
@@ -807,14 +812,14 @@ __device__ __forceinline__ void proj_body(const ProjArgs& a, const int k, const 
       }
     }
     if (part == 1) {
-      // leader: the helper's tiles (columns 1 .. hc), one per wave and round, behind an acquire of the exchange count
-      const unsigned want = proj_await_helper(a, k, tid);
+      // leader: the helpers' tiles (every column that is not its own), one per wave and round, behind an acquire of the hand-over count
+      const unsigned want = proj_await_helper(a, k, tid, split_helpers(nt, a.split));
       const double* const in = a.sB + (size_t)k * kSplitTileDoubles;
       int nth = 0;
-      for (int c = 1; c <= hc; ++c) nth += nt - c;
+      for (int c = 1; c < nt; ++c) if (!((scols >> c) & 1u)) nth += nt - c;
       for (int t = wv; t < nth; t += NW) {
         int tt = t, ti = 0, tj = 0;
-        for (int c = 1; c <= hc; ++c) { const int cnt = nt - c; if (tt < cnt) { tj = c; ti = c + tt; break; } tt -= cnt; }
+        for (int c = 1; c < nt; ++c) if (!((scols >> c) & 1u)) { const int cnt = nt - c; if (tt < cnt) { tj = c; ti = c + tt; break; } tt -= cnt; }
 #pragma unroll
         for (int r = 0; r < 4; ++r)
           A[(16 * ti + lc + 4 * r) * lda + 16 * tj + lr] = __hip_atomic_load(in + (size_t)(ti * nt + tj) * 256 + 64 * r + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -919,7 +924,7 @@ __device__ __forceinline__ void proj_body(const ProjArgs& a, const int k, const 
       const int rs = a.rstate[4 * k]; wait = rs & 255; level = (rs >> 8) & 255; credit = (rs >> 16) & 255; gcred = (rs >> 24) & 15;
       rdef = *reinterpret_cast<const double*>(a.rstate + 4 * k + 2);
     }
-    // (a leader of a one-tile block owns no column of the split: it keeps the one-workgroup order of the phases)
+    // (a leader of a one-tile block has no helper - the deal leaves it its only column: it keeps the one-workgroup order of the phases)
     stage_b = warm && a.refine != 0 && wait == 0 && role != 2 && !(role == 1 && npg < 32);
   }
   if (warm && V_LDS) {
@@ -1254,8 +1259,8 @@ __device__ __forceinline__ void proj_body(const ProjArgs& a, const int k, const 
         // accumulated (same chain per tile as the congruence runs: identical bits).  The analysis needs nothing of the other waves but
         // the diagonal, so a wave that owns a diagonal tile runs that chain first and publishes its 16 entries of dvec and rdg; behind
         // ONE barrier the waves with a single tile classify it on the vector units while the others run their second chain.
-        const int hc = nt >= 6 ? nt / 3 : 1;      // (two workgroups per block: the helper's tile columns 1 .. hc, as the congruence splits them)
-        auto own = [&](const int m) { return role != 1 || ttj[m] == 0 || ttj[m] > hc; };
+        const unsigned lcols = role == 1 ? split_cols(nt, a.split, 0) : ~0u;      // (split block: the leader's tile columns, as the congruence deals them)
+        auto own = [&](const int m) { return ((lcols >> ttj[m]) & 1u) != 0u; };
         auto chains = [&](auto m_) {
           constexpr int m = decltype(m_)::value;
           d4_t c = {0.0, 0.0, 0.0, 0.0}, c2 = {0.0, 0.0, 0.0, 0.0};
@@ -1288,12 +1293,12 @@ __device__ __forceinline__ void proj_body(const ProjArgs& a, const int k, const 
         };
         const std::integral_constant<int, 0> m0{}; const std::integral_constant<int, 1> m1{};
         if (role == 1) {
-          // leader of a split block: its own tiles and the whole Gram product first - they run while the helper's tiles travel - then
-          // the hand-over, with the helper's tiles taken by the waves that own them in the stage (the element a lane reads is the
+          // leader of a split block: its own tiles and the whole Gram product first - they run while the helpers' tiles travel - then
+          // the hand-over, with the helpers' tiles taken by the waves that own them in the stage (the element a lane reads is the
           // element of the accumulator it would have computed: 64 r + lane of the tile)
           chains(m0); chains(m1);
           RST(1)
-          const unsigned want = proj_await_helper(a, k, tid);
+          const unsigned want = proj_await_helper(a, k, tid, split_helpers(nt, a.split));
           const double* const in = a.sB + (size_t)k * kSplitTileDoubles;
 #pragma unroll
           for (int m = 0; m < 2; ++m)
@@ -2498,15 +2503,17 @@ __device__ __forceinline__ void proj_body(const ProjArgs& a, const int k, const 
 
 template <bool V_LDS, int NT, int ALG = 0, int SPW = 1, int RPW = 1>
 __global__ __launch_bounds__(NT) void k_proj_jacobi(ProjArgs a) {
-  int k = blockIdx.x, role = 0;
+  int k = blockIdx.x, role = 0, hidx = 0;
   if (ALG == 3 && a.split) {
-    // helpers first (they never wait), leaders from the next multiple of 8: workgroup ids go round robin over the 8 XCDs, so a block's
-    // two workgroups share an XCD - and its L2, through which the helper's tiles travel
+    // helpers first (they never wait), one band of nb8 ids per helper number, leaders behind the last band: workgroup ids go round
+    // robin over the 8 XCDs, so a block's workgroups share an XCD - and its L2, through which the helpers' tiles travel (a saving, not
+    // a condition: the hand-over is ordered at agent scope)
     const int nb8 = (a.nblk + 7) & ~7;
-    if (k < nb8) { if (k >= a.nblk) return; role = 2; }
-    else { k -= nb8; role = 1; }
+    for (hidx = 1; hidx <= a.split && k >= nb8; ++hidx) k -= nb8;      // (bands walked: a handful of helpers, no division)
+    if (hidx <= a.split) { if (k >= a.nblk) return; role = 2; }
+    else { hidx = 0; role = 1; }
   }
-  proj_body<V_LDS, NT, ALG, SPW, RPW>(a, k, role);
+  proj_body<V_LDS, NT, ALG, SPW, RPW>(a, k, role, hidx);
 }
 // one launch for the blocks of SEVERAL independent SDPs: map[blockIdx.x] = (SDP, block of that SDP)
 template <bool V_LDS, int NT, int ALG = 0, int SPW = 1, int RPW = 1>
@@ -2559,7 +2566,7 @@ struct ProjPlan {
   void (*kernel)(ProjArgs) = nullptr;                          // the k_proj_jacobi instantiation
   void (*kernel_b)(const ProjArgs*, const int2*) = nullptr;    // the same instantiation of the batched form
   bool packed() const { return alg == kProjPacked; }          // needs the Tg / Ug scratch (warm start, rotation log; basis of the refinement stage)
-  bool split_ok() const { return alg == kProjPingPong; }       // may take two workgroups per block (ProjArgs::split)
+  bool split_ok() const { return alg == kProjPingPong; }       // may take helper workgroups (ProjArgs::split)
   bool has_refine_stage() const { return alg == kProjPingPong || alg == kProjPacked; }   // (blocks 41 .. 160)
   template <bool V_LDS, int NT, int ALG = 0, int SPW = 1, int RPW = 1>
   void use() { nt = NT; kernel = k_proj_jacobi<V_LDS, NT, ALG, SPW, RPW>; kernel_b = k_proj_jacobi_b<V_LDS, NT, ALG, SPW, RPW>; }
@@ -2606,9 +2613,20 @@ inline hipError_t proj_allow_big_lds(const ProjPlan& p) {
 // one launch over `nblocks` blocks; a warm ping-pong launch over all a.nblk blocks with a.split set takes the split grid (kernel above)
 inline void launch_proj(const ProjPlan& p, const ProjArgs& a, int nblocks, hipStream_t st) {
   ProjArgs b = a;
-  b.split = p.split_ok() && a.split != 0 && a.warm != 0 && a.nblk == nblocks ? 1 : 0;
-  const int grid = b.split ? ((nblocks + 7) & ~7) + nblocks : nblocks;
+  b.split = p.split_ok() && a.split > 0 && a.warm != 0 && a.nblk == nblocks ? a.split : 0;
+  const int grid = b.split * ((nblocks + 7) & ~7) + nblocks;
   hipLaunchKernelGGL(p.kernel, dim3(grid), dim3(p.nt), p.lds, st, b);
+}
+// helpers per block a split launch over nblk blocks may take on the current device, at most `want`: every workgroup of the grid finds a
+// CU of its own (the kernel takes a CU's whole LDS) - over the device (hipDeviceProp_t::multiProcessorCount) and on each of the 8 XCDs
+// the ids go round over (a band of nb8 ids puts nb8 / 8 workgroups on every XCD, the leaders up to ceil(nblk / 8))
+inline int split_cap(const int want, const int nblk) {
+  int dev = 0;
+  hipDeviceProp_t pr;
+  if (want <= 0 || nblk <= 0 || hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&pr, dev) != hipSuccess) return 0;
+  const int cus = pr.multiProcessorCount, nb8 = (nblk + 7) & ~7;
+  const int cap = std::min((cus - nblk) / nb8, (cus / 8 - (nblk + 7) / 8) / (nb8 / 8));
+  return std::max(std::min(want, cap), 0);
 }
 // batched form: `nblocks` blocks in total over the SDPs of a batch handle (device arrays args / map)
 inline void launch_proj_batched(const ProjPlan& p, const ProjArgs* dargs, const int2* dmap, int nblocks, hipStream_t st) {

@@ -32,18 +32,21 @@ struct RefineTuning {
   }
 };
 
-// scratch of two workgroups per block for the warm-start congruence (ProjArgs::split): helper tiles, hand-over counters, error flag
+// scratch of the helper workgroups of the warm-start congruence (ProjArgs::split): helper tiles, hand-over counters, error flag
+static constexpr int kSplitHelpers = 5;      // helpers per block where the split is on by default (setup_member)
 struct SplitScratch {
   DBuf<double> B;
-  DBuf<unsigned> ack, seen, xcc;
+  DBuf<unsigned> ack, seen;
   DBuf<int> err;
+  int helpers = 0;      // per block
   bool on() const { return B.p != nullptr; }
-  void alloc(int nblk) {
+  void alloc(int nblk, int nhelpers) {
+    helpers = nhelpers;
     B.alloc((size_t)nblk * kSplitTileDoubles);
-    ack.alloc(nblk); ack.zero(); seen.alloc(nblk); seen.zero(); xcc.alloc(nblk); xcc.zero(); err.alloc(1); err.zero();
+    ack.alloc(nblk); ack.zero(); seen.alloc(nblk); seen.zero(); err.alloc(1); err.zero();
   }
   void bind(ProjArgs& a, int nblk) const {
-    a.split = 1; a.nblk = nblk; a.sB = B.p; a.sack = ack.p; a.sseen = seen.p; a.sxcc = xcc.p; a.serr = err.p; a.spin_limit = 20000000;
+    a.split = helpers; a.nblk = nblk; a.sB = B.p; a.sack = ack.p; a.sseen = seen.p; a.serr = err.p; a.spin_limit = 20000000;
   }
   bool failed() const { return on() && err.download()[0] != 0; }
 };
@@ -369,7 +372,7 @@ struct nnsdp_solver {
   nnsdp::IpcArgs ipa{};
   std::vector<void*> ipc_opened;
   bool ipc_fine = false;               // exchange buffers in fine-grained device memory
-  SplitScratch split;                   // two workgroups per block (ProjArgs::split): ping-pong variant, one SDP, no compacted block list
+  SplitScratch split;                   // helper workgroups per block (ProjArgs::split): ping-pong variant, one SDP, no compacted block list
   int giters = kGraphIters;             // iterations per captured graph (graph_iters_for)
   // the check iteration's control numbers and stage counters land in PINNED host memory (check_enqueue), so that it can be captured too
   double* acc_host = nullptr;
@@ -599,9 +602,12 @@ struct nnsdp_solver {
       // the launch was SLOWER (66.4 against 61.8 us at n = 85); with workgroup-scope ordering only it was fast and WRONG under
       // multi-process contention (the two-rank test saw stale tiles in 2 runs of 3: the pair does not always share an L2 then); with
       // ONE agent-scope release behind the helper's barrier and ONE acquire fence after the leader's poll it is right and 3-4 us
-      // faster per launch (56.8 against 59.9 us, W40-D20 76.5 against 78.1 us per step; profiles/r04_split_probe.log)
-      const int want = (int)env_int("NNSDP_SPLIT", nsm > 80 ? 1 : 0);      // (diagnostic override)
-      if (want != 0 && plan.split_ok() && big_idx.empty() && ncl <= 120) split.alloc(ncl);
+      // faster per launch (56.8 against 59.9 us, W40-D20 76.5 against 78.1 us per step; profiles/r04_split_probe.log).  kSplitHelpers
+      // helpers per block, each with a release of its own behind the leader's ONE acquire: 50.7 against 53.6 us per launch with five
+      // (sweep 1 / 2 / 3 / 5: 55.0 / 51.1 / 51.0 / 50.7 us; profiles/split_helpers_bench_W40-D20.log).
+      // NNSDP_SPLIT=<H> (diagnostic override): helpers per block, 0 = off, 1 = the two-workgroup form; never more than find a CU
+      const int want = plan.split_ok() && big_idx.empty() && ncl <= 120 ? split_cap((int)env_int("NNSDP_SPLIT", nsm > 80 ? kSplitHelpers : 0), ncl) : 0;
+      if (want > 0) split.alloc(ncl, want);
     }
     d_stats.alloc(14); d_stats.zero();
     {
@@ -705,7 +711,7 @@ struct nnsdp_solver {
     NNSDP_B(m_clo) NNSDP_B(m_chi) NNSDP_B(m_w0) NNSDP_B(m_w1) NNSDP_B(m_hslot0) NNSDP_B(m_chunk_of) NNSDP_B(m_sep_of) NNSDP_B(m_sep_gen)
     NNSDP_B(m_slot_chunk) NNSDP_B(m_slotA) NNSDP_B(m_slotB) NNSDP_B(m_poff) NNSDP_B(m_hoff) NNSDP_B(m_P) NNSDP_B(m_H) NNSDP_B(m_HT) NNSDP_B(m_Sc)
     NNSDP_B(m_v) NNSDP_B(m_kap) NNSDP_B(m_t) NNSDP_B(m_rpart) NNSDP_B(m_rvec) NNSDP_B(m_xS) NNSDP_B(m_coef) NNSDP_B(m_dpart) NNSDP_B(m_tiles) NNSDP_B(symv_part)
-    NNSDP_B(split.B) NNSDP_B(split.ack) NNSDP_B(split.seen) NNSDP_B(split.xcc) NNSDP_B(split.err)
+    NNSDP_B(split.B) NNSDP_B(split.ack) NNSDP_B(split.seen) NNSDP_B(split.err)
 #undef NNSDP_B
   }
 
@@ -1301,7 +1307,7 @@ struct nnsdp_solver {
     // rocSOLVER's convergence report of the library eigensolves, sticky since the solver was created.  Clique-sharded: only a block's
     // owner runs dsyevd, so the flag rides in the all-reduced control block (acc[7] >= 1024) and all ranks leave the loop together;
     // a rank-local exit would strand the others in the next iteration's all-reduce.
-    if (split.failed()) throw HipError("projection kernel, two workgroups per block: a helper workgroup did not deliver its tiles in time, or ran on another XCD than its leader");
+    if (split.failed()) throw HipError("projection kernel, helper workgroup(s): a helper did not deliver its tiles in time");
     if (ipc && ipc_err.download()[0] != 0) throw HipError("clique-sharded exchange over hipIpc: a peer did not publish its partial sum in time (rank stopped or not co-scheduled)");
     if (!big_idx.empty()) {
       if (sharded) big_fail = big_fail || acc_host[7] >= 1024.0;
