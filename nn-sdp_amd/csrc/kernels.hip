@@ -121,7 +121,8 @@ struct ProjArgs {
                           // projected this block in this iteration; the workgroup returns at once
   // 1 + split workgroups per block for the warm-start congruence (ping-pong variant, warm launches of one SDP; launch_proj): with
   // nb8 = nblk rounded up to 8 the grid is split x nb8 + nblk - helper h = 1 .. split of block k runs at workgroup (h - 1) nb8 + k (the
-  // HELPERS never wait: dispatched first, they always finish), its LEADER at split x nb8 + k.  All load the block; each computes the tile
+  // HELPERS never wait: dispatched first, they always finish), its LEADER at split x nb8 + k.  All load the block (a helper what its
+  // columns read: proj_helper_load); each computes the tile
   // columns of T = A V and of B = V'T it owns (split_cols of split_deal.hpp; same instruction sequence per tile as the one-workgroup
   // form: identical bits); a helper leaves its tiles of B in `sB` behind a release of `sack[k]` and exits, the leader takes them after
   // its own and goes on alone.  sack / sseen count the helpers' hand-overs per block (device-resident: replayed graphs need no
@@ -270,9 +271,11 @@ static constexpr int kSysHead = 16 + 66;   // red[16], sel[npg + 2 <= 130 ints] 
 #ifdef NNSDP_STAMPS
 #define RST(i) { rst[i] = clock64(); }
 #define STAMP(i, tprev) { long long tn_ = clock64(); st_acc[i] += tn_ - tprev; tprev = tn_; }
+#define RST_PTR rst
 #else
 #define RST(i)
 #define STAMP(i, tprev)
+#define RST_PTR nullptr
 #endif
 
 // One block of a launch as the phases below see it: proj_body's geometry and pointers under their names, filled once per block
@@ -589,6 +592,86 @@ __device__ __forceinline__ void proj_rescale_store(const ProjBlock& b, const Pro
   }
 }
 
+// The load of a HELPER of a split block (ping-pong variant, warm launches only; cmin: the lowest tile column of its share, 1 .. nt - 1).
+// Everything a helper computes - T_c = A V_c and the lower tiles of B_c = V'T_c of its columns c - reads all of A = sym(nu_k) but of
+// V only the tile columns from cmin, its lowest, upwards (T_c: strip c; B_c: strips c .. nt - 1), in HBM a contiguous tail of the
+// column-major V_k that starts at a whole number of 16-byte pieces.  So, against the load of proj_body:
+//   * V_k is read and its padding written from column 16 cmin on only (the same linear 16-byte pieces, clamped and unconditional);
+//   * no |A|_F^2 (the tolerances are the leader's business: a helper leaves behind its hand-over), hence no block reduction;
+//   * the symmetrisation is dealt flat: row r of the strict lower triangle (r elements) is joined with row n - r to a row of n,
+//     the floor(n / 2) x n rectangle goes round the threads, every read in front of the first write (0.5 (x + y) does not depend on
+//     the order of its operands: the bits of the leader's A).
+// The caller's barrier behind the load stands behind this one too.
+template <int NT>
+__device__ __forceinline__ void proj_helper_load(const ProjBlock& b, const ProjArgs& a, const int k, const int cmin, long long* const rst) {
+  constexpr int MR = 5;              // ceil(96 * 96 / 2 / 1024) pieces of nu_k, and slots of the triangle's rectangle (48 * 96), per thread
+  const int n = b.n, npg = b.npg, lda = b.lda, ldv = b.ldv, tid = b.tid;
+  double* const A = b.A; double* const V = b.V;
+  const double* const nuk = b.nuk; const double* const vgk = a.Vg + a.coff[k];
+  const int n2 = n * n, npc = (n2 + 1) >> 1;               // (a helper's block has two tile columns at least: n >= 17)
+  const int jmin = 16 * cmin;                              // first column of V that is read,
+  const int pv0 = (jmin * n) >> 1;                         // its first piece (16 cmin n elements: even)
+  double2 ta[MR], tv[MR];
+#pragma unroll
+  for (int m = 0; m < MR; ++m) {
+    const int pc = tid + NT * m;
+    if (NT * m < npc) ta[m] = *reinterpret_cast<const double2*>(nuk + min(2 * pc, n2 - 2));
+    if (NT * m + pv0 < npc) tv[m] = *reinterpret_cast<const double2*>(vgk + min(2 * (pc + pv0), n2 - 2));
+  }
+  RST(17)
+  const float rn = 1.0f / (float)n, rg = 1.0f / (float)npg;
+  const int pad = npg - n;
+  for (int q = tid; q < pad * npg; q += NT) {              // rows n .. npg - 1, every column of A, the kept columns of V
+    const int r = (int)(((float)q + 0.5f) * rg), j = q - r * npg, i = n + r;
+    A[i * lda + j] = 0.0;
+    if (j >= jmin) V[i + j * ldv] = (i == j) ? 1.0 : 0.0;
+  }
+  for (int q = tid; q < pad * n; q += NT) {                // columns n .. npg - 1 (in the last strip, which every helper keeps), rows below n
+    const int r = (int)(((float)q + 0.5f) * rn), i = q - r * n, j = n + r;
+    A[i * lda + j] = 0.0; V[i + j * ldv] = 0.0;
+  }
+#pragma unroll
+  for (int m = 0; m < MR; ++m) {
+    const int pc = tid + NT * m;
+    if (pc < npc) {
+      // piece pc of nu_k and piece pc + pv0 of V_k: the same row, jmin columns apart (2 pv0 = jmin n).  The last piece of an odd
+      // block was read from n2 - 2 and holds (n2 - 2, n2 - 1): it arrives at different m for the two
+      const int e = 2 * pc;
+      const bool hasv = pc + pv0 < npc, moved = e > n2 - 2, movedv = e + 2 * pv0 > n2 - 2;
+      int j = (int)(((float)e + 0.5f) * rn), i = e - j * n;              // (e < 9216: the float quotient is exact)
+      A[i * lda + j] = moved ? ta[m].y : ta[m].x;
+      if (hasv) V[i + (j + jmin) * ldv] = movedv ? tv[m].y : tv[m].x;
+      ++i; if (i == n) { i = 0; ++j; }
+      if (!moved) A[i * lda + j] = ta[m].y;
+      if (hasv && !movedv) V[i + (j + jmin) * ldv] = tv[m].y;
+    }
+  }
+  RST(12)
+  __syncthreads();
+  RST(13)
+  const int nslot = (n >> 1) * n;
+  int o1[MR], o2[MR];
+  double x[MR], y[MR];
+#pragma unroll
+  for (int m = 0; m < MR; ++m) {
+    const int q = tid + NT * m;
+    o1[m] = -1;
+    if (q < nslot) {
+      const int r0 = (int)(((float)q + 0.5f) * rn), c = q - r0 * n, r = r0 + 1;
+      // slot (r, c): element (r, c) of row r for c < r, else element (n - r, c - r) of its partner (even n: row n / 2 is its own)
+      if (c < r || 2 * r != n) {
+        const int i = c < r ? r : n - r, j = c < r ? c : c - r;
+        o1[m] = i * lda + j; o2[m] = j * lda + i;
+        x[m] = A[o1[m]]; y[m] = A[o2[m]];
+      }
+    }
+  }
+#pragma unroll
+  for (int m = 0; m < MR; ++m)
+    if (o1[m] >= 0) { const double v = 0.5 * (x[m] + y[m]); A[o1[m]] = v; A[o2[m]] = v; }
+  RST(14)
+}
+
 // ALG = 2: register-resident systolic sweeps (below).  SPW = pair slots (2 matrix rows each) per wave, RPW = eigenvector
 // rows per wave; NT/64 * SPW >= ceil(n/2) and NT/64 * RPW >= n + 1 for every block of the launch.
 template <bool V_LDS, int NT, int ALG = 0, int SPW = 1, int RPW = 1>
@@ -608,9 +691,8 @@ __device__ __forceinline__ void proj_body(const ProjArgs& a, const int k, const 
   const int np = (n + 1) & ~1;   // Jacobi dimension (even)
   const int npg = (n + 15) & ~15;  // storage / MFMA dimension (multiple of 16; zero rows, identity in V)
   const int half = np >> 1;
-  // split block: a helper without a share returns in front of the load.  (The deal - split_cols, split_helpers - is worked out again
+  // split block: a helper without a share never gets here (k_proj_jacobi).  (The deal - split_cols, split_helpers - is worked out again
   // where it is used, not kept: the 1024-thread variants have no register to spare for a value that lives through the sweeps)
-  if (role == 2 && split_cols(npg >> 4, a.split, hidx) == 0u) return;
   // (ping-pong sweeps keep a one-cell border around the matrix: 2 more rows / columns of storage)
   const int lda = PP ? kPpLda : npg + 1;    // odd stride (in doubles): column walks hit distinct banks; a constant for the ping-pong variant (immediate LDS offsets)
   const int nrow = PP ? npg + 2 : npg;      // rows of LDS storage per matrix
@@ -640,7 +722,9 @@ __device__ __forceinline__ void proj_body(const ProjArgs& a, const int k, const 
   // ---- load: A = sym(nu_k) (full, both triangles, for the warm-start products), padded row/col zero; starting basis
   double fro2 = 0.0;
   const bool warm = a.warm != 0;
-  if constexpr (PP) {
+  if (PP && role == 2) {
+    proj_helper_load<NT>(b, a, k, split_first_col(hidx), RST_PTR);
+  } else if constexpr (PP) {
     // every global load of the block (matrix, read ONCE, and the warm basis) is issued before the first LDS store; the matrix is
     // symmetrised in LDS afterwards.  The block is n^2 contiguous doubles: thread t takes the 16-byte pieces t, t + 1024, ... of that
     // LINEAR range (8 + 8 wave instructions per thread instead of 12 + 12 guarded 8-byte ones - a CU issues one vector-memory wave
@@ -664,6 +748,7 @@ __device__ __forceinline__ void proj_body(const ProjArgs& a, const int k, const 
         if (warm) tv[m] = *reinterpret_cast<const double2*>(vgk + e);
       }
     }
+    RST(17)
     // padding first (rows / columns n .. npg - 1: zero in A, identity in V), disjoint from what the pieces write
     const float rn = 1.0f / (float)n, rg = 1.0f / (float)npg;
     const int pad = npg - n;
@@ -696,11 +781,28 @@ __device__ __forceinline__ void proj_body(const ProjArgs& a, const int k, const 
     RST(12)
     __syncthreads();
     RST(13)
-    for (int j = wvi; j < n; j += NT >> 6)
-      for (int i = ln + j + 1; i < n; i += 64) {
-        const double v = 0.5 * (A[i * lda + j] + A[j * lda + i]);
-        A[i * lda + j] = v; A[j * lda + i] = v;
-        fro2 += 2.0 * v * v;
+    // (one column per wave and trip, lanes over the rows below the diagonal - the deal and the per-thread order of the sum are part
+    // of fro2's bits and stay - but all of a thread's reads are issued in front of its first write: a pair belongs to one thread alone,
+    // and the trips no longer wait for their two reads one after the other)
+    constexpr int MJ = 96 / (NT >> 6), MI = 2;            // columns per wave, 64-row pieces of a column
+    double sx[MJ * MI], sy[MJ * MI];
+#pragma unroll
+    for (int m = 0; m < MJ; ++m)
+#pragma unroll
+      for (int q = 0; q < MI; ++q) {
+        const int j = wvi + (NT >> 6) * m, i = ln + j + 1 + 64 * q;
+        if (i < n) { sx[m * MI + q] = A[i * lda + j]; sy[m * MI + q] = A[j * lda + i]; }
+      }
+#pragma unroll
+    for (int m = 0; m < MJ; ++m)
+#pragma unroll
+      for (int q = 0; q < MI; ++q) {
+        const int j = wvi + (NT >> 6) * m, i = ln + j + 1 + 64 * q;
+        if (i < n) {
+          const double v = 0.5 * (sx[m * MI + q] + sy[m * MI + q]);
+          A[i * lda + j] = v; A[j * lda + i] = v;
+          fro2 += 2.0 * v * v;
+        }
       }
     if (tid < n) { const double v = A[tid * lda + tid]; fro2 += v * v; }
     RST(14)
@@ -750,7 +852,12 @@ __device__ __forceinline__ void proj_body(const ProjArgs& a, const int k, const 
       }
       acc[m] = c;
     }
-    __syncthreads();
+    // T overwrites A in place: every chain must have read its rows of A before any tile is stored - except where the part is ONE
+    // column of at most NW tiles (ncol and nt are uniform over the workgroup): wave ti then holds the only tile of row strip ti, its
+    // chain read rows 16 ti .. 16 ti + 15 of A (and V, which nobody writes), its stores go into those same rows, and the stores wait
+    // for the chain's result.  No wave touches another's rows, so nothing is left for the barrier to order; the one behind the
+    // stores stays (the second product reads all of T)
+    if (!(ncol == 1 && nt <= NW)) __syncthreads();
 #pragma unroll
     for (int m = 0; m < MAXT; ++m) {
       int t = wv + m * NW;
@@ -761,6 +868,7 @@ __device__ __forceinline__ void proj_body(const ProjArgs& a, const int k, const 
       }
     }
     __syncthreads();
+    RST(18)
     // t_only: the refinement stage takes the second product itself, on the tiles its waves own (it classifies B from the accumulators)
     if (t_only) return;
     int tis[MAXT], tjs[MAXT];
@@ -778,6 +886,7 @@ __device__ __forceinline__ void proj_body(const ProjArgs& a, const int k, const 
       }
       acc[m] = c;
     }
+    RST(19)
     if (part == 2) {
       // helper: its tiles of B go to the exchange buffer in tile order (tile (ti, tj) at (ti nt + tj) x 256, element (lc + 4 r, lr) at
       // 64 r + lane), then one release of the block's exchange count; nothing else of this workgroup is needed
@@ -800,7 +909,18 @@ __device__ __forceinline__ void proj_body(const ProjArgs& a, const int k, const 
       // ONE agent-scope release for the whole workgroup (the barrier orders every wave's stores in front of it): the L2 write-back it
       // implies is what a leader on ANOTHER XCD needs - under multi-process contention the workgroups of a block do not always stay on
       // one XCD.  An atomic add: the block's other helpers count on the same word
+#ifdef NNSDP_STAMPS
+      const long long t_drained = clock64();
+#endif
       if (tid == 0) __hip_atomic_fetch_add(a.sack + k, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+#ifdef NNSDP_STAMPS
+      // the first and the last helper of block 0, wave 0: the path the leader's wait for the hand-over count ends on
+      if (k == 0 && tid == 0 && !a.eig && (hidx == 1 || hidx == nt - 1)) {
+        const long long te = clock64();
+        printf("[stamps n=%d helper %d cols 0x%x] load issued %lld landed + to LDS %lld barrier %lld symmetrise %lld sum + barrier %lld | T %lld B chains %lld stores drained %lld release %lld | total %lld\n",
+               n, hidx, scols, rst[17] - sec_t[0], rst[12] - rst[17], rst[13] - rst[12], rst[14] - rst[13], sec_t[1] - rst[14], rst[18] - sec_t[1], rst[19] - rst[18], t_drained - rst[19], te - t_drained, te - sec_t[0]);
+      }
+#endif
       return;
     }
     __syncthreads();
@@ -2510,7 +2630,9 @@ __global__ __launch_bounds__(NT) void k_proj_jacobi(ProjArgs a) {
     // a condition: the hand-over is ordered at agent scope)
     const int nb8 = (a.nblk + 7) & ~7;
     for (hidx = 1; hidx <= a.split && k >= nb8; ++hidx) k -= nb8;      // (bands walked: a handful of helpers, no division)
-    if (hidx <= a.split) { if (k >= a.nblk) return; role = 2; }
+    // (a helper learns whether it has a share, and its lowest column, in closed form - split_has_share, split_first_col - not by a
+    // walk of split_cols on the scalar unit its 16 waves share: a helper's path to its hand-over is the leader's wait)
+    if (hidx <= a.split) { if (k >= a.nblk || !split_has_share((a.cn[k] + 15) >> 4, a.split, hidx)) return; role = 2; }
     else { hidx = 0; role = 1; }
   }
   proj_body<V_LDS, NT, ALG, SPW, RPW>(a, k, role, hidx);

@@ -42,6 +42,11 @@ NNSDP_HD inline unsigned split_cols(const int nt, const int H, const int h) {
   }
   return m;
 }
+// Two facts about split_cols that a helper needs in front of its load, without the walk (tests/test_split_first_col_cpu.py holds
+// them against split_cols for every nt, H and h): helper h has a share exactly when h <= split_helpers(nt, H), and the lowest column
+// of its share is h - the first pass of the deal goes forwards, and the one helper of H = 1 starts at column 1
+NNSDP_HD inline bool split_has_share(const int nt, const int H, const int h) { return h >= 1 && h <= split_helpers(nt, H); }
+NNSDP_HD inline int split_first_col(const int h) { return h; }
 NNSDP_HD inline int split_col_count(const unsigned cols) { return __builtin_popcount(cols); }
 // a column set (columns below 16, at most 8 of them) as a list: 4 bits per entry, ascending.  The kernel builds the list once per
 // workgroup, from wave-uniform values, and then finds the column of a tile with a shift - no loop in front of a tile's chain

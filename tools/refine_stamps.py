@@ -2,7 +2,10 @@
 library that is never shipped:
     hipcc -O3 --offload-arch=gfx950 -fPIC -shared -std=c++17 -pthread -DNNSDP_STAMPS nn-sdp_amd/csrc/api.hip -o nn-sdp_amd/nnsdp_amd/libnnsdp_hip_stamps.so -lrocsolver -lrocblas -ldl
 usage: python tools/refine_stamps.py [n=85] [blocks=19] [carry]     (carry: the per-block state travels from launch to launch as in a
-solver, so launches 1 and 2 of every case run on the credit of launch 0 - without the Gram product)"""
+solver, so launches 1 and 2 of every case run on the credit of launch 0 - without the Gram product)
+With NNSDP_SPLIT_WARM=<H> in the environment the launches run H helper workgroups per block, and the build also prints wave 0 of
+helpers 1 and nt - 1 of block 0 beside the leader's lines: loads issued / landed and stored / barrier / symmetrise / barrier, then T,
+the B chains, the drained stores and the release (the helpers' printf delays their release: the leader's wait is longer than without)."""
 import sys, os
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "nn-sdp_amd")); sys.path.insert(0, os.path.join(ROOT, "tests")); sys.path.insert(0, ROOT)
