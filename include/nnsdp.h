@@ -477,8 +477,41 @@ int nnsdp_crown_search(nnsdp_crown* h, const double* x1min, const double* x1max,
  * meaningless), else the proved literal, or the best literal of an open box, with its bound. */
 int nnsdp_crown_search_leaves(nnsdp_crown* h, double* lo, double* hi, int32_t* depth, int32_t* proved, int32_t* literal, double* bound);
 
+/* The reach search of nnsdp_amd/split.py (reachSplit, _reach_levels with sdp_per_level = 0) with the frontier kept on the device
+ * (csrc/crown_reach.hpp): encloses the support values  max_x c_i' f(x)  of the handle's nlit directions c_i over the root box
+ * x1min / x1max (xdims[0] each) by branch and bound with an incumbent, on ONE bisection tree for all directions.  Per level: the
+ * handle's bound kernel on chunks of at most `chunk` boxes read directly from the frontier; per box  ub[i] = min(sum_j max(c_ij ymin_j,
+ * c_ij ymax_j), smax_i)  (the sum as in nnsdp_crown_search), the centre and, with corner_points, per direction the corner
+ * where(uA[i] >= 0, hi, lo); the forward pass on the level's (1 + nlit) nb (corner_points, else nb) points; per direction
+ * s = c_i[0] y_0, then + c_i[j] y_j for j ascending, every product and sum rounded on its own, the first maximum over the points in the
+ * order centres, then the corners of direction 0, 1, ..., each in box order; it replaces the incumbent L_i and its point when it is
+ * greater; thr_i = L_i + tol[i]; a box is open when ub[i] > thr_i for some i; open boxes are bisected along the coordinate widest relative
+ * to the root into the second frontier, closed ones write lo, hi, depth and ub to a leaf log, all in device memory; the host reads back
+ * four integers per level.  The tree, the order of the leaves and every number are those of the Python loop with crown_backend
+ * "resident", bit for bit.  No atomics.
+ * The search ends "converged" (status 0) when no box is open, "budget" (1) when a level deeper than max_depth would be needed, no
+ * coordinate can be split, or the children of the open boxes would make more than max_boxes boxes bounded: a level is only created
+ * when the budget holds all of it, so visited <= max_boxes and every leaf has its bounds.  Outputs: status, visited (boxes bounded),
+ * depth_reached (the last level), nleaves (for nnsdp_crown_reach_leaves), incumbent (nlit: L_i), witnesses (xdims[0] x nlit column-major:
+ * the point of L_i), kernel_ms (may be NULL: event time of all launches).
+ * Device memory: 40 xdims[0] max_boxes bytes of frontiers (two of max_boxes boxes) and, per box of max_boxes, 8 (1 + 2 nlit +
+ * (2 + p) xdims[0] + p xdims[K]) + 12 bytes of records, points and leaf log (p = 1 + nlit with corner_points, else 1), allocated at the
+ * first call from max_boxes and reused by a later call that needs no more (a second identical call allocates nothing); the buffers are
+ * the reach search's own, so bound, search and reach can follow each other in any order on one handle; the bound kernel's buffers are
+ * shared and grow as in nnsdp_crown_search.  Counted by nnsdp_crown_info.
+ * -1 with a message, before the GPU is touched and before anything is allocated: max_boxes < 1, chunk < 1, max_depth < 0, a null handle
+ * (in this order, before the handle is used) or argument, a handle created without normals, nlit that is not the handle's, a tol that is
+ * negative or not finite, a non-finite box entry, x1min > x1max, frontiers or point buffers above 2^31 bytes.  Not thread-safe. */
+int nnsdp_crown_reach(nnsdp_crown* h, const double* x1min, const double* x1max, int32_t nlit, const double* tol, int32_t corner_points,
+                      int32_t max_boxes, int32_t max_depth, int32_t chunk, int32_t* status, int32_t* visited, int32_t* depth_reached,
+                      int32_t* nleaves, double* incumbent, double* witnesses, double* kernel_ms);
+
+/* The leaves of the handle's last reach search, in the order of the Python loop (HOST arrays of nleaves entries; lo / hi xdims[0] x
+ * nleaves, bound nlit x nleaves, column-major): closed 1 ("crown") or 0 (open: the budget ended the search); bound: ub of every direction. */
+int nnsdp_crown_reach_leaves(nnsdp_crown* h, double* lo, double* hi, int32_t* depth, int32_t* closed, double* bound);
+
 /* what: 0 device allocations made so far, 1 network uploads so far, 2 box capacity, 3 sample capacity, 4 bound calls (a search counts
- * one per chunk), 5 device bytes held. */
+ * one per chunk), 5 device bytes held, 6 reach searches so far. */
 int nnsdp_crown_info(nnsdp_crown* h, int32_t what, double* out);
 
 /* NULL is a no-op returning 0. */

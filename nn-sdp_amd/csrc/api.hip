@@ -12,6 +12,7 @@
 #include "crown_batch.hpp"
 #include "crown_alpha.hpp"
 #include "crown_search.hpp"
+#include "crown_reach.hpp"
 #include "solver.hpp"
 #include "batch.hpp"
 #include "crown_handle.hpp"
@@ -664,6 +665,28 @@ int nnsdp_crown_search_leaves(nnsdp_crown* h, double* lo, double* hi, int32_t* d
   API_END
 }
 
+int nnsdp_crown_reach(nnsdp_crown* h, const double* x1min, const double* x1max, int32_t nlit, const double* tol, int32_t corner_points,
+                      int32_t max_boxes, int32_t max_depth, int32_t chunk, int32_t* status, int32_t* visited, int32_t* depth_reached,
+                      int32_t* nleaves, double* incumbent, double* witnesses, double* kernel_ms) {
+  API_BEGIN
+  nnsdp_crown::reach(h, x1min, x1max, nlit, tol, corner_points, max_boxes, max_depth, chunk, status, visited, depth_reached, nleaves,
+                     incumbent, witnesses, kernel_ms);
+  API_END
+}
+
+int nnsdp_crown_reach_leaves(nnsdp_crown* h, double* lo, double* hi, int32_t* depth, int32_t* closed, double* bound) {
+  API_BEGIN
+  if (!h) throw std::invalid_argument("null handle");
+  const nnsdp_crown::ReachLeaves& L = h->rleaves;
+  if (!L.depth.empty() && (!lo || !hi || !depth || !closed || !bound)) throw std::invalid_argument("null argument");
+  std::copy(L.lo.begin(), L.lo.end(), lo);
+  std::copy(L.hi.begin(), L.hi.end(), hi);
+  std::copy(L.depth.begin(), L.depth.end(), depth);
+  std::copy(L.closed.begin(), L.closed.end(), closed);
+  std::copy(L.bound.begin(), L.bound.end(), bound);
+  API_END
+}
+
 int nnsdp_crown_info(nnsdp_crown* h, int32_t what, double* out) {
   API_BEGIN
   if (!h || !out) throw std::invalid_argument("null argument");
@@ -674,7 +697,8 @@ int nnsdp_crown_info(nnsdp_crown* h, int32_t what, double* out) {
     case 3: *out = (double)h->sample_cap; break;
     case 4: *out = (double)h->n_bound; break;
     case 5: *out = (double)h->device_bytes(); break;
-    default: throw std::invalid_argument("nnsdp_crown_info: what must be in 0..5");
+    case 6: *out = (double)h->n_reach; break;
+    default: throw std::invalid_argument("nnsdp_crown_info: what must be in 0..6");
   }
   API_END
 }

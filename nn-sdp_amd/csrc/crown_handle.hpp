@@ -54,6 +54,16 @@ struct nnsdp_crown {
     std::vector<int32_t> depth, proved, literal;
     void clear() { lo.clear(); hi.clear(); bound.clear(); depth.clear(); proved.clear(); literal.clear(); }
   } leaves;
+  // nnsdp_crown_reach only (nothing before its first call): its own two frontiers, records / points / leaf log / incumbents, sized from
+  // max_boxes at the first call; the bound kernel's buffers and the status record's pinned copy are the ones the search uses
+  DBuf<double> rfr, rdb;
+  DBuf<int> rcu, rib;
+  long long n_reach = 0;
+  struct ReachLeaves {                   // flat, in the order of the Python loop; lo / hi n0 x nleaves, bound nlit x nleaves column-major
+    std::vector<double> lo, hi, bound;
+    std::vector<int32_t> depth, closed;
+    void clear() { lo.clear(); hi.clear(); bound.clear(); depth.clear(); closed.clear(); }
+  } rleaves;
 
   size_t scr_per_box() const { return (size_t)(activ == NNSDP_ACTIV_TANH ? 6 : 2) * acdim; }
   nnsdp::CrownLayout layout(size_t nbox) const { return nnsdp::CrownLayout{nbox, (size_t)n0, (size_t)acdim, (size_t)ny, (size_t)nlit}; }
@@ -73,7 +83,8 @@ struct nnsdp_crown {
   }
   size_t device_bytes() const {
     return dxd.bytes() + dao.bytes() + dmo.bytes() + dM.bytes() + din.bytes() + dscr.bytes() + dout.bytes() + dX.bytes() + dY.bytes() +
-           dain.bytes() + daout.bytes() + dast.bytes() + sfr.bytes() + sdb.bytes() + scu.bytes() + sib.bytes();
+           dain.bytes() + daout.bytes() + dast.bytes() + sfr.bytes() + sdb.bytes() + scu.bytes() + sib.bytes() +
+           rfr.bytes() + rdb.bytes() + rcu.bytes() + rib.bytes();
   }
   // the capacity grows geometrically and never shrinks
   // staging = false (a search: nothing of a box crosses the bus): the pinned copies wait for the next bound call
@@ -105,6 +116,13 @@ struct nnsdp_crown {
     if (4 * cap * n0 > sfr.n) { dalloc(sfr, 4 * cap * n0); scu.alloc(2 * cap * n0); ++n_alloc; }
     if (nd > sdb.n) dalloc(sdb, nd);
     if (ni > sib.n) { sib.alloc(ni); ++n_alloc; }
+    if (!hstatus) HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&hstatus), 4 * sizeof(int), hipHostMallocDefault));
+  }
+  // the buffers of a reach search: frontiers of `cap` boxes each, `nd` doubles and `ni` ints of records; they only grow
+  void reserve_reach(size_t cap, size_t nd, size_t ni) {
+    if (4 * cap * n0 > rfr.n) { dalloc(rfr, 4 * cap * n0); rcu.alloc(2 * cap * n0); ++n_alloc; }
+    if (nd > rdb.n) dalloc(rdb, nd);
+    if (ni > rib.n) { rib.alloc(ni); ++n_alloc; }
     if (!hstatus) HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&hstatus), 4 * sizeof(int), hipHostMallocDefault));
   }
   void reserve_samples(size_t N) {
@@ -409,6 +427,136 @@ struct nnsdp_crown {
       if (open[b]) from_frontier(b, best[b], bnd[b]);
     *verdict = verd; *visited = vis; *depth_reached = depth; *nleaves = (int32_t)L.depth.size();
     if (verd == 1) std::copy(wit.begin(), wit.end(), witness);
+    if (kernel_ms) *kernel_ms = ms_all;
+  }
+
+  // nnsdp_crown_reach.  h may be null: the scalar options come first so that their refusals can be tested on a machine without a GPU,
+  // where no handle exists; every refusal comes before anything is allocated
+  static void reach(nnsdp_crown* h, const double* x1min, const double* x1max, int32_t nlit, const double* tol, int32_t corner_points,
+                    int32_t max_boxes, int32_t max_depth, int32_t chunk, int32_t* status, int32_t* visited, int32_t* depth_reached,
+                    int32_t* nleaves, double* incumbent, double* witnesses, double* kernel_ms) {
+    if (max_boxes < 1) throw std::invalid_argument("max_boxes must be >= 1, got " + std::to_string(max_boxes));
+    if (chunk < 1) throw std::invalid_argument("chunk must be >= 1, got " + std::to_string(chunk));
+    if (max_depth < 0) throw std::invalid_argument("max_depth must be >= 0, got " + std::to_string(max_depth));
+    if (!h) throw std::invalid_argument("null handle");
+    if (!x1min || !x1max || !tol || !status || !visited || !depth_reached || !nleaves || !incumbent || !witnesses) throw std::invalid_argument("null argument");
+    const int n0 = h->n0, ny = h->ny;
+    if (h->nlit < 1) throw std::invalid_argument("reach needs directions: the handle was created without normals");
+    if (nlit != h->nlit) throw std::invalid_argument("nlit must be the handle's " + std::to_string(h->nlit) + ", got " + std::to_string(nlit));
+    for (int i = 0; i < nlit; ++i)
+      if (!std::isfinite(tol[i]) || !(tol[i] >= 0.0))
+        throw std::invalid_argument("direction " + std::to_string(i) + ": tol must be finite and >= 0 (no NaN, no infinity)");
+    unsigned long long splitmask = 0;
+    for (int t = 0; t < n0; ++t) {
+      if (!std::isfinite(x1min[t]) || !std::isfinite(x1max[t]) || !(x1min[t] <= x1max[t]))
+        throw std::invalid_argument("the root box: x1min must be <= x1max and both finite (no NaN, no infinity)");
+      if (x1max[t] > x1min[t]) splitmask |= 1ull << t;
+    }
+    // every level fits the budget as a whole, so no level and no set of children has more than max_boxes boxes
+    const size_t mb = (size_t)max_boxes, npmax = corner_points ? (size_t)(1 + nlit) * mb : mb, logw = 2 * (size_t)n0 + 1 + (size_t)nlit;
+    const size_t frontier_bytes = 2 * mb * n0 * (2 * sizeof(double) + sizeof(int));
+    if (frontier_bytes > nnsdp::kSearchFrontierCap)
+      throw std::invalid_argument("max_boxes = " + std::to_string(max_boxes) + " needs " + std::to_string(frontier_bytes) +
+                                  " bytes of frontier buffers, above the cap of 2^31 bytes");
+    // doubles: ub, points in, points out, leaf log, normals, tol, L, thr, xw;  ints: open, coord, slot, status
+    const size_t o_ub = 0, o_X = o_ub + (size_t)nlit * mb, o_Y = o_X + npmax * n0, o_log = o_Y + npmax * ny, o_nrm = o_log + mb * logw,
+                 o_tol = o_nrm + (size_t)nlit * ny, o_L = o_tol + nlit, o_thr = o_L + nlit, o_xw = o_thr + nlit, nd = o_xw + (size_t)nlit * n0;
+    if (nd * sizeof(double) > nnsdp::kSearchFrontierCap)
+      throw std::invalid_argument("max_boxes = " + std::to_string(max_boxes) + " needs " + std::to_string(nd * sizeof(double)) +
+                                  " bytes of point and leaf-log buffers, above the cap of 2^31 bytes");
+    const size_t ni = 3 * mb + 4;
+    const size_t cb = std::min((size_t)chunk, mb);
+    h->rleaves.clear();
+    h->reserve_reach(mb, nd, ni);
+    ++h->n_reach;
+    hipStream_t st = h->st;
+    double* D = h->rdb.p;
+    int* I = h->rib.p;
+    double *flo[2] = {h->rfr.p, h->rfr.p + 2 * mb * n0}, *fhi[2] = {flo[0] + mb * n0, flo[1] + mb * n0};
+    int* fcu[2] = {h->rcu.p, h->rcu.p + mb * n0};
+    const std::vector<double> Linit((size_t)nlit, -HUGE_VAL);
+    HIPCHK(hipMemcpyAsync(flo[0], x1min, n0 * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(fhi[0], x1max, n0 * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(fcu[0], 0, n0 * sizeof(int), st));
+    HIPCHK(hipMemcpyAsync(D + o_nrm, h->normals.data(), (size_t)nlit * ny * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(D + o_tol, tol, nlit * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(D + o_L, Linit.data(), nlit * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(D + o_thr, 0, ((size_t)nlit + (size_t)nlit * n0) * sizeof(double), st));
+    HIPCHK(hipStreamSynchronize(st));      // (the sources are pageable arrays)
+
+    nnsdp::ReachArgs r;
+    r.n0 = n0; r.ny = ny; r.nlit = nlit; r.corner_points = corner_points != 0; r.max_boxes = max_boxes; r.splitmask = splitmask;
+    r.normals = D + o_nrm; r.tol = D + o_tol; r.open = I; r.coord = I + mb; r.slot = I + 2 * mb; r.status = I + 3 * mb;
+    r.ub = D + o_ub; r.X = D + o_X; r.Y = D + o_Y; r.L = D + o_L; r.thr = D + o_thr; r.xw = D + o_xw; r.log = D + o_log;
+    // k_search_scan as it is: it reads nb, open and (no points: never) pflag of its SearchArgs and writes slot and status
+    nnsdp::SearchArgs s{};
+    s.open = r.open; s.slot = r.slot; s.pflag = I + 3 * mb; s.status = I + 3 * mb;
+
+    int cur = 0, nb = 1, vis = 1, depth = 0, stat = -1;
+    long long log_n = 0;
+    double ms_all = 0.0;
+    for (;;) {
+      h->reserve_boxes(std::min(cb, (size_t)nb), false, cb);      // (the stream is idle here: the bound kernel's buffers grow with the levels)
+      r.nb = nb; r.depth = depth; r.visited = vis; r.children = depth < max_depth && splitmask != 0;
+      r.lo = flo[cur]; r.hi = fhi[cur]; r.cuts = fcu[cur]; r.nlo = flo[cur ^ 1]; r.nhi = fhi[cur ^ 1]; r.ncuts = fcu[cur ^ 1]; r.log_base = log_n;
+      s.nb = nb;
+      HIPCHK(hipEventRecord(h->e0, st));
+      for (int off = 0; off < nb; off += (int)cb) {
+        const size_t nc = std::min(cb, (size_t)(nb - off));
+        const nnsdp::CrownArgs a = h->bound_args(h->layout(nc), flo[cur] + (size_t)off * n0, fhi[cur] + (size_t)off * n0, h->dout.p);
+        h->launch_bound(a, nc);
+        hipLaunchKernelGGL(nnsdp::k_reach_points, dim3((unsigned)cdiv((long long)nc, 256)), dim3(256), 0, st, r, off, (int)nc,
+                           (const double*)a.ymin, (const double*)a.ymax, (const double*)a.smax, (const double*)a.uA);
+        HIPCHK(hipGetLastError());
+        ++h->n_bound;
+      }
+      const long long npts = (long long)nb * (corner_points ? 1 + nlit : 1);
+      h->launch_forward(r.X, D + o_Y, npts);
+      hipLaunchKernelGGL(nnsdp::k_reach_incumbent, dim3((unsigned)nlit), dim3(256), 0, st, r, npts);
+      HIPCHK(hipGetLastError());
+      hipLaunchKernelGGL(nnsdp::k_reach_classify, dim3((unsigned)cdiv(nb, 256)), dim3(256), 0, st, r);
+      HIPCHK(hipGetLastError());
+      hipLaunchKernelGGL(nnsdp::k_search_scan, dim3(1), dim3(256), 0, st, s, 0LL);
+      HIPCHK(hipGetLastError());
+      hipLaunchKernelGGL(nnsdp::k_reach_scatter, dim3((unsigned)cdiv(nb, 256)), dim3(256), 0, st, r);
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipEventRecord(h->e1, st));
+      HIPCHK(hipMemcpyAsync(h->hstatus, r.status, 4 * sizeof(int), hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
+      ms_all += h->elapsed_ms();
+      const int nclosed = h->hstatus[1], nopen = h->hstatus[2];
+      if (h->hstatus[0] != nb || nclosed < 0 || nopen < 0 || nclosed + nopen != nb) throw std::runtime_error("nnsdp_crown_reach: inconsistent status record");
+      log_n += nclosed;
+      if (nopen == 0) { stat = 0; break; }
+      if (!r.children || (long long)vis + 2LL * nopen > (long long)max_boxes) { stat = 1; break; }      // (k_reach_scatter's rule)
+      cur ^= 1; nb = 2 * nopen; vis += nb; ++depth;
+    }
+    // the leaves in the order of the Python loop: the log, then (budget) the open boxes of the last level
+    std::vector<double> log((size_t)log_n * logw);
+    if (log_n) HIPCHK(hipMemcpy(log.data(), r.log, log.size() * sizeof(double), hipMemcpyDeviceToHost));
+    ReachLeaves& Lv = h->rleaves;
+    auto leaf = [&](const double* blo, const double* bhi, int d, int closed, const double* bound) {
+      Lv.lo.insert(Lv.lo.end(), blo, blo + n0); Lv.hi.insert(Lv.hi.end(), bhi, bhi + n0);
+      Lv.bound.insert(Lv.bound.end(), bound, bound + nlit);
+      Lv.depth.push_back(d); Lv.closed.push_back(closed);
+    };
+    for (long long k = 0; k < log_n; ++k) {
+      const double* row = log.data() + (size_t)k * logw;
+      leaf(row, row + n0, (int)row[2 * n0], 1, row + 2 * n0 + 1);
+    }
+    if (stat == 1) {
+      std::vector<double> lo((size_t)nb * n0), hi((size_t)nb * n0), ub((size_t)nb * nlit);
+      std::vector<int> open((size_t)nb);
+      HIPCHK(hipMemcpy(lo.data(), flo[cur], lo.size() * sizeof(double), hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(hi.data(), fhi[cur], hi.size() * sizeof(double), hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(ub.data(), r.ub, ub.size() * sizeof(double), hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(open.data(), r.open, open.size() * sizeof(int), hipMemcpyDeviceToHost));
+      for (int b = 0; b < nb; ++b)
+        if (open[b]) leaf(lo.data() + (size_t)b * n0, hi.data() + (size_t)b * n0, depth, 0, ub.data() + (size_t)b * nlit);
+    }
+    HIPCHK(hipMemcpy(incumbent, r.L, nlit * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(witnesses, r.xw, (size_t)nlit * n0 * sizeof(double), hipMemcpyDeviceToHost));
+    *status = stat; *visited = vis; *depth_reached = depth; *nleaves = (int32_t)Lv.depth.size();
     if (kernel_ms) *kernel_ms = ms_all;
   }
 

@@ -375,7 +375,7 @@ class CrownBounder:
     ReLU and Tanh networks with every width <= 64; anything else raises (no fall-back to the host).  The ReLU results have the bits of
     makeIntervalsBatch(backend="gpu"); the Tanh kernel exists only here.  A context manager; not thread-safe."""
 
-    _INFO = ("device_allocations", "network_uploads", "box_capacity", "sample_capacity", "bound_calls", "device_bytes")
+    _INFO = ("device_allocations", "network_uploads", "box_capacity", "sample_capacity", "bound_calls", "device_bytes", "reach_calls")
 
     def __init__(self, net: M.FeedFwdNet, normals=None):
         self._h = None
@@ -496,6 +496,37 @@ class CrownBounder:
                                                        lproved.ctypes.data_as(ip), llit.ctypes.data_as(ip), lbound.ctypes.data_as(dp)))
         return dict(verdict=("holds", "violated", "unknown")[verdict], visited=visited, depth=depth, witness=wit if verdict == 1 else None,
                     kernel_ms=ms.value, lo=llo, hi=lhi, leaf_depth=ldepth, proved=lproved, literal=llit, bound=lbound)
+
+    def reach(self, lo, hi, tol, *, corner_points: bool = False, max_boxes: int = 512, max_depth: int = 24, chunk: int = 4096) -> dict:
+        """nnsdp_crown_reach: the bounds-only level loop of split.reachSplit on the root box lo / hi (xdims[0] each) for the bounder's
+        directions, with the frontier and the incumbents kept on the GPU (csrc/crown_reach.hpp); tol: one tolerance per direction (or a
+        scalar).  Returns the pieces of a ReachSplitResult: status, visited, depth, incumbent (nlit), witnesses (nlit x xdims[0]),
+        kernel_ms, and the leaves as arrays in the Python loop's order: lo, hi (nleaves x xdims[0]), leaf_depth, closed (1 "crown",
+        0 open), bound (nleaves x nlit)."""
+        h, dp, ip = self._handle(), _lib.c_double_p, _lib.c_int32_p
+        lo = np.ascontiguousarray(lo, dtype=np.float64)
+        hi = np.ascontiguousarray(hi, dtype=np.float64)
+        if lo.shape != (self._n0,) or hi.shape != (self._n0,):
+            raise ValueError("lo / hi must have xdims[0] entries")
+        nlit = self._nlit or 0
+        tol = np.ascontiguousarray(tol, dtype=np.float64)
+        if tol.ndim == 0:
+            tol = np.full(max(nlit, 1), float(tol))
+        if tol.ndim != 1 or tol.size != max(nlit, 1):
+            raise ValueError("tol must be a scalar or one tolerance per direction")
+        out = (C.c_int32 * 4)()
+        inc, wit, ms = np.zeros(max(nlit, 1)), np.zeros((max(nlit, 1), self._n0)), C.c_double(0.0)
+        _lib.check(self._lib.nnsdp_crown_reach(h, lo.ctypes.data_as(dp), hi.ctypes.data_as(dp), nlit, tol.ctypes.data_as(dp),
+                                               int(bool(corner_points)), int(max_boxes), int(max_depth), int(chunk),
+                                               *[C.cast(C.byref(out, 4 * k), ip) for k in range(4)],
+                                               inc.ctypes.data_as(dp), wit.ctypes.data_as(dp), C.byref(ms)))
+        status, visited, depth, n = (int(v) for v in out)
+        llo, lhi, lbound = np.zeros((n, self._n0)), np.zeros((n, self._n0)), np.zeros((n, nlit))
+        ldepth, lclosed = (np.zeros(n, dtype=np.int32) for _ in range(2))
+        _lib.check(self._lib.nnsdp_crown_reach_leaves(h, llo.ctypes.data_as(dp), lhi.ctypes.data_as(dp), ldepth.ctypes.data_as(ip),
+                                                      lclosed.ctypes.data_as(ip), lbound.ctypes.data_as(dp)))
+        return dict(status=("converged", "budget")[status], visited=visited, depth=depth, incumbent=inc, witnesses=wit, kernel_ms=ms.value,
+                    lo=llo, hi=lhi, leaf_depth=ldepth, closed=lclosed, bound=lbound)
 
     def info(self) -> dict:
         h, v, out = self._handle(), C.c_double(0.0), {}

@@ -19,6 +19,9 @@ answers of a single solve.  verifySplit works level by level on the frontier of 
 The driver is deterministic: no random numbers unless samples > 0, and then seeded from the box index.  With
 sdp_per_level = 0 and crown_backend = "host" it needs no GPU.  The reference has no counterpart (it prints :unsafe for a clause
 it could not certify on the whole box, experiments/acas.jl:87-137).
+
+reachSplit (below) is the same tree for a reach question: no threshold is given, the threshold of direction i is the incumbent
+L_i + tol_i, which moves as better points are found, and the result is an enclosure [lower_i, upper_i] of  max_x c_i' f(x).
 """
 from __future__ import annotations
 
@@ -67,6 +70,7 @@ class SplitOptions:
     # (CrownBounder.search, csrc/crown_search.hpp); the same SplitResult bit for bit.  Needs crown_backend "resident", samples = 0 and
     # alpha_steps = 0.  With sdp_per_level > 0 the SDPs run once, on the open leaves of a search that ended "unknown".
     # SplitResult.seconds then has one more key, "kernel": the HIP-event time of the search's launches (tools/split_timing.py reads it).
+    # reachSplit takes the same option (CrownBounder.reach, csrc/crown_reach.hpp) and then also needs sdp_per_level = 0.
     # chunk: boxes per launch of the bound kernel, which bounds the device memory of a level's interval arrays
     frontier: str = "host"
     chunk: int = 4096
@@ -366,3 +370,229 @@ def _split_levels(net, frontier, root_lo, root_hi, normals, hs, beta, opts, spli
     # every box of the last level was proved; boxes that the budget kept from being bounded are open leaves, and one open leaf is
     # enough for "unknown"
     return done("holds" if all(lf.proved_by is not None for lf in leaves) else "unknown")
+
+
+# ----------------------------------------------------------------------------- reach: support values to a tolerance
+@dataclass
+class ReachLeaf:
+    lo: np.ndarray
+    hi: np.ndarray
+    depth: int
+    closed_by: Optional[str]      # "crown" | "sdp" | None (open: the budget ended the search)
+    bound: np.ndarray             # nlit: the upper bound of every direction on the box
+
+
+@dataclass
+class ReachSplitResult:
+    status: str                   # "converged" | "budget"
+    lower: np.ndarray             # nlit: c_i' f(witness_i), recomputed on the host in fp64
+    upper: np.ndarray             # nlit: the maximum of bound[i] over the leaves
+    incumbent: np.ndarray         # nlit: the loop's own L_i (the value at witness_i as the backend's forward pass gave it)
+    witnesses: np.ndarray         # nlit x n0
+    leaves: List[ReachLeaf]
+    visited: int
+    depth: int
+    sdp_solves: int
+    seconds: Dict[str, float] = field(default_factory=dict)
+
+
+def _support_values(Cn, Y) -> np.ndarray:
+    """s[i, p] = c_i' Y[:, p] with a fixed order: c_i[0] Y[0, p], then + c_i[j] Y[j, p] for j ascending, every product and every sum
+    rounded on its own (no BLAS, whose order and fused multiply-adds are its own business); csrc/crown_reach.hpp restates it"""
+    s = Cn[:, 0:1] * Y[0:1, :]
+    for j in range(1, Cn.shape[1]):
+        s = s + Cn[:, j:j + 1] * Y[j:j + 1, :]
+    return s
+
+
+def reachSplit(net: M.FeedFwdNet, x1min, x1max, normals, tol, beta: int = 0, opts: M.AdmmSdpOptions = None,
+               split: SplitOptions = None) -> ReachSplitResult:
+    """Enclose the support values  max_x c_i' f(x)  over the box [x1min, x1max] for the rows c_i of `normals` (nlit x xdims[K],
+    1 <= nlit <= 64) in [lower_i, upper_i] by branch and bound on ONE bisection tree for all directions; tol is a scalar or nlit values,
+    finite and >= 0.  Per level of the tree, on its frontier of boxes:
+
+      bound      the bound call of verifySplit with the normals always passed: ub[i, b] = min(per-output bound, literal bound)
+      points     the box centres, then with corner_points per direction the corner  where(A[i, :, b] >= 0, hi, lo)  of every box,
+                 through the backend's forward pass
+      incumbent  L_i = the largest c_i' f(point) seen so far (the first of equal points), with its point x_i
+      classify   a box is open when  ub[i, b] > L_i + tol_i  for some i; the others are leaves ("crown") carrying ub[:, b]
+      sdp        (sdp_per_level > 0, host frontier) the open boxes closest to closing get one reach SDP per direction with the target
+                 L_i + tol_i; a certified  rho <= L_i + tol_i  replaces ub[i, b], and a box with no direction left is a leaf ("sdp")
+      stop       no open box: "converged".  depth >= max_depth, nothing splittable, or visited + 2 * open > max_boxes: "budget", the
+                 open boxes become open leaves.  A level is only created when the budget holds all of it
+      split      every open box is bisected along the coordinate widest relative to the root, as in verifySplit
+
+    Guarantees: the leaves tile the root box; every leaf has a bound and visited <= max_boxes;  lower_i <= max c_i' f <= upper_i  up to
+    the bound routine's own rounding slack; on "converged"  upper_i <= incumbent_i + tol_i  holds as a floating-point comparison.
+    SplitOptions as in verifySplit (literal_bounds is implied; samples must be 0; alpha_steps > 0 on the host frontier with
+    crown_backend "host" or "resident" on a ReLU network).  frontier = "device" runs the same loop in CrownBounder.reach
+    (csrc/crown_reach.hpp) with the same result bit for bit as frontier = "host" with crown_backend = "resident"; it needs
+    crown_backend "resident", samples = 0, alpha_steps = 0 and sdp_per_level = 0."""
+    split = split or SplitOptions()
+    opts = opts or M.AdmmSdpOptions()
+    if split.crown_backend not in ("gpu", "host", "resident"):
+        raise ValueError("crown_backend must be 'gpu', 'host' or 'resident'")
+    if split.samples != 0:
+        raise ValueError("reachSplit needs samples == 0")
+    if split.alpha_steps < 0:
+        raise ValueError("alpha_steps must be >= 0")
+    if split.alpha_steps > 0:
+        if split.crown_backend not in ("host", "resident"):
+            raise ValueError("alpha_steps > 0 needs crown_backend 'host' or 'resident'")
+        if M._activ_code(net.activ) != M.ACTIV_RELU:
+            raise ValueError("alpha_steps > 0 is for ReLU networks")
+    if split.frontier not in ("host", "device"):
+        raise ValueError("frontier must be 'host' or 'device'")
+    if split.frontier == "device":
+        if split.crown_backend != "resident":
+            raise ValueError("frontier 'device' needs crown_backend 'resident'")
+        if split.alpha_steps != 0:
+            raise ValueError("frontier 'device' needs alpha_steps == 0")
+        if split.sdp_per_level != 0:
+            raise ValueError("frontier 'device' of reachSplit needs sdp_per_level == 0")
+    if int(split.max_boxes) < 1:
+        raise ValueError("max_boxes must be >= 1")
+    t_start = time.perf_counter()
+    root_lo, root_hi = np.array(x1min, dtype=np.float64), np.array(x1max, dtype=np.float64)
+    n0, ny = net.xdims[0], net.xdims[-1]
+    if root_lo.shape != (n0,) or root_hi.shape != (n0,) or not np.all(root_lo <= root_hi):
+        raise ValueError("x1min / x1max must have xdims[0] entries with x1min <= x1max")
+    Cn = np.array(normals, dtype=np.float64)
+    if Cn.ndim != 2 or Cn.shape[1] != ny or not 1 <= Cn.shape[0] <= 64:
+        raise ValueError("normals must be nlit x xdims[K] with 1 <= nlit <= 64")
+    nlit = Cn.shape[0]
+    tol = np.array(tol, dtype=np.float64)
+    if tol.ndim == 0:
+        tol = np.full(nlit, float(tol))
+    if tol.shape != (nlit,) or not np.all(np.isfinite(tol)) or not np.all(tol >= 0.0):
+        raise ValueError("tol must be a scalar or nlit values, finite and >= 0")
+    seconds = {"crown": 0.0, "setup": 0.0, "solve": 0.0, "finish": 0.0, "total": 0.0}
+    bounder = F.CrownBounder(net, Cn) if split.crown_backend == "resident" else None
+    try:
+        if split.frontier == "device":
+            res = _reach_device(root_lo, root_hi, tol, split, bounder, seconds)
+        else:
+            res = _reach_levels(net, root_lo, root_hi, Cn, tol, beta, opts, split, bounder, seconds)
+    finally:
+        if bounder is not None:
+            bounder.close()
+    status, L, W, leaves, visited, depth, sdp_solves = res
+    lower = np.array([float(Cn[i] @ F.evalFeedFwdNet(net, W[i])) for i in range(nlit)])
+    upper = np.max(np.stack([lf.bound for lf in leaves], axis=1), axis=1)
+    seconds["total"] = time.perf_counter() - t_start
+    return ReachSplitResult(status, lower, upper, L, W, leaves, visited, depth, sdp_solves, seconds)
+
+
+def _reach_device(root_lo, root_hi, tol, split, bounder, seconds):
+    t0 = time.perf_counter()
+    r = bounder.reach(root_lo, root_hi, tol, corner_points=split.corner_points, max_boxes=int(split.max_boxes),
+                      max_depth=int(split.max_depth), chunk=int(split.chunk))
+    seconds["crown"] += time.perf_counter() - t0
+    seconds["kernel"] = 1e-3 * r["kernel_ms"]
+    leaves = [ReachLeaf(r["lo"][k].copy(), r["hi"][k].copy(), int(r["leaf_depth"][k]), "crown" if r["closed"][k] else None, r["bound"][k].copy())
+              for k in range(len(r["closed"]))]
+    return r["status"], r["incumbent"], r["witnesses"], leaves, r["visited"], r["depth"], 0
+
+
+def _reach_levels(net, root_lo, root_hi, Cn, tol, beta, opts, split, bounder, seconds):
+    """the levels of reachSplit; bounder: the CrownBounder of crown_backend = "resident" (the caller closes it), else None"""
+    n0, nlit = net.xdims[0], Cn.shape[0]
+    frontier = [_Box(root_lo, root_hi, np.zeros(n0, dtype=np.int64))]
+    leaves: List[ReachLeaf] = []
+    L, W = np.full(nlit, -np.inf), np.zeros((nlit, n0))
+    visited, sdp_solves, depth = 1, 0, 0
+    splittable = root_hi > root_lo
+    while True:
+        nb = len(frontier)
+        # 1. bound
+        t0 = time.perf_counter()
+        lo, hi = np.stack([b.lo for b in frontier], axis=1), np.stack([b.hi for b in frontier], axis=1)
+        ak = {}
+        if split.alpha_steps > 0:
+            ak = dict(alpha_steps=int(split.alpha_steps), eta0=split.alpha_eta0, decay=split.alpha_decay)
+            if split.alpha_inherit and frontier[0].alpha0 is not None:
+                ak["alpha0"] = np.stack([b.alpha0 for b in frontier], axis=2)
+        if bounder is not None:
+            iv = bounder.bound(lo, hi, **ak)
+        else:
+            iv = F.makeIntervalsBatch(net, lo, hi, backend=split.crown_backend, normals=Cn, **ak)
+        *iv, lits = iv
+        iv = tuple(iv)
+        seconds["crown"] += time.perf_counter() - t0
+        ymin, ymax = iv[4], iv[5]
+        cheap = np.stack([np.maximum(nrm[:, None] * ymin, nrm[:, None] * ymax).sum(axis=0) for nrm in Cn])   # direction x box
+        ub = np.minimum(cheap, lits.smax)
+        # 2. points: the centres, then per direction the corners of its linear upper bound
+        pts = [0.5 * (lo + hi)]
+        if split.corner_points:
+            for i in range(nlit):
+                pts.append(np.where(lits.A[i] >= 0.0, hi, lo))
+        X = np.concatenate(pts, axis=1)
+        if bounder is not None:
+            Y = bounder.eval(X)
+        else:
+            Y = F.evalFeedFwdNetBatch(net, X) if split.crown_backend == "gpu" else F.evalFeedFwdNet(net, X)
+        # 3. incumbent: the first of equal maxima
+        s = _support_values(Cn, np.asarray(Y, dtype=np.float64))
+        for i in range(nlit):
+            p = int(np.argmax(s[i]))
+            if s[i, p] > L[i]:
+                L[i] = s[i, p]
+                W[i] = X[:, p]
+        # 4. classify
+        thr = L + tol
+        is_open = np.any(ub > thr[:, None], axis=0)
+        for b in np.flatnonzero(~is_open):
+            leaves.append(ReachLeaf(frontier[b].lo, frontier[b].hi, depth, "crown", ub[:, b].copy()))
+        open_ids = [int(b) for b in np.flatnonzero(is_open)]
+        # 5. SDP on the open boxes closest to closing
+        if open_ids and split.sdp_per_level > 0:
+            gap = np.max(ub - thr[:, None], axis=0)
+            order = sorted(open_ids, key=lambda b: (gap[b], b))[:int(split.sdp_per_level)]
+            todo = [(frontier[b], tuple(a[:, b] for a in iv)) for b in order]
+            got = _solve_boxes(net, todo, Cn, thr, beta, opts, split.batch, seconds)
+            sdp_solves += len(order) * nlit
+            for b, res in zip(order, got):
+                for li, (sol, h0) in enumerate(res):
+                    if not ub[li, b] > thr[li]:
+                        continue
+                    rho = float(sol.objective_value) + h0
+                    if sol.termination_status == "TARGET_CERTIFIED" and V.isSolutionGood(sol) and rho <= thr[li]:
+                        ub[li, b] = rho
+                if not np.any(ub[:, b] > thr):
+                    leaves.append(ReachLeaf(frontier[b].lo, frontier[b].hi, depth, "sdp", ub[:, b].copy()))
+                    open_ids.remove(b)
+        # 6. stop or split
+        if not open_ids:
+            return "converged", L, W, leaves, visited, depth, sdp_solves
+        if depth >= split.max_depth or not np.any(splittable) or visited + 2 * len(open_ids) > int(split.max_boxes):
+            for b in open_ids:
+                leaves.append(ReachLeaf(frontier[b].lo, frontier[b].hi, depth, None, ub[:, b].copy()))
+            return "budget", L, W, leaves, visited, depth, sdp_solves
+        nxt = []
+        for b in open_ids:
+            box = frontier[b]
+            j = int(np.argmin(np.where(splittable, box.cuts, np.iinfo(np.int64).max)))     # widest relative to the root, lowest index on ties
+            mid = 0.5 * (box.lo[j] + box.hi[j])
+            cuts = box.cuts.copy()
+            cuts[j] += 1
+            left_hi, right_lo = box.hi.copy(), box.lo.copy()
+            left_hi[j] = mid
+            right_lo[j] = mid
+            a0 = lits.alpha[:, :, b] if split.alpha_steps > 0 and split.alpha_inherit else None
+            nxt.append(_Box(box.lo, left_hi, cuts, alpha0=a0))
+            nxt.append(_Box(right_lo, box.hi, cuts.copy(), alpha0=a0))
+        frontier = nxt
+        visited += len(nxt)
+        depth += 1
+
+
+def findReach2DpolySplit(net: M.FeedFwdNet, x1min, x1max, tol, num_hplanes: int = 6, split: SplitOptions = None):
+    """findReach2Dpoly by input splitting: the normals of findReach2Dpoly (angle 2 pi k / num_hplanes of a two-output network) through
+    reachSplit -> ([(normal, upper_i)], the ReachSplitResult).  The polytope  normal_i' y <= upper_i  contains the reach set, and on
+    "converged" each face is within tol of touching it."""
+    if net.xdims[-1] != 2:
+        raise ValueError("findReach2DpolySplit needs a network with two outputs")
+    normals = np.array([[np.cos(2 * np.pi * i / num_hplanes), np.sin(2 * np.pi * i / num_hplanes)] for i in range(num_hplanes)])
+    res = reachSplit(net, x1min, x1max, normals, tol, split=split)
+    return [(normals[i].copy(), float(res.upper[i])) for i in range(len(normals))], res

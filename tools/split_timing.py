@@ -1,6 +1,12 @@
 #!/usr/bin/env python3
 """Batched CROWN bounds: the GPU kernel against the host routine, and where one verifySplit spends its time.
-usage: python tools/split_timing.py [--nlit | --resident | --alpha | --frontier] [case ...]   cases: W10-D5 W40-D20 acas-shape   (default: all)
+usage: python tools/split_timing.py [--nlit | --resident | --alpha | --frontier | --reach] [case ...]   cases: W10-D5 W40-D20 acas-shape   (default: all)
+With --reach only the reach leg runs and profiles/split_timing_reach_<case>.json is written:
+  reach    one bounds-only reachSplit (crown_backend "resident", corner_points, max_boxes 16384, max_depth 64) with frontier "host" and then
+           "device" in this process; the directions are findReach2Dpoly's six normals on a two-output net, else e_j and -e_j of every
+           output; tol_i = f (upper_i - incumbent_i of the root box alone), f the first of 0.25, 0.1, 0.05, 0.02 at which the host frontier
+           visits at least 1 000 boxes, else the one with the most boxes visited.  Median of 5 runs after 1 warm run: total seconds,
+           seconds["crown"], and for the device frontier the HIP-event time of its kernels; status, visited, levels, worst upper - lower
 With --frontier only the frontier leg runs and profiles/split_timing_frontier_<case>.json is written:
   split    one bounds-only verifySplit (crown_backend "resident", literal_bounds, max_boxes 16384) of the literal
            y_0 - y_last <= s + f (c0 - s) with frontier "host" and then "device" in this process; f is the first of 0.25, 0.1, 0.05, 0.02 at
@@ -199,6 +205,40 @@ def frontier_rows(net, lo, hi, max_boxes=16384):
     return out
 
 
+def reach_rows(net, lo, hi, max_boxes=16384):
+    ny = net.xdims[-1]
+    if ny == 2:
+        Cm = np.array([[np.cos(2 * np.pi * i / 6), np.sin(2 * np.pi * i / 6)] for i in range(6)])
+    else:
+        Cm = np.vstack([np.eye(ny), -np.eye(ny)])
+
+    def run(tol, frontier, mb=max_boxes):
+        return na.reachSplit(net, lo, hi, Cm, tol, split=na.SplitOptions(max_boxes=mb, max_depth=64, sdp_per_level=0, crown_backend="resident",
+                                                                         corner_points=True, frontier=frontier))
+
+    root = run(0.0, "host", 1)
+    gap0 = root.upper - root.incumbent
+    tried = {}
+    for f in (0.25, 0.1, 0.05, 0.02):
+        tried[f] = run(f * gap0, "host").visited
+        if tried[f] >= 1000:
+            break
+    f = f if tried[f] >= 1000 else max(tried, key=tried.get)
+    out = dict(nlit=len(Cm), root_upper=root.upper.tolist(), root_incumbent=root.incumbent.tolist(), f=f, tol=(f * gap0).tolist(), max_boxes=max_boxes,
+               host_visited_per_f={str(k): v for k, v in tried.items()})
+    for frontier in ("host", "device"):
+        runs = [run(f * gap0, frontier) for _ in range(6)][1:]
+        r = runs[0]
+        row = dict(status=r.status, visited=r.visited, leaves=len(r.leaves), levels=1 + r.depth, worst_upper_minus_lower=float(np.max(r.upper - r.lower)),
+                   total_s_median=statistics.median(q.seconds["total"] for q in runs), crown_s_median=statistics.median(q.seconds["crown"] for q in runs))
+        if frontier == "device":
+            row["kernel_s_median"] = statistics.median(q.seconds["kernel"] for q in runs)
+        out[frontier] = row
+        print(frontier, row, flush=True)
+    out["host_over_device_total"] = out["host"]["total_s_median"] / out["device"]["total_s_median"]
+    return out
+
+
 def split_row(net, lo, hi):
     nrm = np.zeros(net.xdims[-1]); nrm[0] = 1.0
     X = lo[:, None] + np.random.default_rng(0).random((len(lo), 20000)) * (hi - lo)[:, None]
@@ -219,12 +259,17 @@ def split_row(net, lo, hi):
 
 if __name__ == "__main__":
     args = sys.argv[1:]
-    lit_leg, res_leg, alpha_leg, frontier_leg = "--nlit" in args, "--resident" in args, "--alpha" in args, "--frontier" in args
-    names = [a for a in args if a not in ("--nlit", "--resident", "--alpha", "--frontier")] or ["W10-D5", "W40-D20", "acas-shape"]
+    lit_leg, res_leg, alpha_leg, frontier_leg, reach_leg = ("--nlit" in args, "--resident" in args, "--alpha" in args, "--frontier" in args,
+                                                            "--reach" in args)
+    names = [a for a in args if a not in ("--nlit", "--resident", "--alpha", "--frontier", "--reach")] or ["W10-D5", "W40-D20", "acas-shape"]
     out_dir = os.environ.get("SPLIT_TIMING_OUT", os.path.join(ROOT, "profiles"))
     os.makedirs(out_dir, exist_ok=True)
     for name in names:
         net, lo, hi = case(name)
+        if reach_leg:
+            with open(os.path.join(out_dir, f"split_timing_reach_{name}.json"), "w") as fh:
+                json.dump(dict(case=name, xdims=net.xdims, **reach_rows(net, lo, hi)), fh, indent=1)
+            continue
         if frontier_leg:
             with open(os.path.join(out_dir, f"split_timing_frontier_{name}.json"), "w") as fh:
                 json.dump(dict(case=name, xdims=net.xdims, **frontier_rows(net, lo, hi)), fh, indent=1)
