@@ -398,7 +398,12 @@ int nnsdp_make_intervals_batch_lits(int32_t K, const int32_t* xdims, const doubl
  * head (uploaded once, at creation), and the box, scratch, output and sample buffers, which grow geometrically when a call exceeds
  * their capacity and never shrink; it owns pinned host staging, one stream and two events.  A bound call is one asynchronous upload
  * of the boxes, one launch, one asynchronous download and one stream synchronisation.
- * ReLU and Tanh networks (the one-shot batched entries stay ReLU-only), every width (xdims[0..K]) <= 64, nlit in 0..64.  The ReLU
+ * ReLU and Tanh networks (the one-shot batched entries stay ReLU-only), every width (xdims[0..K]) <= 64, nlit in 0..64.
+ * Wide handles (nnsdp_crown_create_wide with max_width 128): hidden layers (xdims[1..K-1]) up to 128 wide, on a second instance of the
+ * kernel (csrc/crown_wide.hpp) that walks a pass in slabs of 64 rows x 128 columns; xdims[0], xdims[K] and nlit stay at 64 or below.
+ * It needs 137 KB of LDS - one workgroup per CU where the narrow instance has two - so it is asked for, never chosen.  bound, eval,
+ * search, search_leaves, reach, reach_leaves, info and destroy work on a wide handle as on a narrow one; nnsdp_crown_bound_alpha does
+ * not (the alpha kernel keeps a 64-wide layout).  On a network of widths <= 64 a wide handle returns the narrow handle's bits.  The ReLU
  * kernel is the one-shot entry's arithmetic operation for operation: same bits.  The Tanh kernel restates the host routine's
  * tanh relaxation (csrc/intervals.hpp, tanh_relax) in fp64; the relaxation of a layer is computed once per box, by the pass that
  * produces the layer's pre-activation bounds (csrc/crown_batch.hpp).  A box's bits depend neither on nbox, nor on its position, nor
@@ -411,6 +416,13 @@ typedef struct nnsdp_crown nnsdp_crown;
  * touched. */
 int nnsdp_crown_create(int32_t K, const int32_t* xdims, const double* M, int32_t activ, int32_t nlit, const double* normals,
                        nnsdp_crown** out);
+
+/* nnsdp_crown_create with the widest hidden layer the handle's kernel takes: max_width 64 is nnsdp_crown_create exactly (its checks and
+ * messages); 128 creates a wide handle, which always launches the wide instance, also on a narrow network.
+ * -1 with a message, before the GPU is touched: max_width not 64 or 128; with 128, a hidden width above 128 (the message names the
+ * width and 128), xdims[0] or xdims[K] above 64 (the message names the width and 64); otherwise the refusals of nnsdp_crown_create. */
+int nnsdp_crown_create_wide(int32_t K, const int32_t* xdims, const double* M, int32_t activ, int32_t nlit, const double* normals,
+                            int32_t max_width, nnsdp_crown** out);
 
 /* Bounds of nbox boxes; arguments, layouts and refusals of the boxes as in the one-shot _lits entry (HOST pointers, NULL outputs are
  * skipped, nbox = 0 returns 0; smin / smax / uA / ub0 are left alone by a handle without literals). */
@@ -427,7 +439,7 @@ int nnsdp_crown_bound(nnsdp_crown* h, int32_t nbox, const double* x1min, const d
  * The per-(literal, neuron) state lives in buffers of the handle that are allocated at the first call of this entry, grow like the
  * others and are counted by nnsdp_crown_info; a handle that never calls it holds what it held without it.  No atomics: a literal's
  * bits depend neither on nbox, nor on the box's position, nor on the other literals, nor on earlier calls.
- * -1 with a message, before the GPU is touched, for a Tanh handle, a handle without literals, steps outside 0..64, eta0 not positive
+ * -1 with a message, before the GPU is touched, for a wide handle (max_width 128), a Tanh handle, a handle without literals, steps outside 0..64, eta0 not positive
  * and finite, decay outside (0, 1], or a non-finite alpha0 entry. */
 int nnsdp_crown_bound_alpha(nnsdp_crown* h, int32_t nbox, const double* x1min, const double* x1max,
                             double* acymin, double* acymax, double* acxmin, double* acxmax, double* ymin, double* ymax,
@@ -511,7 +523,7 @@ int nnsdp_crown_reach(nnsdp_crown* h, const double* x1min, const double* x1max, 
 int nnsdp_crown_reach_leaves(nnsdp_crown* h, double* lo, double* hi, int32_t* depth, int32_t* closed, double* bound);
 
 /* what: 0 device allocations made so far, 1 network uploads so far, 2 box capacity, 3 sample capacity, 4 bound calls (a search counts
- * one per chunk), 5 device bytes held, 6 reach searches so far. */
+ * one per chunk), 5 device bytes held, 6 reach searches so far, 7 the handle's max_width (64 or 128). */
 int nnsdp_crown_info(nnsdp_crown* h, int32_t what, double* out);
 
 /* NULL is a no-op returning 0. */

@@ -10,6 +10,7 @@
 #include "intervals.hpp"
 #include "forward.hpp"
 #include "crown_batch.hpp"
+#include "crown_wide.hpp"
 #include "crown_alpha.hpp"
 #include "crown_search.hpp"
 #include "crown_reach.hpp"
@@ -612,6 +613,22 @@ int nnsdp_crown_create(int32_t K, const int32_t* xdims, const double* M, int32_t
   API_END
 }
 
+int nnsdp_crown_create_wide(int32_t K, const int32_t* xdims, const double* M, int32_t activ, int32_t nlit, const double* normals,
+                            int32_t max_width, nnsdp_crown** out) {
+  API_BEGIN
+  if (!out) throw std::invalid_argument("null argument");
+  *out = nullptr;
+  if (K < 2 || !xdims || !M) throw std::invalid_argument("null / empty network (K >= 2 layers are needed)");
+  if (activ != NNSDP_ACTIV_RELU && activ != NNSDP_ACTIV_TANH) throw std::invalid_argument("unknown activation");
+  nnsdp_crown::check_widths_wide(K, xdims, max_width);
+  check_literals(xdims[K], nlit, normals);
+  require_gpu();
+  std::unique_ptr<nnsdp_crown> h(new nnsdp_crown);
+  h->create(K, xdims, M, activ, nlit, normals, max_width);
+  *out = h.release();
+  API_END
+}
+
 int nnsdp_crown_bound(nnsdp_crown* h, int32_t nbox, const double* x1min, const double* x1max,
                       double* acymin, double* acymax, double* acxmin, double* acxmax, double* ymin, double* ymax,
                       double* smin, double* smax, double* uA, double* ub0, double* kernel_ms) {
@@ -698,7 +715,8 @@ int nnsdp_crown_info(nnsdp_crown* h, int32_t what, double* out) {
     case 4: *out = (double)h->n_bound; break;
     case 5: *out = (double)h->device_bytes(); break;
     case 6: *out = (double)h->n_reach; break;
-    default: throw std::invalid_argument("nnsdp_crown_info: what must be in 0..6");
+    case 7: *out = (double)h->max_width; break;
+    default: throw std::invalid_argument("nnsdp_crown_info: what must be in 0..7");
   }
   API_END
 }

@@ -30,6 +30,7 @@ static void check_alpha0(const double* alpha0, size_t count) {
 // ---------------------------------------------------------------------------------------------
 struct nnsdp_crown {
   int K = 0, activ = 0, nlit = 0, acdim = 0, n0 = 0, ny = 0, wp = 0;
+  int max_width = nnsdp::kCbW;           // 64: k_crown_resident; 128: k_crown_wide (crown_wide.hpp), also on a narrow network
   std::vector<long long> moff;
   DBuf<int> dxd, dao;
   DBuf<long long> dmo;
@@ -71,8 +72,15 @@ struct nnsdp_crown {
   size_t ain_per_box() const { return 2 * (size_t)n0 + layout(1).nst(); }
   size_t aout_per_box() const { return layout(1).alpha_total(); }
   size_t ast_per_box() const { return 3 * layout(1).nst(); }
-  size_t lds_bytes() const { return activ == NNSDP_ACTIV_TANH ? kCbLdsBytesTanh : kCbLdsBytes; }
+  bool wide() const { return max_width > nnsdp::kCbW; }
+  size_t lds_bytes() const {
+    if (wide()) return activ == NNSDP_ACTIV_TANH ? kCwLdsBytesTanh : kCwLdsBytes;
+    return activ == NNSDP_ACTIV_TANH ? kCbLdsBytesTanh : kCbLdsBytes;
+  }
   const void* kernel() const {
+    if (wide())
+      return activ == NNSDP_ACTIV_TANH ? reinterpret_cast<const void*>(&k_crown_wide<kCbTanh>)
+                                       : reinterpret_cast<const void*>(&k_crown_wide<kCbRelu>);
     return activ == NNSDP_ACTIV_TANH ? reinterpret_cast<const void*>(&k_crown_resident<kCbTanh>)
                                      : reinterpret_cast<const void*>(&k_crown_resident<kCbRelu>);
   }
@@ -141,6 +149,21 @@ struct nnsdp_crown {
         throw std::invalid_argument("layer width " + std::to_string(xdims[k]) + " is above 64, the widest layer of the batched intervals");
     }
   }
+  // the width refusals of nnsdp_crown_create_wide: max_width 64 is check_widths; 128 lets the hidden layers go up to 128
+  static void check_widths_wide(int K, const int32_t* xdims, int max_width) {
+    if (max_width != nnsdp::kCbW && max_width != nnsdp::kCwCols)
+      throw std::invalid_argument("max_width must be 64 or 128, got " + std::to_string(max_width));
+    if (max_width == nnsdp::kCbW) return check_widths(K, xdims);
+    for (int k = 0; k <= K; ++k) {
+      if (xdims[k] < 1) throw std::invalid_argument("layer widths must be >= 1");
+      const bool end = k == 0 || k == K;
+      if (end && xdims[k] > nnsdp::kCwRows)
+        throw std::invalid_argument((k == 0 ? "input width " : "output width ") + std::to_string(xdims[k]) +
+                                    " is above 64, the widest input and output of the wide bounder (only hidden layers go up to 128)");
+      if (!end && xdims[k] > nnsdp::kCwCols)
+        throw std::invalid_argument("layer width " + std::to_string(xdims[k]) + " is above 128, the widest hidden layer of the wide bounder");
+    }
+  }
   // M, then the literal head behind it, into dM (net.mlen() + net.head_len(nlit) doubles)
   static void upload_network(double* dM, const nnsdp::NetLayout& net, const int32_t* xdims, const double* M, int nlit, const double* normals) {
     HIPCHK(hipMemcpy(dM, M, net.mlen() * sizeof(double), hipMemcpyHostToDevice));
@@ -149,8 +172,9 @@ struct nnsdp_crown {
       HIPCHK(hipMemcpy(dM + net.mlen(), head.H.data(), net.head_len(nlit) * sizeof(double), hipMemcpyHostToDevice));
     }
   }
-  void create(int K_, const int32_t* xdims, const double* M, int activ_, int nlit_, const double* normals_) {
+  void create(int K_, const int32_t* xdims, const double* M, int activ_, int nlit_, const double* normals_, int max_width_ = nnsdp::kCbW) {
     const nnsdp::NetLayout net(K_, xdims);
+    max_width = max_width_;
     K = K_; activ = activ_; nlit = nlit_; acdim = net.acdim(); n0 = net.n0(); ny = net.ny(); wp = net.wp; moff = net.moff;
     if (nlit > 0) normals.assign(normals_, normals_ + (size_t)nlit * ny);
     dxd.upload(net.xd); dao.upload(net.acoff); dmo.upload(net.moff);
@@ -158,7 +182,7 @@ struct nnsdp_crown {
     n_alloc += 4;
     upload_network(dM.p, net, xdims, M, nlit, normals_);
     ++n_upload;
-    // (k_forward_mfma needs no attribute here: widths <= 64 keep its LDS at 2 * 68 * 16 doubles)
+    // (k_forward_mfma needs no attribute here: widths <= 128 keep its LDS at 2 * 132 * 16 doubles, 33.8 KB)
     HIPCHK(hipFuncSetAttribute(kernel(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes()));
     HIPCHK(hipStreamCreate(&st));
     HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
@@ -173,7 +197,11 @@ struct nnsdp_crown {
     return a;
   }
   void launch_bound(const nnsdp::CrownArgs& a, size_t nbox) {
-    if (activ == NNSDP_ACTIV_TANH)
+    if (wide() && activ == NNSDP_ACTIV_TANH)
+      hipLaunchKernelGGL(nnsdp::k_crown_wide<nnsdp::kCbTanh>, dim3((unsigned)nbox), dim3(256), nnsdp::kCwLdsBytesTanh, st, a);
+    else if (wide())
+      hipLaunchKernelGGL(nnsdp::k_crown_wide<nnsdp::kCbRelu>, dim3((unsigned)nbox), dim3(256), nnsdp::kCwLdsBytes, st, a);
+    else if (activ == NNSDP_ACTIV_TANH)
       hipLaunchKernelGGL(nnsdp::k_crown_resident<nnsdp::kCbTanh>, dim3((unsigned)nbox), dim3(256), nnsdp::kCbLdsBytesTanh, st, a);
     else
       hipLaunchKernelGGL(nnsdp::k_crown_resident<nnsdp::kCbRelu>, dim3((unsigned)nbox), dim3(256), nnsdp::kCbLdsBytes, st, a);
@@ -220,6 +248,7 @@ struct nnsdp_crown {
   void bound_alpha(int32_t nbox, const double* x1min, const double* x1max, double* const host[nnsdp::CrownLayout::kSegs], double* kernel_ms,
                    int32_t steps, double eta0, double decay, const double* alpha0,
                    double* a_smax, double* a_uA, double* a_ub0, double* alpha, int32_t* best_step) {
+    if (wide()) throw std::invalid_argument("optimised slopes (alpha) are not available on a wide bounder (max_width 128): the alpha kernel keeps a 64-wide layout");
     if (activ != NNSDP_ACTIV_RELU) throw std::invalid_argument("optimised slopes (alpha) are for ReLU networks, not Tanh");
     if (nlit < 1) throw std::invalid_argument("optimised slopes (alpha) need literals: the handle was created without normals");
     check_alpha_options(steps, eta0, decay);

@@ -101,6 +101,7 @@ SYMBOLS = [
     ("nnsdp_make_intervals_lits", C.c_int, [C.c_int32, c_int32_p, c_double_p, C.c_int32, c_double_p, c_double_p] + [c_double_p] * 8
      + [C.c_int32, c_double_p] + [c_double_p] * 4),
     ("nnsdp_crown_create", C.c_int, [C.c_int32, c_int32_p, c_double_p, C.c_int32, C.c_int32, c_double_p, C.POINTER(C.c_void_p)]),
+    ("nnsdp_crown_create_wide", C.c_int, [C.c_int32, c_int32_p, c_double_p, C.c_int32, C.c_int32, c_double_p, C.c_int32, C.POINTER(C.c_void_p)]),
     ("nnsdp_crown_bound", C.c_int, [C.c_void_p, C.c_int32, c_double_p, c_double_p] + [c_double_p] * 11),
     ("nnsdp_crown_bound_alpha", C.c_int, [C.c_void_p, C.c_int32, c_double_p, c_double_p] + [c_double_p] * 11
      + [C.c_int32, C.c_double, C.c_double] + [c_double_p] * 5 + [c_int32_p]),

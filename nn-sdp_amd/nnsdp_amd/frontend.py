@@ -373,12 +373,20 @@ class CrownBounder:
     """makeIntervalsBatch(backend="gpu") and evalFeedFwdNetBatch for many calls on one network (the nnsdp_crown handle of include/nnsdp.h):
     the network, the literal head of `normals` (nlit x xdims[K], nlit <= 64) and every device buffer stay on the GPU until close().
     ReLU and Tanh networks with every width <= 64; anything else raises (no fall-back to the host).  The ReLU results have the bits of
-    makeIntervalsBatch(backend="gpu"); the Tanh kernel exists only here.  A context manager; not thread-safe."""
+    makeIntervalsBatch(backend="gpu"); the Tanh kernel exists only here.
+    max_width=128 (nnsdp_crown_create_wide) asks for the wide instance of the kernel (csrc/crown_wide.hpp): hidden layers up to 128
+    wide, while xdims[0], xdims[K] and nlit stay at 64 or below.  It runs one workgroup per CU where the narrow one runs two, so it is
+    never chosen silently; on a network of widths <= 64 it returns the bits of the narrow instance.  bound, eval, search, reach and info
+    work on it; optimised slopes (alpha_steps, alpha0) do not - the alpha kernel keeps its 64-wide layout - and raise ValueError.
+    A context manager; not thread-safe."""
 
     _INFO = ("device_allocations", "network_uploads", "box_capacity", "sample_capacity", "bound_calls", "device_bytes", "reach_calls")
 
-    def __init__(self, net: M.FeedFwdNet, normals=None):
+    def __init__(self, net: M.FeedFwdNet, normals=None, max_width: int = 64):
         self._h = None
+        if max_width not in (64, 128):
+            raise ValueError("max_width must be 64 or 128")
+        self._max_width = int(max_width)
         self._lib = _lib.load()
         self.net = net
         xd, Mp = _net_arrays(net)
@@ -390,9 +398,19 @@ class CrownBounder:
                 raise ValueError("normals must be nlit x xdims[K]")
             self._nlit, nrp = nrm.shape[0], nrm.ctypes.data_as(_lib.c_double_p)
         h = C.c_void_p()
-        _lib.check(self._lib.nnsdp_crown_create(net.K, xd.ctypes.data_as(_lib.c_int32_p), Mp.ctypes.data_as(_lib.c_double_p),
-                                                M._activ_code(net.activ), self._nlit or 0, nrp, C.byref(h)))
+        args = (net.K, xd.ctypes.data_as(_lib.c_int32_p), Mp.ctypes.data_as(_lib.c_double_p), M._activ_code(net.activ), self._nlit or 0, nrp)
+        if self._max_width == 64:
+            _lib.check(self._lib.nnsdp_crown_create(*args, C.byref(h)))
+        else:
+            _lib.check(self._lib.nnsdp_crown_create_wide(*args, self._max_width, C.byref(h)))
         self._h = h
+
+    @property
+    def max_width(self) -> int:
+        """the widest hidden layer the handle's kernel takes (nnsdp_crown_info 7): 64, or 128 for the wide instance"""
+        v = C.c_double(0.0)
+        _lib.check(self._lib.nnsdp_crown_info(self._handle(), 7, C.byref(v)))
+        return int(v.value)
 
     def _handle(self):
         if self._h is None:
@@ -419,6 +437,8 @@ class CrownBounder:
             louts = [np.zeros((nbox, nl)), np.zeros((nbox, nl)), np.zeros((nbox, nl, self._n0)), np.zeros((nbox, nl))]    # smin, smax, uA, ub0
         ms = C.c_double(0.0)
         if alpha_steps != 0 or alpha0 is not None:
+            if self._max_width != 64:
+                raise ValueError("optimised slopes (alpha_steps, alpha0) are not available on a wide bounder (max_width=128)")
             steps, eta0, decay, a0 = _alpha_args(alpha_steps, alpha0, eta0, decay, self._nlit, self._acdim, nbox)
             aouts, step = _alpha_outs(nbox, self._nlit, self._n0, self._acdim)
             _lib.check(self._lib.nnsdp_crown_bound_alpha(h, nbox, loc.ctypes.data_as(dp), hic.ctypes.data_as(dp),

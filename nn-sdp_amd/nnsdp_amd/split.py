@@ -74,6 +74,10 @@ class SplitOptions:
     # chunk: boxes per launch of the bound kernel, which bounds the device memory of a level's interval arrays
     frontier: str = "host"
     chunk: int = 4096
+    # the widest hidden layer of the CrownBounder of crown_backend "resident": 64, or 128 for the wide instance of the kernel
+    # (csrc/crown_wide.hpp: one workgroup per CU instead of two, so it is asked for; xdims[0], xdims[K] and the literals stay at 64).
+    # 128 needs crown_backend "resident" and alpha_steps = 0 (the alpha kernel keeps a 64-wide layout); both frontiers take it
+    crown_max_width: int = 64
 
 
 @dataclass
@@ -170,6 +174,23 @@ def _solve_boxes(net, todo, normals, hs, beta: int, opts: M.AdmmSdpOptions, batc
     return out
 
 
+def _check_crown_max_width(split: SplitOptions) -> None:
+    if split.crown_max_width not in (64, 128):
+        raise ValueError("crown_max_width must be 64 or 128")
+    if split.crown_max_width == 128:
+        if split.crown_backend != "resident":
+            raise ValueError("crown_max_width 128 needs crown_backend 'resident'")
+        if split.alpha_steps > 0:
+            raise ValueError("crown_max_width 128 needs alpha_steps == 0")
+
+
+def _crown_bounder(net, normals, split: SplitOptions):
+    """the CrownBounder of crown_backend "resident": the call of before at the default width, max_width only when it is asked for"""
+    if split.crown_max_width == 64:
+        return F.CrownBounder(net, normals)
+    return F.CrownBounder(net, normals, max_width=split.crown_max_width)
+
+
 def verifySplit(net: M.FeedFwdNet, x1min, x1max, literals: Sequence[Tuple[Any, float]], beta: int, opts: M.AdmmSdpOptions,
                 split: SplitOptions = None) -> SplitResult:
     """Decide the clause  OR_i normal_i' f(x) <= h_i  on the box [x1min, x1max]: "holds" when every leaf of the bisection tree has
@@ -196,6 +217,7 @@ def verifySplit(net: M.FeedFwdNet, x1min, x1max, literals: Sequence[Tuple[Any, f
             raise ValueError("frontier 'device' needs samples == 0")
         if split.alpha_steps != 0:
             raise ValueError("frontier 'device' needs alpha_steps == 0")
+    _check_crown_max_width(split)
     t_start = time.perf_counter()
     root_lo, root_hi = np.array(x1min, dtype=np.float64), np.array(x1max, dtype=np.float64)
     n0, ny = net.xdims[0], net.xdims[-1]
@@ -210,7 +232,7 @@ def verifySplit(net: M.FeedFwdNet, x1min, x1max, literals: Sequence[Tuple[Any, f
     seconds = {"crown": 0.0, "setup": 0.0, "solve": 0.0, "finish": 0.0, "total": 0.0}
     frontier = [_Box(root_lo, root_hi, np.zeros(n0, dtype=np.int64))]
     want_lits = split.literal_bounds or split.corner_points
-    bounder = F.CrownBounder(net, normals if want_lits else None) if split.crown_backend == "resident" else None
+    bounder = _crown_bounder(net, normals if want_lits else None, split) if split.crown_backend == "resident" else None
     try:
         if split.frontier == "device":
             return _split_device(net, root_lo, root_hi, normals, hs, beta, opts, split, bounder, want_lits, seconds, t_start)
@@ -450,6 +472,7 @@ def reachSplit(net: M.FeedFwdNet, x1min, x1max, normals, tol, beta: int = 0, opt
             raise ValueError("frontier 'device' needs alpha_steps == 0")
         if split.sdp_per_level != 0:
             raise ValueError("frontier 'device' of reachSplit needs sdp_per_level == 0")
+    _check_crown_max_width(split)
     if int(split.max_boxes) < 1:
         raise ValueError("max_boxes must be >= 1")
     t_start = time.perf_counter()
@@ -467,7 +490,7 @@ def reachSplit(net: M.FeedFwdNet, x1min, x1max, normals, tol, beta: int = 0, opt
     if tol.shape != (nlit,) or not np.all(np.isfinite(tol)) or not np.all(tol >= 0.0):
         raise ValueError("tol must be a scalar or nlit values, finite and >= 0")
     seconds = {"crown": 0.0, "setup": 0.0, "solve": 0.0, "finish": 0.0, "total": 0.0}
-    bounder = F.CrownBounder(net, Cn) if split.crown_backend == "resident" else None
+    bounder = _crown_bounder(net, Cn, split) if split.crown_backend == "resident" else None
     try:
         if split.frontier == "device":
             res = _reach_device(root_lo, root_hi, tol, split, bounder, seconds)

@@ -1,6 +1,12 @@
 #!/usr/bin/env python3
 """Batched CROWN bounds: the GPU kernel against the host routine, and where one verifySplit spends its time.
-usage: python tools/split_timing.py [--nlit | --resident | --alpha | --frontier | --reach] [case ...]   cases: W10-D5 W40-D20 acas-shape   (default: all)
+usage: python tools/split_timing.py [--nlit | --resident | --alpha | --frontier | --reach | --wide] [case ...]   cases: W10-D5 W40-D20 acas-shape   (default: all)
+With --wide only the wide leg runs (cases W40-D20, acas-shape - the 5-50x6-5 net - and 5-100x4-5 by default) and
+profiles/split_timing_wide_<case>.json is written:
+  bound    CrownBounder(max_width=128).bound at nbox = 1, 256, 4096: HIP-event time of the launch and wall-clock of the call, median of 7
+           after 2 warm calls.  On a net of widths <= 64 beside CrownBounder(max_width=64).bound in the same process - what the slab loop and
+           one workgroup per CU instead of two cost; on a wider net beside makeIntervalsBatch(backend="host") with 1 and 16 workers on the
+           same boxes, wall-clock, one run (the 1-worker run on at most 256 boxes, scaled to nbox) - the only other route there
 With --reach only the reach leg runs and profiles/split_timing_reach_<case>.json is written:
   reach    one bounds-only reachSplit (crown_backend "resident", corner_points, max_boxes 16384, max_depth 64) with frontier "host" and then
            "device" in this process; the directions are findReach2Dpoly's six normals on a two-output net, else e_j and -e_j of every
@@ -45,6 +51,8 @@ def case(name):
         z = np.load(os.path.join(helpers.GOLDEN, "nets", f"scale-I2-O2-{name}.npz"))
         xdims = [int(v) for v in z["xdims"]]
         return na.FeedFwdNet(xdims=xdims, Ms=[np.array(z[f"M{k}"], dtype=np.float64) for k in range(len(xdims) - 1)]), np.full(2, 0.5), np.full(2, 1.5)
+    if name == "5-100x4-5":
+        return na.randomNetwork([5] + [100] * 4 + [5], seed=1234), np.full(5, 0.25), np.full(5, 0.35)
     if name == "acas-shape":
         return na.randomNetwork([5] + [50] * 6 + [5], seed=1234), np.full(5, 0.25), np.full(5, 0.35)
     raise SystemExit(f"unknown case {name}")
@@ -137,6 +145,29 @@ def resident_rows(net, lo, hi):
         split[backend] = dict(verdict=r.verdict, visited=r.visited, leaves=len(r.leaves), seconds=r.seconds)
         print(backend, split[backend], flush=True)
     return dict(bound=bound, eval=ev, handle=info, h=h, split=split)
+
+
+def wide_rows(net, lo, hi):
+    narrow_fits = max(net.xdims) <= 64
+    rows = []
+    with na.CrownBounder(net, max_width=128) as wd:
+        for nbox in (1, 256, 4096):
+            blo, bhi = sub_boxes(lo, hi, nbox)
+            ww, wk = _timed(lambda: wd.bound(blo, bhi, return_ms=True))
+            row = dict(nbox=nbox, wide_call_ms_median=ww, wide_kernel_ms_median=wk)
+            if narrow_fits:
+                with na.CrownBounder(net) as nr:
+                    nw, nk = _timed(lambda: nr.bound(blo, bhi, return_ms=True))
+                row.update(narrow_call_ms_median=nw, narrow_kernel_ms_median=nk, wide_kernel_over_narrow=wk / nk)
+            else:
+                n1 = min(nbox, 256)
+                t = time.perf_counter(); na.makeIntervalsBatch(net, blo[:, :n1], bhi[:, :n1], backend="host", workers=1); h1 = 1e3 * (time.perf_counter() - t) * nbox / n1
+                t = time.perf_counter(); na.makeIntervalsBatch(net, blo, bhi, backend="host", workers=16); h16 = 1e3 * (time.perf_counter() - t)
+                row.update(host_1_worker_ms=h1, host_1_worker_boxes_timed=n1, host_16_workers_ms=h16, wide_call_over_host_16=ww / h16,
+                           wide_kernel_over_host_16=wk / h16)
+            rows.append(row)
+            print(row, flush=True)
+    return rows
 
 
 def alpha_rows(net, lo, hi, nbox=256):
@@ -259,13 +290,18 @@ def split_row(net, lo, hi):
 
 if __name__ == "__main__":
     args = sys.argv[1:]
-    lit_leg, res_leg, alpha_leg, frontier_leg, reach_leg = ("--nlit" in args, "--resident" in args, "--alpha" in args, "--frontier" in args,
-                                                            "--reach" in args)
-    names = [a for a in args if a not in ("--nlit", "--resident", "--alpha", "--frontier", "--reach")] or ["W10-D5", "W40-D20", "acas-shape"]
+    lit_leg, res_leg, alpha_leg, frontier_leg, reach_leg, wide_leg = ("--nlit" in args, "--resident" in args, "--alpha" in args, "--frontier" in args,
+                                                                      "--reach" in args, "--wide" in args)
+    names = [a for a in args if a not in ("--nlit", "--resident", "--alpha", "--frontier", "--reach", "--wide")] or \
+        (["W40-D20", "acas-shape", "5-100x4-5"] if wide_leg else ["W10-D5", "W40-D20", "acas-shape"])
     out_dir = os.environ.get("SPLIT_TIMING_OUT", os.path.join(ROOT, "profiles"))
     os.makedirs(out_dir, exist_ok=True)
     for name in names:
         net, lo, hi = case(name)
+        if wide_leg:
+            with open(os.path.join(out_dir, f"split_timing_wide_{name}.json"), "w") as fh:
+                json.dump(dict(case=name, xdims=net.xdims, bound=wide_rows(net, lo, hi)), fh, indent=1)
+            continue
         if reach_leg:
             with open(os.path.join(out_dir, f"split_timing_reach_{name}.json"), "w") as fh:
                 json.dump(dict(case=name, xdims=net.xdims, **reach_rows(net, lo, hi)), fh, indent=1)
