@@ -489,6 +489,43 @@ int nnsdp_crown_search(nnsdp_crown* h, const double* x1min, const double* x1max,
  * meaningless), else the proved literal, or the best literal of an open box, with its bound. */
 int nnsdp_crown_search_leaves(nnsdp_crown* h, double* lo, double* hi, int32_t* depth, int32_t* proved, int32_t* literal, double* bound);
 
+/* nnsdp_crown_search for nroot root boxes in ONE level loop (csrc/crown_forest.hpp): the same network and normals, root r the box
+ * x1min / x1max column r (xdims[0] x nroot column-major) with the thresholds hs column r (nlit x nroot column-major), its own
+ * splittable coordinates, and max_boxes / max_depth applied to it alone.  Level d of every root that is still undecided forms one
+ * frontier in device memory, ordered by root, so one pass of launches (the bound kernel on chunks of at most `chunk` boxes, which
+ * may cross root boundaries), one synchronisation and one read-back of three integers per undecided root serve all of them; a
+ * decided root leaves the frontier.  Per root the outputs (verdict, visited, depth_reached, nleaves: nroot each; witness: xdims[0] x
+ * nroot, column r written when root r is violated) and the leaves are those of nnsdp_crown_search on that root alone, bit for bit and
+ * in the same order.  A root's level beyond its budget is bounded with the others and thrown away; visited does not count it.
+ * confirm: as in nnsdp_crown_search, with the index of the root whose candidate it is; per root in that entry's order.
+ * kernel_ms (may be NULL): event time of all launches.
+ * Memory: the roots are handled in groups that share one set of buffers, one group after the other; a group is the largest number of
+ * roots whose frontier buffers, point and leaf-log buffers and record buffers each stay within 2^31 bytes (nnsdp_crown_forest_plan
+ * states the rule), or `group` when that is positive and smaller.  The results do not depend on the grouping.  The buffers are the
+ * forest's own, allocated at the first call and reused by a later call that needs no more; counted by nnsdp_crown_info, where every
+ * launch of the bound kernel counts as a bound call.
+ * -1 with a message: max_boxes < 1, chunk < 1, max_depth < 0, group < 0, nroot < 0 (in this order, before the handle is used; nroot
+ * = 0 then returns 0 at once), a null handle or argument, the clause refusals of nnsdp_crown_search, a non-finite threshold (the
+ * message names the root and the literal) or box entry or x1min > x1max (it names the root), one root whose buffers exceed 2^31
+ * bytes (it gives the byte count).  Not thread-safe. */
+typedef int32_t (*nnsdp_confirm_many_fn)(void* user, int32_t root, const double* x);
+int nnsdp_crown_search_many(nnsdp_crown* h, int32_t nroot, const double* x1min, const double* x1max, int32_t nlit, const double* normals,
+                            const double* hs, int32_t literal_bounds, int32_t corner_points, int32_t max_boxes, int32_t max_depth,
+                            int32_t chunk, int32_t group, nnsdp_confirm_many_fn confirm, void* user, int32_t* verdict, int32_t* visited,
+                            int32_t* depth_reached, int32_t* nleaves, double* witness, double* kernel_ms);
+
+/* The leaves of root `root` of the handle's last nnsdp_crown_search_many, as nnsdp_crown_search_leaves gives them; root = -1: the
+ * leaves of all roots, one root after the other (the sum of nleaves entries). */
+int nnsdp_crown_search_many_leaves(nnsdp_crown* h, int32_t root, double* lo, double* hi, int32_t* depth, int32_t* proved, int32_t* literal,
+                                   double* bound);
+
+/* The grouping rule of nnsdp_crown_search_many, without a handle or a GPU: for input width n0, output width ny, nlit literals,
+ * max_boxes, corner_points, nroot roots and the `group` argument, out[0] = roots per group, out[1] = boxes a level of the group can
+ * hold (2 max_boxes per root; at most 2^26, the longest level of the scan), out[2] = bytes of the two frontiers, out[3] = bytes of the
+ * point and leaf-log buffers, out[4] = bytes of the record buffers.  -1 with the byte count when one root does not fit. */
+int nnsdp_crown_forest_plan(int32_t n0, int32_t ny, int32_t nlit, int32_t max_boxes, int32_t corner_points, int32_t nroot, int32_t group,
+                            int64_t* out);
+
 /* The reach search of nnsdp_amd/split.py (reachSplit, _reach_levels with sdp_per_level = 0) with the frontier kept on the device
  * (csrc/crown_reach.hpp): encloses the support values  max_x c_i' f(x)  of the handle's nlit directions c_i over the root box
  * x1min / x1max (xdims[0] each) by branch and bound with an incumbent, on ONE bisection tree for all directions.  Per level: the
@@ -522,8 +559,8 @@ int nnsdp_crown_reach(nnsdp_crown* h, const double* x1min, const double* x1max, 
  * nleaves, bound nlit x nleaves, column-major): closed 1 ("crown") or 0 (open: the budget ended the search); bound: ub of every direction. */
 int nnsdp_crown_reach_leaves(nnsdp_crown* h, double* lo, double* hi, int32_t* depth, int32_t* closed, double* bound);
 
-/* what: 0 device allocations made so far, 1 network uploads so far, 2 box capacity, 3 sample capacity, 4 bound calls (a search counts
- * one per chunk), 5 device bytes held, 6 reach searches so far, 7 the handle's max_width (64 or 128). */
+/* what: 0 device allocations made so far, 1 network uploads so far, 2 box capacity, 3 sample capacity, 4 bound calls (a search and a
+ * search_many count one per chunk), 5 device bytes held, 6 reach searches so far, 7 the handle's max_width (64 or 128). */
 int nnsdp_crown_info(nnsdp_crown* h, int32_t what, double* out);
 
 /* NULL is a no-op returning 0. */

@@ -13,6 +13,7 @@
 #include "crown_wide.hpp"
 #include "crown_alpha.hpp"
 #include "crown_search.hpp"
+#include "crown_forest.hpp"
 #include "crown_reach.hpp"
 #include "solver.hpp"
 #include "batch.hpp"
@@ -679,6 +680,50 @@ int nnsdp_crown_search_leaves(nnsdp_crown* h, double* lo, double* hi, int32_t* d
   std::copy(L.proved.begin(), L.proved.end(), proved);
   std::copy(L.literal.begin(), L.literal.end(), literal);
   std::copy(L.bound.begin(), L.bound.end(), bound);
+  API_END
+}
+
+int nnsdp_crown_search_many(nnsdp_crown* h, int32_t nroot, const double* x1min, const double* x1max, int32_t nlit, const double* normals,
+                            const double* hs, int32_t literal_bounds, int32_t corner_points, int32_t max_boxes, int32_t max_depth,
+                            int32_t chunk, int32_t group, nnsdp_confirm_many_fn confirm, void* user, int32_t* verdict, int32_t* visited,
+                            int32_t* depth_reached, int32_t* nleaves, double* witness, double* kernel_ms) {
+  API_BEGIN
+  nnsdp_crown::search_many(h, nroot, x1min, x1max, nlit, normals, hs, literal_bounds, corner_points, max_boxes, max_depth, chunk, group,
+                           confirm, user, verdict, visited, depth_reached, nleaves, witness, kernel_ms);
+  API_END
+}
+
+int nnsdp_crown_search_many_leaves(nnsdp_crown* h, int32_t root, double* lo, double* hi, int32_t* depth, int32_t* proved, int32_t* literal,
+                                   double* bound) {
+  API_BEGIN
+  if (!h) throw std::invalid_argument("null handle");
+  const int32_t nroot = (int32_t)h->fleaves.size();
+  if (root < -1 || root >= nroot)
+    throw std::invalid_argument("root must be -1 or in 0.." + std::to_string(nroot - 1) + " (the roots of the last search_many), got " + std::to_string(root));
+  for (int32_t r = root < 0 ? 0 : root; r < (root < 0 ? nroot : root + 1); ++r) {
+    const nnsdp_crown::SearchLeaves& L = h->fleaves[(size_t)r];
+    if (L.depth.empty()) continue;
+    if (!lo || !hi || !depth || !proved || !literal || !bound) throw std::invalid_argument("null argument");
+    lo = std::copy(L.lo.begin(), L.lo.end(), lo);
+    hi = std::copy(L.hi.begin(), L.hi.end(), hi);
+    depth = std::copy(L.depth.begin(), L.depth.end(), depth);
+    proved = std::copy(L.proved.begin(), L.proved.end(), proved);
+    literal = std::copy(L.literal.begin(), L.literal.end(), literal);
+    bound = std::copy(L.bound.begin(), L.bound.end(), bound);
+  }
+  API_END
+}
+
+int nnsdp_crown_forest_plan(int32_t n0, int32_t ny, int32_t nlit, int32_t max_boxes, int32_t corner_points, int32_t nroot, int32_t group,
+                            int64_t* out) {
+  API_BEGIN
+  if (!out) throw std::invalid_argument("null argument");
+  if (n0 < 1 || ny < 1 || nlit < 1) throw std::invalid_argument("n0, ny and nlit must be >= 1");
+  if (max_boxes < 1) throw std::invalid_argument("max_boxes must be >= 1, got " + std::to_string(max_boxes));
+  if (group < 0) throw std::invalid_argument("group must be >= 0 (0: derived from the memory cap), got " + std::to_string(group));
+  if (nroot < 1) throw std::invalid_argument("nroot must be >= 1, got " + std::to_string(nroot));
+  const nnsdp::ForestPlan P = nnsdp_crown::forest_group_plan(n0, ny, nlit, max_boxes, corner_points, nroot, group);
+  out[0] = (int64_t)P.group; out[1] = (int64_t)P.cap; out[2] = (int64_t)P.frontier_bytes; out[3] = (int64_t)P.double_bytes; out[4] = (int64_t)P.int_bytes;
   API_END
 }
 

@@ -65,6 +65,14 @@ struct nnsdp_crown {
     std::vector<int32_t> depth, closed;
     void clear() { lo.clear(); hi.clear(); bound.clear(); depth.clear(); closed.clear(); }
   } rleaves;
+  // nnsdp_crown_search_many only (nothing before its first call): the two frontiers of a group of roots with the root of every box, the
+  // records / points / leaf logs / per-root tables (csrc/crown_forest.hpp, ForestPlan), the pinned copy of a level's table and counts;
+  // the leaves of the last call, per root
+  DBuf<double> ffr, fdb;
+  DBuf<int> fcu, fib;
+  int* hforest = nullptr;
+  size_t hforest_cap = 0;
+  std::vector<SearchLeaves> fleaves;
 
   size_t scr_per_box() const { return (size_t)(activ == NNSDP_ACTIV_TANH ? 6 : 2) * acdim; }
   nnsdp::CrownLayout layout(size_t nbox) const { return nnsdp::CrownLayout{nbox, (size_t)n0, (size_t)acdim, (size_t)ny, (size_t)nlit}; }
@@ -92,7 +100,7 @@ struct nnsdp_crown {
   size_t device_bytes() const {
     return dxd.bytes() + dao.bytes() + dmo.bytes() + dM.bytes() + din.bytes() + dscr.bytes() + dout.bytes() + dX.bytes() + dY.bytes() +
            dain.bytes() + daout.bytes() + dast.bytes() + sfr.bytes() + sdb.bytes() + scu.bytes() + sib.bytes() +
-           rfr.bytes() + rdb.bytes() + rcu.bytes() + rib.bytes();
+           rfr.bytes() + rdb.bytes() + rcu.bytes() + rib.bytes() + ffr.bytes() + fdb.bytes() + fcu.bytes() + fib.bytes();
   }
   // the capacity grows geometrically and never shrinks
   // staging = false (a search: nothing of a box crosses the bus): the pinned copies wait for the next bound call
@@ -132,6 +140,18 @@ struct nnsdp_crown {
     if (nd > rdb.n) dalloc(rdb, nd);
     if (ni > rib.n) { rib.alloc(ni); ++n_alloc; }
     if (!hstatus) HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&hstatus), 4 * sizeof(int), hipHostMallocDefault));
+  }
+  // the buffers of a forest search (one group of roots): they only grow
+  void reserve_forest(const nnsdp::ForestPlan& p) {
+    if (4 * p.cap * n0 > ffr.n) dalloc(ffr, 4 * p.cap * n0);
+    if (2 * p.cap * (n0 + 1) > fcu.n) { fcu.alloc(2 * p.cap * (n0 + 1)); ++n_alloc; }
+    if (p.nd > fdb.n) dalloc(fdb, p.nd);
+    if (p.ni > fib.n) { fib.alloc(p.ni); ++n_alloc; }
+    if (8 * p.group > hforest_cap) {
+      if (hforest) { HIPCHK(hipHostFree(hforest)); hforest = nullptr; }
+      HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&hforest), 8 * p.group * sizeof(int), hipHostMallocDefault));
+      hforest_cap = 8 * p.group;
+    }
   }
   void reserve_samples(size_t N) {
     if (N <= sample_cap) return;
@@ -459,6 +479,271 @@ struct nnsdp_crown {
     if (kernel_ms) *kernel_ms = ms_all;
   }
 
+  // the group size of nnsdp_crown_search_many and its refusal (nnsdp_crown_forest_plan enumerates it without a handle)
+  static nnsdp::ForestPlan forest_group_plan(int n0, int ny, int nlit, int32_t max_boxes, int32_t corner_points, int32_t nroot, int32_t group) {
+    const size_t limit = std::max<size_t>(1, group > 0 ? std::min<size_t>((size_t)group, (size_t)nroot) : (size_t)nroot);
+    const size_t g = nnsdp::forest_group((size_t)n0, (size_t)ny, (size_t)nlit, (size_t)max_boxes, corner_points != 0, limit);
+    if (!g) {
+      const nnsdp::ForestPlan one = nnsdp::forest_plan((size_t)n0, (size_t)ny, (size_t)nlit, (size_t)max_boxes, corner_points != 0, 1);
+      const bool fr = one.frontier_bytes > nnsdp::kSearchFrontierCap, db = !fr && one.double_bytes > nnsdp::kSearchFrontierCap;
+      throw std::invalid_argument("max_boxes = " + std::to_string(max_boxes) + " needs " +
+                                  std::to_string(fr ? one.frontier_bytes : db ? one.double_bytes : one.int_bytes) + " bytes of " +
+                                  (fr ? "frontier" : db ? "point and leaf-log" : "record") + " buffers for one root, above the cap of 2^31 bytes");
+    }
+    return nnsdp::forest_plan((size_t)n0, (size_t)ny, (size_t)nlit, (size_t)max_boxes, corner_points != 0, g);
+  }
+
+  // nnsdp_crown_search_many: search() for nroot root boxes with thresholds of their own in one level loop (csrc/crown_forest.hpp); per
+  // root the result of search().  h may be null: the scalar options come first, as in search()
+  static void search_many(nnsdp_crown* h, int32_t nroot, const double* x1min, const double* x1max, int32_t nlit, const double* normals,
+                          const double* hs, int32_t literal_bounds, int32_t corner_points, int32_t max_boxes, int32_t max_depth, int32_t chunk,
+                          int32_t group, nnsdp_confirm_many_fn confirm, void* user, int32_t* verdict, int32_t* visited, int32_t* depth_reached,
+                          int32_t* nleaves, double* witness, double* kernel_ms) {
+    if (max_boxes < 1) throw std::invalid_argument("max_boxes must be >= 1, got " + std::to_string(max_boxes));
+    if (chunk < 1) throw std::invalid_argument("chunk must be >= 1, got " + std::to_string(chunk));
+    if (max_depth < 0) throw std::invalid_argument("max_depth must be >= 0, got " + std::to_string(max_depth));
+    if (group < 0) throw std::invalid_argument("group must be >= 0 (0: derived from the memory cap), got " + std::to_string(group));
+    if (nroot < 0) throw std::invalid_argument("nroot must be >= 0, got " + std::to_string(nroot));
+    if (kernel_ms) *kernel_ms = 0.0;
+    if (nroot == 0) {
+      if (h) h->fleaves.clear();
+      return;
+    }
+    if (!h) throw std::invalid_argument("null handle");
+    if (!x1min || !x1max || !hs || !verdict || !visited || !depth_reached || !nleaves || !witness) throw std::invalid_argument("null argument");
+    const int n0 = h->n0, ny = h->ny;
+    if (h->nlit > 0) {
+      if (normals) throw std::invalid_argument("the handle has literals of its own: normals must be NULL");
+      if (nlit != h->nlit) throw std::invalid_argument("nlit must be the handle's " + std::to_string(h->nlit) + ", got " + std::to_string(nlit));
+      normals = h->normals.data();
+    } else {
+      if (literal_bounds) throw std::invalid_argument("literal_bounds needs literals: the handle was created without normals");
+      if (corner_points) throw std::invalid_argument("corner_points needs literals: the handle was created without normals");
+      if (nlit < 1) throw std::invalid_argument("a clause needs at least one literal (nlit >= 1)");
+      check_literals(ny, nlit, normals);
+    }
+    std::vector<unsigned long long> masks((size_t)nroot, 0);
+    for (int r = 0; r < nroot; ++r) {
+      for (int i = 0; i < nlit; ++i)
+        if (!std::isfinite(hs[(size_t)r * nlit + i]))
+          throw std::invalid_argument("root " + std::to_string(r) + ", literal " + std::to_string(i) + ": the threshold hs is not finite (NaN or infinity)");
+      for (int t = 0; t < n0; ++t) {
+        const double l = x1min[(size_t)r * n0 + t], u = x1max[(size_t)r * n0 + t];
+        if (!std::isfinite(l) || !std::isfinite(u) || !(l <= u))
+          throw std::invalid_argument("root " + std::to_string(r) + ": x1min must be <= x1max and both finite (no NaN, no infinity)");
+        if (u > l) masks[(size_t)r] |= 1ull << t;
+      }
+    }
+    const nnsdp::ForestPlan P = forest_group_plan(n0, ny, nlit, max_boxes, corner_points, nroot, group);
+    const size_t G = P.group, cap = P.cap, logw = P.logw;
+    const size_t cb = std::min((size_t)chunk, cap);
+    h->fleaves.assign((size_t)nroot, SearchLeaves());
+    h->reserve_forest(P);
+    hipStream_t st = h->st;
+    double* D = h->fdb.p;
+    int* I = h->fib.p;
+    double *flo[2] = {h->ffr.p, h->ffr.p + 2 * cap * n0}, *fhi[2] = {flo[0] + cap * n0, flo[1] + cap * n0};
+    int *fcu[2] = {h->fcu.p, h->fcu.p + cap * n0}, *fro[2] = {h->fcu.p + 2 * cap * n0, h->fcu.p + 2 * cap * n0 + cap};
+    HIPCHK(hipMemcpyAsync(D + P.o_nrm, normals, (size_t)nlit * ny * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
+
+    nnsdp::ForestArgs s;
+    s.n0 = n0; s.ny = ny; s.nlit = nlit; s.literal_bounds = literal_bounds != 0; s.corner_points = corner_points != 0;
+    s.normals = D + P.o_nrm; s.hs = D + P.o_hs; s.mask = reinterpret_cast<const unsigned long long*>(D + P.o_mask);
+    s.seg = I + P.o_seg; s.len = I + P.o_len; s.nb = I + P.o_nb; s.flags = I + P.o_flags; s.act = I + P.o_act; s.tab = I + P.o_tab;
+    s.counts = I + P.o_cnt; s.open = I + P.o_open; s.best = I + P.o_best; s.coord = I + P.o_coord; s.pflag = I + P.o_pflag;
+    s.pre = I + P.o_pre; s.bt = I + P.o_bt; s.pre_stride = (long long)cap; s.bt_stride = (long long)(P.nblk + 1);
+    s.bound = D + P.o_bound; s.X = D + P.o_X; s.Y = D + P.o_Y; s.log = D + P.o_log; s.elog = D + P.o_elog;
+
+    struct Ent { int r, seg, len, nb, flags; };      // a root's segment of a level (flags as in ForestArgs)
+    struct Tail { std::vector<double> lo, hi, bound; std::vector<int> literal; };      // open boxes of a root read from the frontier
+    double ms_all = 0.0;
+    std::vector<int> iota(G);
+    for (size_t k = 0; k < G; ++k) iota[k] = (int)k;
+    for (size_t g0 = 0; g0 < (size_t)nroot; g0 += G) {
+      const size_t ng = std::min(G, (size_t)nroot - g0);
+      // level 0: the roots themselves, in order (the caller's columns g0 .. g0 + ng - 1 are contiguous)
+      HIPCHK(hipMemcpyAsync(flo[0], x1min + g0 * n0, ng * n0 * sizeof(double), hipMemcpyHostToDevice, st));
+      HIPCHK(hipMemcpyAsync(fhi[0], x1max + g0 * n0, ng * n0 * sizeof(double), hipMemcpyHostToDevice, st));
+      HIPCHK(hipMemsetAsync(fcu[0], 0, ng * n0 * sizeof(int), st));
+      HIPCHK(hipMemcpyAsync(fro[0], iota.data(), ng * sizeof(int), hipMemcpyHostToDevice, st));
+      HIPCHK(hipMemcpyAsync(D + P.o_hs, hs + g0 * nlit, ng * nlit * sizeof(double), hipMemcpyHostToDevice, st));
+      HIPCHK(hipMemcpyAsync(D + P.o_mask, masks.data() + g0, ng * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
+      HIPCHK(hipStreamSynchronize(st));      // (the sources are pageable arrays)
+
+      std::vector<int> vis(ng, 0), verd(ng, -1), dep(ng, 0);
+      std::vector<Tail> tails(ng);
+      std::vector<char> has_tail(ng, 0);
+      std::vector<Ent> lev(ng), nxt;
+      for (size_t r = 0; r < ng; ++r) lev[r] = Ent{(int)r, (int)r, 1, 0, 0};
+      int cur = 0, depth = 0;
+      long long log_n = 0, elog_n = 0;
+      for (;;) {
+        int nl = 0, nlive = 0;
+        for (Ent& e : lev) {
+          nl += e.len;
+          if (e.flags & 2) { e.nb = 0; continue; }
+          ++nlive;
+          const size_t r = (size_t)e.r;
+          e.nb = std::min(e.len, max_boxes - vis[r]);      // (>= 1: a level that uses the budget up is the root's last one)
+          vis[r] += e.nb;
+          const bool stop = vis[r] >= max_boxes || depth >= max_depth || masks[g0 + r] == 0;
+          e.flags = stop ? 0 : 1;
+        }
+        if (!nlive) break;
+        const int nent = (int)lev.size();
+        int* tab = h->hforest;
+        int* cnt = h->hforest + 5 * G;
+        for (int i = 0; i < nent; ++i) {
+          const Ent& e = lev[(size_t)i];
+          tab[5 * i] = e.r; tab[5 * i + 1] = e.seg; tab[5 * i + 2] = e.len; tab[5 * i + 3] = e.nb; tab[5 * i + 4] = e.flags;
+        }
+        h->reserve_boxes(std::min(cb, (size_t)nl), false, cb);      // (the stream is idle here: the bound kernel's buffers grow with the levels)
+        s.nl = nl; s.depth = depth; s.nblk = (int)cdiv(nl, nnsdp::kForestScanBlock);
+        s.lo = flo[cur]; s.hi = fhi[cur]; s.cuts = fcu[cur]; s.root = fro[cur];
+        s.nlo = flo[cur ^ 1]; s.nhi = fhi[cur ^ 1]; s.ncuts = fcu[cur ^ 1]; s.nroot = fro[cur ^ 1];
+        s.log_base = log_n; s.elog_base = elog_n;
+        HIPCHK(hipMemcpyAsync(I + P.o_tab, tab, (size_t)5 * nent * sizeof(int), hipMemcpyHostToDevice, st));
+        HIPCHK(hipEventRecord(h->e0, st));
+        hipLaunchKernelGGL(nnsdp::k_forest_roots, dim3((unsigned)cdiv(nent, 256)), dim3(256), 0, st, s, nent);
+        HIPCHK(hipGetLastError());
+        for (int off = 0; off < nl; off += (int)cb) {
+          const size_t nc = std::min(cb, (size_t)(nl - off));
+          // (per chunk: reserve_boxes may have moved the scratch and the outputs)
+          const nnsdp::CrownArgs a = h->bound_args(h->layout(nc), flo[cur] + (size_t)off * n0, fhi[cur] + (size_t)off * n0, h->dout.p);
+          h->launch_bound(a, nc);
+          hipLaunchKernelGGL(nnsdp::k_forest_classify, dim3((unsigned)cdiv((long long)nc, 256)), dim3(256), 0, st, s, off, (int)nc,
+                             (const double*)a.ymin, (const double*)a.ymax, (const double*)a.smax, (const double*)a.uA);
+          HIPCHK(hipGetLastError());
+          ++h->n_bound;
+        }
+        const long long npts = (long long)nl * (corner_points ? 2 : 1);
+        h->launch_forward(s.X, D + P.o_Y, npts);
+        hipLaunchKernelGGL(nnsdp::k_forest_refute, dim3((unsigned)cdiv(npts, 256)), dim3(256), 0, st, s, npts);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(nnsdp::k_forest_scan_block, dim3((unsigned)s.nblk), dim3(256), 0, st, s);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(nnsdp::k_forest_scan_totals, dim3(1), dim3(256), 0, st, s);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(nnsdp::k_forest_counts, dim3((unsigned)cdiv(nent, 256)), dim3(256), 0, st, s, nent);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(nnsdp::k_forest_scatter, dim3((unsigned)cdiv(nl, 256)), dim3(256), 0, st, s);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(h->e1, st));
+        HIPCHK(hipMemcpyAsync(cnt, s.counts, (size_t)3 * nent * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        ms_all += h->elapsed_ms();
+        bool any_cand = false;
+        for (int i = 0; i < nent; ++i) {
+          const Ent& e = lev[(size_t)i];
+          if (e.flags & 2) continue;
+          if (cnt[3 * i] < 0 || cnt[3 * i + 1] < 0 || cnt[3 * i] + cnt[3 * i + 1] != e.nb)
+            throw std::runtime_error("nnsdp_crown_search_many: inconsistent counts of root " + std::to_string(g0 + (size_t)e.r));
+          log_n += cnt[3 * i];
+          if (!(e.flags & 1)) elog_n += (e.len - e.nb) + cnt[3 * i + 1];
+          any_cand = any_cand || cnt[3 * i + 2] > 0;
+        }
+        std::vector<int> pf;
+        std::vector<double> X;
+        if (any_cand) {      // the level's flags and points; per root walked in the single search's order: the centres in box order, then the corners
+          pf.resize((size_t)npts); X.resize((size_t)npts * n0);
+          HIPCHK(hipMemcpy(pf.data(), s.pflag, pf.size() * sizeof(int), hipMemcpyDeviceToHost));
+          HIPCHK(hipMemcpy(X.data(), s.X, X.size() * sizeof(double), hipMemcpyDeviceToHost));
+        }
+        nxt.clear();
+        int acc = 0;
+        for (int i = 0; i < nent; ++i) {
+          const Ent& e = lev[(size_t)i];
+          if (e.flags & 2) continue;
+          const size_t r = (size_t)e.r;
+          const int nopen = cnt[3 * i + 1];
+          bool wit = false;
+          if (cnt[3 * i + 2] > 0)
+            for (int half = 0; half < (corner_points ? 2 : 1) && !wit; ++half)
+              for (int b = e.seg; b < e.seg + e.nb && !wit; ++b) {
+                const size_t p = (size_t)half * nl + b;
+                if (pf[p] && (!confirm || confirm(user, (int32_t)(g0 + r), X.data() + p * n0) != 0)) {
+                  std::copy(X.begin() + p * n0, X.begin() + (p + 1) * n0, witness + (g0 + r) * n0);
+                  wit = true;
+                }
+              }
+          const bool cont = (e.flags & 1) != 0;
+          if (wit) verd[r] = 1;
+          else if (nopen == 0) verd[r] = e.nb < e.len ? 2 : 0;
+          else if (!cont) verd[r] = 2;
+          if (verd[r] >= 0) dep[r] = depth;
+          if (wit && cont && nopen > 0) {      // its open boxes are leaves, and only the frontier has them: the end log holds roots that do not continue
+            const size_t nb = (size_t)e.nb;
+            std::vector<double> lo(nb * n0), hi(nb * n0), bnd(nb);
+            std::vector<int> open(nb), best(nb);
+            HIPCHK(hipMemcpy(lo.data(), flo[cur] + (size_t)e.seg * n0, lo.size() * sizeof(double), hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(hi.data(), fhi[cur] + (size_t)e.seg * n0, hi.size() * sizeof(double), hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(bnd.data(), s.bound + e.seg, nb * sizeof(double), hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(open.data(), s.open + e.seg, nb * sizeof(int), hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(best.data(), s.best + e.seg, nb * sizeof(int), hipMemcpyDeviceToHost));
+            Tail& T = tails[r];
+            has_tail[r] = 1;
+            for (size_t b = 0; b < nb; ++b)
+              if (open[b] == 1) {
+                T.lo.insert(T.lo.end(), lo.begin() + b * n0, lo.begin() + (b + 1) * n0);
+                T.hi.insert(T.hi.end(), hi.begin() + b * n0, hi.begin() + (b + 1) * n0);
+                T.bound.push_back(bnd[b]); T.literal.push_back(best[b]);
+              }
+          }
+          // the children were written before the host looked at the candidates: a violated root keeps its segment of the next level, dead
+          if (cont && nopen > 0) { nxt.push_back(Ent{e.r, acc, 2 * nopen, 0, wit ? 2 : 0}); acc += 2 * nopen; }
+        }
+        lev.swap(nxt);
+        if (lev.empty()) break;
+        cur ^= 1; ++depth;
+      }
+      // the leaves of every root in the single search's order: the proved log up to the root's last level, the boxes of the last level
+      // that the budget kept from being bounded, the last level's proved boxes, its open boxes
+      std::vector<double> log((size_t)log_n * logw), elog((size_t)elog_n * logw);
+      if (log_n) HIPCHK(hipMemcpy(log.data(), s.log, log.size() * sizeof(double), hipMemcpyDeviceToHost));
+      if (elog_n) HIPCHK(hipMemcpy(elog.data(), s.elog, elog.size() * sizeof(double), hipMemcpyDeviceToHost));
+      auto leaf = [&](SearchLeaves& L, const double* blo, const double* bhi, int d, int proved, int literal, double bound) {
+        L.lo.insert(L.lo.end(), blo, blo + n0); L.hi.insert(L.hi.end(), bhi, bhi + n0);
+        L.depth.push_back(d); L.proved.push_back(proved); L.literal.push_back(literal); L.bound.push_back(bound);
+      };
+      auto root_of = [&](const double* row) {
+        const long long r = (long long)row[2 * n0 + 3];
+        if (r < 0 || r >= (long long)ng) throw std::runtime_error("nnsdp_crown_search_many: a leaf-log row names no root of its group");
+        return (size_t)r;
+      };
+      auto from_row = [&](const double* row, int proved) {
+        leaf(h->fleaves[g0 + root_of(row)], row, row + n0, (int)row[2 * n0], proved, (int)row[2 * n0 + 1], row[2 * n0 + 2]);
+      };
+      for (long long k = 0; k < log_n; ++k) {
+        const double* row = log.data() + (size_t)k * logw;
+        if ((int)row[2 * n0] < dep[root_of(row)]) from_row(row, 1);
+      }
+      for (long long k = 0; k < elog_n; ++k) {
+        const double* row = elog.data() + (size_t)k * logw;
+        if ((int)row[2 * n0 + 1] < 0) from_row(row, 0);
+      }
+      for (long long k = 0; k < log_n; ++k) {
+        const double* row = log.data() + (size_t)k * logw;
+        if ((int)row[2 * n0] == dep[root_of(row)]) from_row(row, 1);
+      }
+      for (long long k = 0; k < elog_n; ++k) {
+        const double* row = elog.data() + (size_t)k * logw;
+        if ((int)row[2 * n0 + 1] >= 0) from_row(row, 0);
+      }
+      for (size_t r = 0; r < ng; ++r) {
+        if (has_tail[r]) {
+          const Tail& T = tails[r];
+          for (size_t k = 0; k < T.literal.size(); ++k)
+            leaf(h->fleaves[g0 + r], T.lo.data() + k * n0, T.hi.data() + k * n0, dep[r], 0, T.literal[k], T.bound[k]);
+        }
+        if (verd[r] < 0) throw std::runtime_error("nnsdp_crown_search_many: root " + std::to_string(g0 + r) + " was left undecided");
+        verdict[g0 + r] = verd[r]; visited[g0 + r] = vis[r]; depth_reached[g0 + r] = dep[r];
+        nleaves[g0 + r] = (int32_t)h->fleaves[g0 + r].depth.size();
+      }
+    }
+    if (kernel_ms) *kernel_ms = ms_all;
+  }
+
   // nnsdp_crown_reach.  h may be null: the scalar options come first so that their refusals can be tested on a machine without a GPU,
   // where no handle exists; every refusal comes before anything is allocated
   static void reach(nnsdp_crown* h, const double* x1min, const double* x1max, int32_t nlit, const double* tol, int32_t corner_points,
@@ -593,6 +878,7 @@ struct nnsdp_crown {
     if (st) (void)hipStreamSynchronize(st);
     for (double* h : {hin, hout, hX, hY, hain, haout}) if (h) (void)hipHostFree(h);
     if (hstatus) (void)hipHostFree(hstatus);
+    if (hforest) (void)hipHostFree(hforest);
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
     if (st) (void)hipStreamDestroy(st);

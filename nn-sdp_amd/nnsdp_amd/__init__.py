@@ -17,6 +17,6 @@ from .vnnlib import (  # noqa: F401
     read_vnnlib, hplaneS, loadVnnlibCnf, loadReluQueriesCnf, verifyAcasSpec, verifyPairs, isSolutionGood, shardPairs, reachForm, safetyFromReach,
 )
 from . import split  # noqa: F401
-from .split import SplitOptions, SplitResult, Leaf, verifySplit, reachSplit, ReachSplitResult, ReachLeaf, findReach2DpolySplit  # noqa: F401
+from .split import SplitOptions, SplitResult, Leaf, verifySplit, verifySplitMany, reachSplit, ReachSplitResult, ReachLeaf, findReach2DpolySplit  # noqa: F401
 
 __version__ = "0.2.0"

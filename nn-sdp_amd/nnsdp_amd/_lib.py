@@ -111,6 +111,10 @@ SYMBOLS = [
     ("nnsdp_crown_search", C.c_int, [C.c_void_p, c_double_p, c_double_p, C.c_int32, c_double_p, c_double_p] + [C.c_int32] * 5
      + [C.c_void_p, C.c_void_p] + [c_int32_p] * 4 + [c_double_p, c_double_p]),
     ("nnsdp_crown_search_leaves", C.c_int, [C.c_void_p, c_double_p, c_double_p, c_int32_p, c_int32_p, c_int32_p, c_double_p]),
+    ("nnsdp_crown_search_many", C.c_int, [C.c_void_p, C.c_int32, c_double_p, c_double_p, C.c_int32, c_double_p, c_double_p] + [C.c_int32] * 6
+     + [C.c_void_p, C.c_void_p] + [c_int32_p] * 4 + [c_double_p, c_double_p]),
+    ("nnsdp_crown_search_many_leaves", C.c_int, [C.c_void_p, C.c_int32, c_double_p, c_double_p, c_int32_p, c_int32_p, c_int32_p, c_double_p]),
+    ("nnsdp_crown_forest_plan", C.c_int, [C.c_int32] * 7 + [C.POINTER(C.c_int64)]),
     ("nnsdp_crown_reach", C.c_int, [C.c_void_p, c_double_p, c_double_p, C.c_int32, c_double_p] + [C.c_int32] * 4 + [c_int32_p] * 4
      + [c_double_p] * 3),
     ("nnsdp_crown_reach_leaves", C.c_int, [C.c_void_p, c_double_p, c_double_p, c_int32_p, c_int32_p, c_double_p]),

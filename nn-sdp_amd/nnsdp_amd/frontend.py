@@ -367,6 +367,16 @@ def evalFeedFwdNetBatch(net: M.FeedFwdNet, X, return_ms: bool = False):
 
 
 _CONFIRM = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.POINTER(C.c_double))      # nnsdp_confirm_fn
+_CONFIRM_MANY = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_double))      # nnsdp_confirm_many_fn
+
+
+def forestPlan(n0: int, ny: int, nlit: int, max_boxes: int, corner_points: bool = False, nroot: int = 1, group: int = 0) -> dict:
+    """nnsdp_crown_forest_plan: how CrownBounder.search_many groups nroot roots (no GPU needed): the roots per group, the boxes a level
+    of a group can hold and the bytes of its frontier, point / leaf-log and record buffers, each within the cap of 2^31 bytes; raises
+    ValueError with the byte count when one root alone does not fit."""
+    out = (C.c_int64 * 5)()
+    _lib.check(_lib.load().nnsdp_crown_forest_plan(int(n0), int(ny), int(nlit), int(max_boxes), int(bool(corner_points)), int(nroot), int(group), out))
+    return dict(group=int(out[0]), level_capacity=int(out[1]), frontier_bytes=int(out[2]), point_log_bytes=int(out[3]), record_bytes=int(out[4]))
 
 
 class CrownBounder:
@@ -376,8 +386,8 @@ class CrownBounder:
     makeIntervalsBatch(backend="gpu"); the Tanh kernel exists only here.
     max_width=128 (nnsdp_crown_create_wide) asks for the wide instance of the kernel (csrc/crown_wide.hpp): hidden layers up to 128
     wide, while xdims[0], xdims[K] and nlit stay at 64 or below.  It runs one workgroup per CU where the narrow one runs two, so it is
-    never chosen silently; on a network of widths <= 64 it returns the bits of the narrow instance.  bound, eval, search, reach and info
-    work on it; optimised slopes (alpha_steps, alpha0) do not - the alpha kernel keeps its 64-wide layout - and raise ValueError.
+    never chosen silently; on a network of widths <= 64 it returns the bits of the narrow instance.  bound, eval, search, search_many,
+    reach and info work on it; optimised slopes (alpha_steps, alpha0) do not - the alpha kernel keeps its 64-wide layout - and raise ValueError.
     A context manager; not thread-safe."""
 
     _INFO = ("device_allocations", "network_uploads", "box_capacity", "sample_capacity", "bound_calls", "device_bytes", "reach_calls")
@@ -516,6 +526,65 @@ class CrownBounder:
                                                        lproved.ctypes.data_as(ip), llit.ctypes.data_as(ip), lbound.ctypes.data_as(dp)))
         return dict(verdict=("holds", "violated", "unknown")[verdict], visited=visited, depth=depth, witness=wit if verdict == 1 else None,
                     kernel_ms=ms.value, lo=llo, hi=lhi, leaf_depth=ldepth, proved=lproved, literal=llit, bound=lbound)
+
+    def search_many(self, lo, hi, hs, *, normals=None, literal_bounds: bool = False, corner_points: bool = False, max_boxes: int = 512,
+                    max_depth: int = 24, chunk: int = 4096, group: int = 0, confirm=None) -> dict:
+        """nnsdp_crown_search_many: search() for the R root boxes lo / hi (xdims[0] x R) with the thresholds hs (nlit x R), one column per
+        root, in one level loop on the GPU (csrc/crown_forest.hpp); max_boxes and max_depth apply to every root alone.  Per root the
+        result is the one search() gives on that root, bit for bit.  group: roots that share the device buffers at a time (0: derived
+        from the memory cap, forestPlan); the result does not depend on it.  confirm(r, x) -> bool decides whether a point that the
+        device flagged for root r is its witness (None: the first flagged point is).  Returns per-root arrays verdict (R strings),
+        visited, depth (R), witness (R x xdims[0], NaN rows where the root is not violated), one kernel_ms, and the leaves of all roots,
+        one root after the other, as search() returns them: lo, hi, leaf_depth, proved, literal, bound, with leaf_start (R + 1): root
+        r owns the leaves leaf_start[r] .. leaf_start[r + 1] - 1."""
+        h, dp, ip = self._handle(), _lib.c_double_p, _lib.c_int32_p
+        lo = np.asarray(lo, dtype=np.float64)
+        hi = np.asarray(hi, dtype=np.float64)
+        if lo.ndim != 2 or lo.shape[0] != self._n0 or hi.shape != lo.shape:
+            raise ValueError("lo / hi must be xdims[0] x R")
+        R = lo.shape[1]
+        hs = np.asarray(hs, dtype=np.float64)
+        if hs.ndim != 2 or hs.shape[0] < 1 or hs.shape[1] != R:
+            raise ValueError("hs must be nlit x R: one threshold per literal and root")
+        nlit = hs.shape[0]
+        nrp = None
+        if normals is not None:
+            nrm = np.ascontiguousarray(normals, dtype=np.float64)               # nlit x ny row-major = ny x nlit column-major
+            if nrm.ndim != 2 or nrm.shape != (nlit, self._ny):
+                raise ValueError("normals must be len(hs) x xdims[K]")
+            nrp = nrm.ctypes.data_as(dp)
+        loc, hic, hsc = np.ascontiguousarray(lo.T), np.ascontiguousarray(hi.T), np.ascontiguousarray(hs.T)      # column-major
+        failed = []
+
+        def call(_user, r, x):
+            try:
+                return 1 if confirm(int(r), np.ctypeslib.as_array(x, shape=(self._n0,)).copy()) else 0
+            except BaseException as e:       # an exception cannot cross the C frames: the root ends at this level, it is raised again below
+                failed.append(e)
+                return 1
+
+        keep = _CONFIRM_MANY(call) if confirm is not None else None
+        cb = C.cast(keep, C.c_void_p) if keep is not None else None
+        verdict, visited, depth, nleaves = (np.zeros(R, dtype=np.int32) for _ in range(4))
+        wit, ms = np.full((R, self._n0), np.nan), C.c_double(0.0)
+        _lib.check(self._lib.nnsdp_crown_search_many(h, R, loc.ctypes.data_as(dp), hic.ctypes.data_as(dp), nlit, nrp, hsc.ctypes.data_as(dp),
+                                                     int(bool(literal_bounds)), int(bool(corner_points)), int(max_boxes), int(max_depth),
+                                                     int(chunk), int(group), cb, None, verdict.ctypes.data_as(ip), visited.ctypes.data_as(ip),
+                                                     depth.ctypes.data_as(ip), nleaves.ctypes.data_as(ip), wit.ctypes.data_as(dp), C.byref(ms)))
+        if failed:
+            raise failed[0]
+        start = np.zeros(R + 1, dtype=np.int64)
+        np.cumsum(nleaves, out=start[1:])
+        n = int(start[-1])
+        llo, lhi = np.zeros((n, self._n0)), np.zeros((n, self._n0))
+        ldepth, lproved, llit = (np.zeros(n, dtype=np.int32) for _ in range(3))
+        lbound = np.zeros(n)
+        if R:
+            _lib.check(self._lib.nnsdp_crown_search_many_leaves(h, -1, llo.ctypes.data_as(dp), lhi.ctypes.data_as(dp), ldepth.ctypes.data_as(ip),
+                                                                lproved.ctypes.data_as(ip), llit.ctypes.data_as(ip), lbound.ctypes.data_as(dp)))
+        names = np.array(["holds", "violated", "unknown"], dtype=object)
+        return dict(verdict=names[verdict], visited=visited, depth=depth, witness=wit, kernel_ms=ms.value, lo=llo, hi=lhi, leaf_depth=ldepth,
+                    proved=lproved, literal=llit, bound=lbound, leaf_start=start)
 
     def reach(self, lo, hi, tol, *, corner_points: bool = False, max_boxes: int = 512, max_depth: int = 24, chunk: int = 4096) -> dict:
         """nnsdp_crown_reach: the bounds-only level loop of split.reachSplit on the root box lo / hi (xdims[0] each) for the bounder's

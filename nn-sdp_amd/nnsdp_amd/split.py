@@ -71,6 +71,7 @@ class SplitOptions:
     # alpha_steps = 0.  With sdp_per_level > 0 the SDPs run once, on the open leaves of a search that ended "unknown".
     # SplitResult.seconds then has one more key, "kernel": the HIP-event time of the search's launches (tools/split_timing.py reads it).
     # reachSplit takes the same option (CrownBounder.reach, csrc/crown_reach.hpp) and then also needs sdp_per_level = 0.
+    # verifySplitMany takes it too (CrownBounder.search_many, csrc/crown_forest.hpp: many root boxes in one level loop); it is bounds-only.
     # chunk: boxes per launch of the bound kernel, which bounds the device memory of a level's interval arrays
     frontier: str = "host"
     chunk: int = 4096
@@ -191,12 +192,8 @@ def _crown_bounder(net, normals, split: SplitOptions):
     return F.CrownBounder(net, normals, max_width=split.crown_max_width)
 
 
-def verifySplit(net: M.FeedFwdNet, x1min, x1max, literals: Sequence[Tuple[Any, float]], beta: int, opts: M.AdmmSdpOptions,
-                split: SplitOptions = None) -> SplitResult:
-    """Decide the clause  OR_i normal_i' f(x) <= h_i  on the box [x1min, x1max]: "holds" when every leaf of the bisection tree has
-    one literal proved on all of it, "violated" with a witness x at which every literal is false, "unknown" when max_boxes or
-    max_depth ends the search (the open leaves are returned as they are)."""
-    split = split or SplitOptions()
+def _check_split_options(net, split: SplitOptions) -> None:
+    """the option refusals of verifySplit"""
     if split.crown_backend not in ("gpu", "host", "resident"):
         raise ValueError("crown_backend must be 'gpu', 'host' or 'resident'")
     if split.alpha_steps < 0:
@@ -218,28 +215,107 @@ def verifySplit(net: M.FeedFwdNet, x1min, x1max, literals: Sequence[Tuple[Any, f
         if split.alpha_steps != 0:
             raise ValueError("frontier 'device' needs alpha_steps == 0")
     _check_crown_max_width(split)
-    t_start = time.perf_counter()
-    root_lo, root_hi = np.array(x1min, dtype=np.float64), np.array(x1max, dtype=np.float64)
-    n0, ny = net.xdims[0], net.xdims[-1]
-    if root_lo.shape != (n0,) or root_hi.shape != (n0,) or not np.all(root_lo <= root_hi):
-        raise ValueError("x1min / x1max must have xdims[0] entries with x1min <= x1max")
+
+
+def _clause(net, literals):
+    """(normals nlit x xdims[K], hs nlit) of a clause"""
     if not literals:
         raise ValueError("a clause needs at least one literal")
     normals = np.array([np.asarray(nrm, dtype=np.float64) for nrm, _ in literals])
     hs = np.array([float(h) for _, h in literals])
-    if normals.shape != (len(literals), ny):
+    if normals.shape != (len(literals), net.xdims[-1]):
         raise ValueError("every normal must have xdims[K] entries")
+    return normals, hs
+
+
+def verifySplit(net: M.FeedFwdNet, x1min, x1max, literals: Sequence[Tuple[Any, float]], beta: int, opts: M.AdmmSdpOptions,
+                split: SplitOptions = None) -> SplitResult:
+    """Decide the clause  OR_i normal_i' f(x) <= h_i  on the box [x1min, x1max]: "holds" when every leaf of the bisection tree has
+    one literal proved on all of it, "violated" with a witness x at which every literal is false, "unknown" when max_boxes or
+    max_depth ends the search (the open leaves are returned as they are)."""
+    split = split or SplitOptions()
+    _check_split_options(net, split)
+    return _verify_split(net, x1min, x1max, literals, beta, opts, split, None)
+
+
+def _verify_split(net, x1min, x1max, literals, beta, opts, split, shared) -> SplitResult:
+    """verifySplit behind its option checks; shared: a CrownBounder of crown_backend "resident" that the caller owns (verifySplitMany),
+    or None: the call makes and closes its own"""
+    t_start = time.perf_counter()
+    root_lo, root_hi = np.array(x1min, dtype=np.float64), np.array(x1max, dtype=np.float64)
+    n0 = net.xdims[0]
+    if root_lo.shape != (n0,) or root_hi.shape != (n0,) or not np.all(root_lo <= root_hi):
+        raise ValueError("x1min / x1max must have xdims[0] entries with x1min <= x1max")
+    normals, hs = _clause(net, literals)
     seconds = {"crown": 0.0, "setup": 0.0, "solve": 0.0, "finish": 0.0, "total": 0.0}
     frontier = [_Box(root_lo, root_hi, np.zeros(n0, dtype=np.int64))]
     want_lits = split.literal_bounds or split.corner_points
-    bounder = _crown_bounder(net, normals if want_lits else None, split) if split.crown_backend == "resident" else None
+    bounder = shared
+    if shared is None and split.crown_backend == "resident":
+        bounder = _crown_bounder(net, normals if want_lits else None, split)
     try:
         if split.frontier == "device":
             return _split_device(net, root_lo, root_hi, normals, hs, beta, opts, split, bounder, want_lits, seconds, t_start)
         return _split_levels(net, frontier, root_lo, root_hi, normals, hs, beta, opts, split, bounder, seconds, t_start)
     finally:
+        if bounder is not None and shared is None:
+            bounder.close()
+
+
+def verifySplitMany(net: M.FeedFwdNet, x1min, x1max, literals: Sequence[Tuple[Any, float]], beta: int, opts: M.AdmmSdpOptions,
+                    split: SplitOptions = None, hs=None) -> List[SplitResult]:
+    """verifySplit for the R root boxes x1min / x1max (xdims[0] x R), bounds only: the clause of `literals` on every root, with the
+    thresholds of root r replaced by hs[:, r] when hs (nlit x R) is given.  max_boxes and max_depth apply to every root alone, and
+    result r is what verifySplit returns for root r with its thresholds (the timings apart).  sdp_per_level must be 0.
+    frontier = "host": the loop over verifySplit, on one CrownBounder when crown_backend is "resident".  frontier = "device" (needs what
+    it needs in verifySplit): one CrownBounder.search_many (csrc/crown_forest.hpp), which runs level d of every undecided root as one
+    frontier on the GPU, so a level's launches and its synchronisation are paid once for all roots; seconds["crown"], ["kernel"] and
+    ["total"] of every result are then the whole call's."""
+    split = split or SplitOptions()
+    _check_split_options(net, split)
+    if split.sdp_per_level != 0:
+        raise ValueError("verifySplitMany is bounds-only: it needs sdp_per_level == 0")
+    t_start = time.perf_counter()
+    lo, hi = np.array(x1min, dtype=np.float64), np.array(x1max, dtype=np.float64)
+    n0 = net.xdims[0]
+    if lo.ndim != 2 or lo.shape[0] != n0 or hi.shape != lo.shape or not np.all(lo <= hi):
+        raise ValueError("x1min / x1max must be xdims[0] x R with x1min <= x1max")
+    R = lo.shape[1]
+    normals, h0 = _clause(net, literals)
+    H = np.repeat(h0[:, None], R, axis=1) if hs is None else np.array(hs, dtype=np.float64)
+    if H.shape != (len(h0), R):
+        raise ValueError("hs must be nlit x R: one threshold per literal and root")
+    if R == 0:
+        return []
+    want_lits = split.literal_bounds or split.corner_points
+    bounder = _crown_bounder(net, normals if want_lits else None, split) if split.crown_backend == "resident" else None
+    try:
+        if split.frontier == "host":
+            return [_verify_split(net, lo[:, r], hi[:, r], [(normals[i], H[i, r]) for i in range(len(h0))], beta, opts, split, bounder)
+                    for r in range(R)]
+        t0 = time.perf_counter()
+        res = bounder.search_many(lo, hi, H, normals=None if want_lits else normals, literal_bounds=split.literal_bounds,
+                                  corner_points=split.corner_points, max_boxes=int(split.max_boxes), max_depth=int(split.max_depth),
+                                  chunk=int(split.chunk),
+                                  confirm=lambda r, x: bool(_violates_all(F.evalFeedFwdNet(net, x)[:, None], normals, H[:, r])[0]))
+        t_crown = time.perf_counter() - t0
+    finally:
         if bounder is not None:
             bounder.close()
+    out = []
+    for r in range(R):
+        leaves = []
+        for k in range(int(res["leaf_start"][r]), int(res["leaf_start"][r + 1])):
+            lit = int(res["literal"][k])
+            leaves.append(Leaf(res["lo"][k].copy(), res["hi"][k].copy(), int(res["leaf_depth"][k]), "crown" if res["proved"][k] else None,
+                               lit if lit >= 0 else None, float(res["bound"][k]) if lit >= 0 else None))
+        verdict = str(res["verdict"][r])
+        seconds = {"crown": t_crown, "setup": 0.0, "solve": 0.0, "finish": 0.0, "total": 0.0, "kernel": 1e-3 * res["kernel_ms"]}
+        out.append(SplitResult(verdict, leaves, res["witness"][r].copy() if verdict == "violated" else None, int(res["visited"][r]), 0, seconds))
+    total = time.perf_counter() - t_start
+    for sr in out:
+        sr.seconds["total"] = total
+    return out
 
 
 def _split_device(net, root_lo, root_hi, normals, hs, beta, opts, split, bounder, want_lits, seconds, t_start) -> SplitResult:

@@ -1,6 +1,12 @@
 #!/usr/bin/env python3
 """Batched CROWN bounds: the GPU kernel against the host routine, and where one verifySplit spends its time.
-usage: python tools/split_timing.py [--nlit | --resident | --alpha | --frontier | --reach | --wide] [case ...]   cases: W10-D5 W40-D20 acas-shape   (default: all)
+usage: python tools/split_timing.py [--nlit | --resident | --alpha | --frontier | --reach | --wide | --forest] [case ...]   cases: W10-D5 W40-D20 acas-shape   (default: all)
+With --forest only the forest leg runs (cases W10-D5 and acas-shape by default) and profiles/split_timing_forest_<case>.json is written:
+  forest   R = 1, 16, 256, 4096 roots: a regular grid of the case's root box (2^k cells, the halvings dealt to the coordinates in turn);
+           per root the literal y_0 - y_last <= s_r + 0.1 (c0_r - s_r), s_r the largest of 256 sampled values in the root, c0_r its
+           per-output bound; literal_bounds, max_boxes 512 per root.  On ONE CrownBounder: R sequential search calls against one
+           search_many: wall-clock of the whole (median of 3 after 1 warm run; one run at R = 4096), the HIP-event time of the launches,
+           levels (sequential: the sum over the roots), bound launches and bounded boxes per launch
 With --wide only the wide leg runs (cases W40-D20, acas-shape - the 5-50x6-5 net - and 5-100x4-5 by default) and
 profiles/split_timing_wide_<case>.json is written:
   bound    CrownBounder(max_width=128).bound at nbox = 1, 256, 4096: HIP-event time of the launch and wall-clock of the call, median of 7
@@ -270,6 +276,58 @@ def reach_rows(net, lo, hi, max_boxes=16384):
     return out
 
 
+def grid_roots(lo, hi, R):
+    """R = 2^k cells of a regular grid of the box: the k halvings go to the coordinates in turn -> lo, hi (n0 x R)"""
+    n0, k = len(lo), int(round(np.log2(R)))
+    assert 2 ** k == R
+    parts = [2 ** ((k + n0 - 1 - t) // n0) for t in range(n0)]
+    idx = np.stack(np.meshgrid(*[np.arange(p) for p in parts], indexing="ij"), axis=0).reshape(n0, -1)
+    w = (hi - lo) / np.array(parts)
+    return lo[:, None] + idx * w[:, None], lo[:, None] + (idx + 1) * w[:, None]
+
+
+def forest_rows(net, lo, hi, max_boxes=512, f=0.1, nsample=256):
+    nrm = np.zeros(net.xdims[-1]); nrm[0] = 1.0; nrm[-1] -= 1.0
+    kw = dict(literal_bounds=True, max_boxes=max_boxes, max_depth=24)
+    rows = []
+    with na.CrownBounder(net, nrm[None]) as cb:
+        for R in (1, 16, 256, 4096):
+            rlo, rhi = grid_roots(lo, hi, R)
+            X = np.repeat(rlo, nsample, axis=1) + np.random.default_rng(0).random((len(lo), R * nsample)) * np.repeat(rhi - rlo, nsample, axis=1)
+            s = (nrm @ cb.eval(X)).reshape(R, nsample).max(axis=1)
+            iv = cb.bound(rlo, rhi)
+            c0 = np.maximum(nrm[:, None] * iv[4], nrm[:, None] * iv[5]).sum(axis=0)
+            hs = (s + f * (c0 - s))[None]
+
+            def sequential():
+                b0, t = cb.info()["bound_calls"], time.perf_counter()
+                res = [cb.search(rlo[:, r], rhi[:, r], hs[:, r], **kw) for r in range(R)]
+                wall = time.perf_counter() - t
+                return dict(wall_ms=1e3 * wall, kernel_ms=sum(q["kernel_ms"] for q in res), levels=sum(q["depth"] + 1 for q in res),
+                            bound_launches=cb.info()["bound_calls"] - b0, visited=sum(q["visited"] for q in res),
+                            verdicts=[sum(q["verdict"] == v for q in res) for v in ("holds", "violated", "unknown")])
+
+            def forest():
+                b0, t = cb.info()["bound_calls"], time.perf_counter()
+                q = cb.search_many(rlo, rhi, hs, **kw)
+                wall = time.perf_counter() - t
+                return dict(wall_ms=1e3 * wall, kernel_ms=q["kernel_ms"], levels=int(q["depth"].max()) + 1, bound_launches=cb.info()["bound_calls"] - b0,
+                            visited=int(q["visited"].sum()), verdicts=[int(np.sum(q["verdict"] == v)) for v in ("holds", "violated", "unknown")])
+
+            row = dict(R=R, max_boxes=max_boxes, f=f)
+            for key, call in (("sequential", sequential), ("forest", forest)):
+                runs = [call() for _ in range(2 if R == 4096 else 4)][1:]
+                r = dict(runs[0], wall_ms=statistics.median(q["wall_ms"] for q in runs), kernel_ms=statistics.median(q["kernel_ms"] for q in runs))
+                r["boxes_per_launch"] = r["visited"] / r["bound_launches"]
+                row[key] = r
+            assert row["sequential"]["visited"] == row["forest"]["visited"] and row["sequential"]["verdicts"] == row["forest"]["verdicts"]
+            row["sequential_over_forest_wall"] = row["sequential"]["wall_ms"] / row["forest"]["wall_ms"]
+            rows.append(row)
+            print(row, flush=True)
+        info = cb.info()
+    return dict(forest=rows, handle=info)
+
+
 def split_row(net, lo, hi):
     nrm = np.zeros(net.xdims[-1]); nrm[0] = 1.0
     X = lo[:, None] + np.random.default_rng(0).random((len(lo), 20000)) * (hi - lo)[:, None]
@@ -292,12 +350,17 @@ if __name__ == "__main__":
     args = sys.argv[1:]
     lit_leg, res_leg, alpha_leg, frontier_leg, reach_leg, wide_leg = ("--nlit" in args, "--resident" in args, "--alpha" in args, "--frontier" in args,
                                                                       "--reach" in args, "--wide" in args)
-    names = [a for a in args if a not in ("--nlit", "--resident", "--alpha", "--frontier", "--reach", "--wide")] or \
-        (["W40-D20", "acas-shape", "5-100x4-5"] if wide_leg else ["W10-D5", "W40-D20", "acas-shape"])
+    forest_leg = "--forest" in args
+    names = [a for a in args if a not in ("--nlit", "--resident", "--alpha", "--frontier", "--reach", "--wide", "--forest")] or \
+        (["W40-D20", "acas-shape", "5-100x4-5"] if wide_leg else ["W10-D5", "acas-shape"] if forest_leg else ["W10-D5", "W40-D20", "acas-shape"])
     out_dir = os.environ.get("SPLIT_TIMING_OUT", os.path.join(ROOT, "profiles"))
     os.makedirs(out_dir, exist_ok=True)
     for name in names:
         net, lo, hi = case(name)
+        if forest_leg:
+            with open(os.path.join(out_dir, f"split_timing_forest_{name}.json"), "w") as fh:
+                json.dump(dict(case=name, xdims=net.xdims, **forest_rows(net, lo, hi)), fh, indent=1)
+            continue
         if wide_leg:
             with open(os.path.join(out_dir, f"split_timing_wide_{name}.json"), "w") as fh:
                 json.dump(dict(case=name, xdims=net.xdims, bound=wide_rows(net, lo, hi)), fh, indent=1)
