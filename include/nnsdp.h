@@ -459,7 +459,7 @@ int nnsdp_crown_eval(nnsdp_crown* h, int64_t N, const double* X, double* Y, doub
  * bisection of the open boxes into the second frontier and the proved boxes' rows of a leaf log, all in device memory; the host reads
  * back four integers per level (boxes bounded, proved, open, candidate points).  The tree, the order of the leaves and every number
  * are those of the Python loop, bit for bit: the sum of the proof test has the order of numpy's pairwise reduction as split.py reaches
- * it (plain ascending below 8 outputs, eight interleaved partial sums from 8 on; csrc/crown_search.hpp, search_cheap).
+ * it (plain ascending below 8 outputs, eight interleaved partial sums from 8 on; csrc/crown_frontier.hpp, search_cheap).
  * The clause: a handle created with literals uses them (normals NULL, nlit the handle's); a handle without takes normals (ny x nlit
  * column-major, nlit in 1..64) and can neither use literal_bounds nor corner_points.
  * confirm: called on the host, only on a level that has candidate points, for each candidate in the order centres then corners, each

@@ -18,6 +18,7 @@
 #include "solver.hpp"
 #include "batch.hpp"
 #include "crown_handle.hpp"
+#include "crown_frontier_host.hpp"
 
 #define API_BEGIN try {
 #define API_END                                                                    \
@@ -672,14 +673,7 @@ int nnsdp_crown_search(nnsdp_crown* h, const double* x1min, const double* x1max,
 int nnsdp_crown_search_leaves(nnsdp_crown* h, double* lo, double* hi, int32_t* depth, int32_t* proved, int32_t* literal, double* bound) {
   API_BEGIN
   if (!h) throw std::invalid_argument("null handle");
-  const nnsdp_crown::SearchLeaves& L = h->leaves;
-  if (!L.depth.empty() && (!lo || !hi || !depth || !proved || !literal || !bound)) throw std::invalid_argument("null argument");
-  std::copy(L.lo.begin(), L.lo.end(), lo);
-  std::copy(L.hi.begin(), L.hi.end(), hi);
-  std::copy(L.depth.begin(), L.depth.end(), depth);
-  std::copy(L.proved.begin(), L.proved.end(), proved);
-  std::copy(L.literal.begin(), L.literal.end(), literal);
-  std::copy(L.bound.begin(), L.bound.end(), bound);
+  h->leaves.copy_out(lo, hi, depth, proved, literal, bound);
   API_END
 }
 
@@ -700,17 +694,7 @@ int nnsdp_crown_search_many_leaves(nnsdp_crown* h, int32_t root, double* lo, dou
   const int32_t nroot = (int32_t)h->fleaves.size();
   if (root < -1 || root >= nroot)
     throw std::invalid_argument("root must be -1 or in 0.." + std::to_string(nroot - 1) + " (the roots of the last search_many), got " + std::to_string(root));
-  for (int32_t r = root < 0 ? 0 : root; r < (root < 0 ? nroot : root + 1); ++r) {
-    const nnsdp_crown::SearchLeaves& L = h->fleaves[(size_t)r];
-    if (L.depth.empty()) continue;
-    if (!lo || !hi || !depth || !proved || !literal || !bound) throw std::invalid_argument("null argument");
-    lo = std::copy(L.lo.begin(), L.lo.end(), lo);
-    hi = std::copy(L.hi.begin(), L.hi.end(), hi);
-    depth = std::copy(L.depth.begin(), L.depth.end(), depth);
-    proved = std::copy(L.proved.begin(), L.proved.end(), proved);
-    literal = std::copy(L.literal.begin(), L.literal.end(), literal);
-    bound = std::copy(L.bound.begin(), L.bound.end(), bound);
-  }
+  for (int32_t r = root < 0 ? 0 : root; r < (root < 0 ? nroot : root + 1); ++r) h->fleaves[(size_t)r].copy_out(lo, hi, depth, proved, literal, bound);
   API_END
 }
 

@@ -1,9 +1,9 @@
-// Device-resident frontier of the reach search (nnsdp_crown::reach of crown_handle.hpp; nnsdp_amd/split.py, reachSplit with frontier =
+// Device-resident frontier of the reach search (nnsdp_crown::reach of crown_frontier_host.hpp; nnsdp_amd/split.py, reachSplit with frontier =
 // "device"): branch and bound with an incumbent that encloses the support values  max_x c_i' f(x)  of every direction c_i of the handle
 // on ONE bisection tree.  The level loop of split.py (_reach_levels) with the boxes, the incumbents and the leaf log in device memory:
 // per level the host launches, per chunk of the level, the handle's bound kernel (k_crown_resident, csrc/crown_batch.hpp) and
 // k_reach_points on the chunk's outputs; then k_forward_mfma on the level's points, k_reach_incumbent, k_reach_classify, k_search_scan
-// (csrc/crown_search.hpp, as it is) and k_reach_scatter, and reads back the four integers of the status record.
+// (csrc/crown_search.hpp, with no points to count) and k_reach_scatter, and reads back the four integers of the status record.
 //
 // Frontier: lo, hi (doubles) and cuts (ints), each n0 x nbox column-major, two of them (the level and its children), as in the search.
 // Per-level records, by the box's position in the level: ub (nlit x nb column-major: the bounds of every direction), the open flag, the
@@ -12,10 +12,11 @@
 // Incumbent state, nlit each: L (the largest c_i' f(point) so far), thr = L + tol, and the point xw (n0 x nlit column-major).
 // Leaf log: one row of 2 n0 + 1 + nlit doubles per closed box, in the order split.py appends them: lo, hi, depth, ub[:, b].
 //
-// As in the search, whatever decides anything restates numpy operation for operation (products and sums rounded separately: contraction is
-// off inside these kernels), so the tree is the Python loop's bit for bit.  The maximum of a direction over the level's points is numpy's
-// argmax, the FIRST of equal values: (value, index) pairs are combined by "greater value, or equal value and smaller index", which is
-// associative and commutative, so the order of the per-thread walk, the cross-lane steps and the LDS tree does not matter.  No atomics.
+// As in the search, whatever decides anything restates numpy operation for operation, so the tree is the Python loop's bit for bit; the
+// arithmetic is the search's, stated once in csrc/crown_frontier.hpp (products and sums rounded separately: its helpers switch
+// contraction off for themselves).  The maximum of a direction over the level's points is numpy's argmax, the FIRST of equal values:
+// (value, index) pairs are combined by "greater value, or equal value and smaller index", which is associative and commutative, so the
+// order of the per-thread walk, the cross-lane steps and the LDS tree does not matter.  No atomics.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -24,26 +25,15 @@
 namespace nnsdp {
 
 struct ReachArgs {
-  int n0, ny, nlit;               // input width, output width, directions
+  FrontierArgs f;                 // nlit: directions; X: n0 x npts
   int nb;                         // boxes of the level
-  int depth;                      // the level
-  int corner_points;
   int children;                   // 0: depth >= max_depth or nothing splittable; the scatter kernel never writes children then
   int visited, max_boxes;         // boxes bounded up to and including this level; children only if visited + 2 open <= max_boxes
   unsigned long long splitmask;   // bit t: root_hi[t] > root_lo[t]
-  const double* normals;          // ny x nlit column-major
   const double* tol;              // nlit
-  const double *lo, *hi;          // the level's frontier
-  const int* cuts;
-  double *nlo, *nhi;              // the next frontier
-  int* ncuts;
   int *open, *coord, *slot;       // records, nb each
   double* ub;                     // nlit x nb
-  double* X;                      // n0 x npts
-  const double* Y;                // ny x npts
   double *L, *thr, *xw;           // incumbents
-  double* log;                    // leaf log; this level's rows start at log_base
-  long long log_base;
   const int* status;              // k_search_scan's record: bounded, closed, open, 0
 };
 
@@ -51,24 +41,17 @@ struct ReachArgs {
 // kernel (indexed by the box's position in the chunk).  ub[i, b] = min(cheap_i, smax_i), the centre and the corners of the box
 __global__ __launch_bounds__(256) void k_reach_points(ReachArgs a, int off, int nc, const double* ymin, const double* ymax,
                                                       const double* smax, const double* uA) {
-#pragma clang fp contract(off)      // numpy rounds every product and every sum
   const int c = blockIdx.x * 256 + threadIdx.x;
   if (c >= nc) return;
-  const int b = off + c, n0 = a.n0, ny = a.ny, nlit = a.nlit;
-  for (int i = 0; i < nlit; ++i) {
-    const double cheap = search_cheap(a.normals + (size_t)i * ny, ymin + (size_t)c * ny, ymax + (size_t)c * ny, ny);
-    const double s = smax[(size_t)c * nlit + i];
-    a.ub[(size_t)b * nlit + i] = cheap <= s ? cheap : s;
-  }
-  const double* lo = a.lo + (size_t)b * n0;
-  const double* hi = a.hi + (size_t)b * n0;
-  for (int t = 0; t < n0; ++t) a.X[(size_t)b * n0 + t] = 0.5 * (lo[t] + hi[t]);
-  if (a.corner_points)
-    for (int i = 0; i < nlit; ++i) {
-      const double* A = uA + ((size_t)c * nlit + i) * n0;
-      double* x = a.X + ((size_t)(1 + i) * a.nb + b) * n0;
-      for (int t = 0; t < n0; ++t) x[t] = A[t] >= 0.0 ? hi[t] : lo[t];
-    }
+  const FrontierArgs& f = a.f;
+  const int b = off + c, n0 = f.n0, ny = f.ny, nlit = f.nlit;
+  for (int i = 0; i < nlit; ++i)
+    a.ub[(size_t)b * nlit + i] = search_literal(f.normals + (size_t)i * ny, ymin + (size_t)c * ny, ymax + (size_t)c * ny, ny, smax + (size_t)c * nlit + i);
+  const double* lo = f.lo + (size_t)b * n0;
+  const double* hi = f.hi + (size_t)b * n0;
+  frontier_centre(f.X + (size_t)b * n0, lo, hi, n0);
+  if (f.corner_points)
+    for (int i = 0; i < nlit; ++i) frontier_corner(f.X + ((size_t)(1 + i) * a.nb + b) * n0, uA + ((size_t)c * nlit + i) * n0, lo, hi, n0);
 }
 
 // (v, p) <- the better of (v, p) and (w, q): greater value, or equal value and smaller index
@@ -76,25 +59,18 @@ __device__ __forceinline__ void reach_take(double& v, long long& p, double w, lo
   if (w > v || (w == v && q < p)) { v = w; p = q; }
 }
 
-// ONE workgroup per direction: s[i, p] = c_i[0] Y[0, p], then + c_i[j] Y[j, p] for j ascending; the first maximum over the level's
-// points; L_i, x_i are replaced when it is greater than L_i; thr_i = L_i + tol_i.  A thread that saw no point carries (-inf, LLONG_MAX)
+// ONE workgroup per direction: s[i, p] = c_i' Y[:, p] (frontier_dot); the first maximum over the level's points; L_i, x_i are replaced
+// when it is greater than L_i; thr_i = L_i + tol_i.  A thread that saw no point carries (-inf, LLONG_MAX)
 __global__ __launch_bounds__(256) void k_reach_incumbent(ReachArgs a, long long npts) {
-#pragma clang fp contract(off)      // numpy rounds every product and every sum
+#pragma clang fp contract(off)      // numpy rounds every sum (L + tol below)
   __shared__ double sv[4];
   __shared__ long long sp[4];
-  const int i = blockIdx.x, tid = threadIdx.x, ny = a.ny;
-  const double* nrm = a.normals + (size_t)i * ny;
+  const FrontierArgs& f = a.f;
+  const int i = blockIdx.x, tid = threadIdx.x, ny = f.ny;
+  const double* nrm = f.normals + (size_t)i * ny;
   double v = -__builtin_inf();
   long long p = 0x7fffffffffffffffLL;
-  for (long long q = tid; q < npts; q += 256) {
-    const double* y = a.Y + (size_t)q * ny;
-    double s = nrm[0] * y[0];
-    for (int j = 1; j < ny; ++j) {
-      const double m = nrm[j] * y[j];
-      s = s + m;
-    }
-    reach_take(v, p, s, q);
-  }
+  for (long long q = tid; q < npts; q += 256) reach_take(v, p, frontier_dot(nrm, f.Y + (size_t)q * ny, ny), q);
   // wave64: six cross-lane steps; every lane takes part in every step (no divergence around __shfl_down)
   for (int d = 32; d > 0; d >>= 1) {
     const double w = __shfl_down(v, d, 64);
@@ -109,60 +85,40 @@ __global__ __launch_bounds__(256) void k_reach_incumbent(ReachArgs a, long long 
     if (npts > 0 && v > L) {
       L = v;
       a.L[i] = v;
-      for (int t = 0; t < a.n0; ++t) a.xw[(size_t)i * a.n0 + t] = a.X[(size_t)p * a.n0 + t];
+      for (int t = 0; t < f.n0; ++t) a.xw[(size_t)i * f.n0 + t] = f.X[(size_t)p * f.n0 + t];
     }
     a.thr[i] = L + a.tol[i];
   }
 }
 
-// one thread per box: open when some direction's bound is above its threshold; the split coordinate as in k_search_classify
+// one thread per box: open when some direction's bound is above its threshold; the split coordinate
 __global__ __launch_bounds__(256) void k_reach_classify(ReachArgs a) {
   const int b = blockIdx.x * 256 + threadIdx.x;
   if (b >= a.nb) return;
+  const FrontierArgs& f = a.f;
   int open = 0;
-  for (int i = 0; i < a.nlit; ++i)
-    if (a.ub[(size_t)b * a.nlit + i] > a.thr[i]) open = 1;
-  int coord = -1, cmin = 0;
-  for (int t = 0; t < a.n0; ++t)
-    if ((a.splitmask >> t) & 1ull) {
-      const int v = a.cuts[(size_t)b * a.n0 + t];
-      if (coord < 0 || v < cmin) { coord = t; cmin = v; }
-    }
+  for (int i = 0; i < f.nlit; ++i)
+    if (a.ub[(size_t)b * f.nlit + i] > a.thr[i]) open = 1;
   a.open[b] = open;
-  a.coord[b] = coord;
+  a.coord[b] = frontier_coord(f.cuts + (size_t)b * f.n0, f.n0, a.splitmask);
 }
 
-// one thread per box: a closed box writes its row of the leaf log (its rank among the closed boxes is its position minus its rank among
-// the open ones); the r-th open box writes its children to slots 2r, 2r + 1 of the next frontier when the level's children fit the
-// budget (the host applies the same rule to the status record it reads back)
+// one thread per box: a closed box writes its row of the leaf log: lo, hi, depth, ub[:, b] (its rank among the closed boxes is its
+// position minus its rank among the open ones); the r-th open box writes its children to slots 2r, 2r + 1 of the next frontier when the
+// level's children fit the budget (the host applies the same rule to the status record it reads back)
 __global__ __launch_bounds__(256) void k_reach_scatter(ReachArgs a) {
-#pragma clang fp contract(off)      // numpy rounds every product and every sum
   const int b = blockIdx.x * 256 + threadIdx.x;
   if (b >= a.nb) return;
-  const int n0 = a.n0, nlit = a.nlit, r = a.slot[b];
-  const double* lo = a.lo + (size_t)b * n0;
-  const double* hi = a.hi + (size_t)b * n0;
+  const FrontierArgs& f = a.f;
+  const int nlit = f.nlit, r = a.slot[b];
   if (!a.open[b]) {
-    double* row = a.log + (size_t)(a.log_base + (b - r)) * (size_t)(2 * n0 + 1 + nlit);
-    for (int t = 0; t < n0; ++t) { row[t] = lo[t]; row[n0 + t] = hi[t]; }
-    row[2 * n0] = (double)a.depth;
-    for (int i = 0; i < nlit; ++i) row[2 * n0 + 1 + i] = a.ub[(size_t)b * nlit + i];
+    double* tail = frontier_log_row(f, f.log, f.log_base + (b - r), 2 * (size_t)f.n0 + 1 + nlit, b);
+    for (int i = 0; i < nlit; ++i) tail[i] = a.ub[(size_t)b * nlit + i];
     return;
   }
   const int j = a.coord[b];
   const long long nopen = a.status[2];
-  if (!a.children || j < 0 || (long long)a.visited + 2 * nopen > (long long)a.max_boxes) return;
-  const double mid = 0.5 * (lo[j] + hi[j]);
-  const size_t Lc = (size_t)(2 * (size_t)r) * n0, Rc = Lc + n0;
-  for (int t = 0; t < n0; ++t) {
-    const int cv = a.cuts[(size_t)b * n0 + t] + (t == j ? 1 : 0);
-    a.nlo[Lc + t] = lo[t];
-    a.nhi[Lc + t] = t == j ? mid : hi[t];
-    a.nlo[Rc + t] = t == j ? mid : lo[t];
-    a.nhi[Rc + t] = hi[t];
-    a.ncuts[Lc + t] = cv;
-    a.ncuts[Rc + t] = cv;
-  }
+  if (a.children && j >= 0 && (long long)a.visited + 2 * nopen <= (long long)a.max_boxes) frontier_bisect(f, b, j, 2 * (size_t)r);
 }
 
 }  // namespace nnsdp

@@ -80,6 +80,22 @@ def test_both_frontiers_give_the_same_enclosure_of_the_exact_maxima(case, box, o
         assert sizes.max() * (1 + len(fb["C"])) > 256, sizes       # a level with more points than one pass of the workgroup
 
 
+def test_a_level_longer_than_a_scan_tile():
+    """levels of more than 256 boxes: k_search_scan carries its offset over tiles, k_reach_scatter runs in workgroups after the first and
+    k_reach_incumbent walks the points with a stride.  The numpy restatement (reach_common.reference) converges after 3 937 boxes at depth
+    21 with four levels above 256, the largest 534"""
+    net = _state.setdefault("long", lc.random_net([4, 24, 24, 3], 3))
+    C = np.vstack([np.eye(3), -np.eye(3)])
+    lo, hi = -np.ones(4), np.ones(4)
+    host, dev = both(net, lo, hi, C, tol=2e-2, corner_points=False, max_boxes=4096)
+    sizes = np.bincount([lf.depth for lf in host.leaves]).astype(float)      # (level_sizes of test_split_frontier_gpu.py)
+    for d in range(len(sizes) - 2, -1, -1):
+        sizes[d] += sizes[d + 1] / 2
+    print(f"long level: {host.status} after {host.visited} boxes, depth {host.depth}; levels {sizes.astype(int).tolist()}")
+    rc.assert_same_reach(host, dev)
+    assert sizes.max() > 256, sizes
+
+
 def test_ten_outputs_take_the_pairwise_sum():
     net = _state.setdefault("wide", lc.random_net([3, 16, 16, 10], 110))
     C = lc.literal_rows(10, 9, 7)

@@ -284,7 +284,7 @@ def test_a_rejecting_confirm_walks_the_single_searchs_path():
 
 
 # ----------------------------------------------------------------------------- 7. scan sizes
-SCAN_BLOCK = 256          # kForestScanBlock of csrc/crown_forest.hpp
+SCAN_BLOCK = 256          # kForestScanBlock of csrc/crown_forest.hpp (kScanTile of csrc/crown_frontier.hpp)
 
 
 @pytest.mark.parametrize("R", [200, 33000])
