@@ -157,14 +157,16 @@ __device__ inline double cb_tanh_d_upper(double lower) {
   for (int it = 0; it < 100; ++it) { const double m = (l + r) / 2.0; if (ok(m)) r = m; else l = m; }
   return r;
 }
-// lw x + lb <= tanh(x) <= uw x + ub on [l, u]; only a neuron whose mask_both = 1 - pos - neg is not zero (l < 0 < u, and the
-// library's l = u = 0 with both masks) enters the bisections
+// lw x + lb <= tanh(x) <= uw x + ub on [l, u]; only a crossing neuron (l < 0 < u) enters the bisections.  Two departures from the
+// library, both for soundness (Tanh paragraph): l = u = 0 takes the l >= 0 regime alone (the library's two masks at once
+// put the lower line above tanh(0) and the upper one below), and an end beyond the clamp at +-500 turns the line that the clamped
+// fit would carry past it into a constant (tanh is monotone).  Any other interval keeps the library's operations and their bits.
 __device__ inline void cb_tanh_relax(double l, double u, double& lw, double& lb, double& uw, double& ub) {
   const double lower = l > -500.0 ? l : -500.0, upper = u < 500.0 ? u : 500.0;
   const double yl = tanh(lower), yu = tanh(upper);
   const double wd = upper - lower;
   const double kd = wd < 1e-6 ? cb_dtanh(upper) : (yu - yl) / (wd > 1e-6 ? wd : 1e-6);
-  const bool pos = l >= 0.0, neg = u <= 0.0;
+  const bool pos = l >= 0.0, neg = u <= 0.0 && !pos;
   const double m = (lower + upper) / 2.0, ym = tanh(m), km = cb_dtanh(m);
   lw = lb = uw = ub = 0.0;
   auto line = [](double k, double x0, double y0, double& w, double& b) { w += k; b += -x0 * k + y0; };
@@ -180,6 +182,8 @@ __device__ inline void cb_tanh_relax(double l, double u, double& lw, double& lb,
     if (kd < cb_dtanh(upper)) line(kd, lower, yl, w, b); else line(cb_dtanh(du), du, tanh(du), w, b);
     uw += fboth * w; ub += fboth * b;
   }
+  if (u > 500.0) { lw = 0.0; lb = yl; }
+  if (l < -500.0) { uw = 0.0; ub = yu; }
 }
 
 // One backward pass for box `box`.  head_identity == 0: bounds of W_{k-1} relu(... ) + b_{k-1}, i.e. the pre-activation of hidden

@@ -85,17 +85,18 @@ inline float tanh_d_upper(float lower) {
   for (int it = 0; it < 100; ++it) { const float m = (l + r) / 2.0f; if (ok(m)) r = m; else l = m; }
   return r;
 }
-// lw x + lb <= tanh(x) <= uw x + ub on [l, u]
+// lw x + lb <= tanh(x) <= uw x + ub on [l, u].  Two departures from the library, both for soundness (Tanh paragraph):
+// l = u = 0 takes the l >= 0 regime alone, and an end beyond the clamp at +-500 turns the line that the clamped fit would carry past
+// it into a constant.  Any other interval keeps the library's operations.
 inline void tanh_relax(float l, float u, float& lw, float& lb, float& uw, float& ub) {
   const float lower = std::max(l, -500.0f), upper = std::min(u, 500.0f);
   const float yl = std::tanh(lower), yu = std::tanh(upper);
   const float kd = (upper - lower) < 1e-6f ? dtanh_f(upper) : (yu - yl) / std::max(upper - lower, 1e-6f);
-  const bool pos = l >= 0.0f, neg = u <= 0.0f;
+  const bool pos = l >= 0.0f, neg = u <= 0.0f && !pos;
   const float m = (lower + upper) / 2.0f, ym = std::tanh(m), km = dtanh_f(m);
   lw = lb = uw = ub = 0.0f;
   auto line = [](float k, float x0, float y0, float& w, float& b) { w += k; b += -x0 * k + y0; };
-  // (a neuron with l >= 0 and u <= 0, i.e. l = u = 0, carries BOTH masks in the library - mask_both = 1 - pos - neg = -1 there;
-  // the three contributions are added exactly as the library adds them)
+  // (in the library a neuron with l = u = 0 carries BOTH masks and mask_both = 1 - pos - neg = -1; here the masks are exclusive)
   const float fpos = pos ? 1.0f : 0.0f, fneg = neg ? 1.0f : 0.0f, fboth = 1.0f - fpos - fneg;
   if (neg) { line(kd, lower, yl, uw, ub); line(km, m, ym, lw, lb); }
   if (pos) { line(kd, lower, yl, lw, lb); line(km, m, ym, uw, ub); }
@@ -108,6 +109,8 @@ inline void tanh_relax(float l, float u, float& lw, float& lb, float& uw, float&
     if (kd < dtanh_f(upper)) line(kd, lower, yl, w, b); else line(dtanh_f(du), du, std::tanh(du), w, b);
     uw += fboth * w; ub += fboth * b;
   }
+  if (u > 500.0f) { lw = 0.0f; lb = yl; }
+  if (l < -500.0f) { uw = 0.0f; ub = yu; }
 }
 
 // backward bound of  Ws[L-1] act(... act(Ws[0] x + bs[0]) ...) + bs[L-1]  over the box [lo, hi] (act = relu, or tanh when tanh_act);

@@ -91,7 +91,8 @@ def relax(l, u, dt, lib=Exact):
     yl, yu = lib.tanh(lower), lib.tanh(upper)
     wd = upper - lower
     kd = np.where(wd < dt(1e-6), _dtanh(upper, dt, lib), (yu - yl) / np.maximum(wd, dt(1e-6)))
-    pos, neg = l >= zero, u <= zero
+    pos = l >= zero
+    neg = (u <= zero) & ~pos                    # l = u = 0 takes the l >= 0 regime alone
     m = (lower + upper) / dt(2)
     ym, km = lib.tanh(m), _dtanh(m, dt, lib)
     fpos, fneg = pos.astype(dt), neg.astype(dt)
@@ -115,6 +116,9 @@ def relax(l, u, dt, lib=Exact):
         use = kd_b < _dtanh(up_b, dt, lib)
         uw[both] += fboth[both] * np.where(use, cw_b, tw)
         ub[both] += fboth[both] * np.where(use, cb_b, tb)
+    over, under = u > dt(500), l < dt(-500)      # an end beyond the clamp: the line the clamped fit would carry past it is a constant
+    lw, lb = np.where(over, zero, lw), np.where(over, yl, lb)
+    uw, ub = np.where(under, zero, uw), np.where(under, yu, ub)
     return lw, lb, uw, ub, np.where(neg, 0, np.where(pos, 1, 2))
 
 
