@@ -175,34 +175,32 @@ int nnsdp_solver_apply_minv_multi(nnsdp_solver* s, int32_t nrhs, const double* Q
   if (nrhs < 1) throw std::invalid_argument("nrhs must be >= 1");
   if (s->minv_structured) throw std::invalid_argument("the fused multi-vector product needs a dense M^-1 (this handle's is structured)");
   const int ng = s->S.ng, ldm = s->ldm, full = s->P.ng;
-  // every vector gets an IterArgs slot of its own (what the kernel reads of it: ng, ldm, Minv, qv, ww), as members of a batch have
+  // every vector gets an IterArgs slot of its own, as members of a batch have: the solver's binding with qv and ww redirected
   DBuf<double> qd, wd;
   std::vector<double> qh((size_t)nrhs * ldm, 0.0);
   for (int j = 0; j < nrhs; ++j)
     for (int g = 0; g < ng; ++g) qh[(size_t)j * ldm + g] = Q[(size_t)j * full + s->S.keep[g]];
   qd.upload(qh);
   wd.alloc((size_t)nrhs * ldm); wd.zero();
-  std::vector<IterArgs> it(nrhs);
+  std::vector<IterArgs> it(nrhs, s->iter_args());
   std::vector<int> mem(nrhs);
   std::vector<FusedPass> ps;
   for (int j = 0; j < nrhs; ++j) {
-    std::memset(&it[j], 0, sizeof(IterArgs));
-    it[j].ng = ng; it[j].ldm = ldm; it[j].Minv = s->Minv.p; it[j].qv = qd.p + (size_t)j * ldm; it[j].ww = wd.p + (size_t)j * ldm;
+    it[j].qv = qd.p + (size_t)j * ldm; it[j].ww = wd.p + (size_t)j * ldm;
     mem[j] = j;
     if (j % kFusedWidth == 0) ps.push_back(FusedPass{j, std::min<int>(kFusedWidth, nrhs - j)});
   }
   DBuf<IterArgs> dit; DBuf<int> dmem; DBuf<FusedPass> dps;
   dit.upload(it); dmem.upload(mem); dps.upload(ps);
-  hipEvent_t e0, e1;
-  HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-  HIPCHK(hipEventRecord(e0, s->st));
-  hipLaunchKernelGGL(k_minv_family, dim3(cdiv(ng, kFusedCols), (int)ps.size()), dim3(kThreads), 0, s->st, dit.p, dmem.p, dps.p);
-  HIPCHK(hipEventRecord(e1, s->st));
-  const hipError_t le = hipGetLastError(), se = hipStreamSynchronize(s->st);
+  EventPair ev;
+  ev.create();
+  HIPCHK(hipEventRecord(ev.e0, s->st));
+  launch_minv_family(s->tg, dit.p, dmem.p, dps.p, (int)ps.size(), s->st);
+  HIPCHK(hipEventRecord(ev.e1, s->st));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(s->st));
   float ms = 0.f;
-  if (le == hipSuccess && se == hipSuccess) (void)hipEventElapsedTime(&ms, e0, e1);
-  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-  HIPCHK(le); HIPCHK(se);
+  (void)hipEventElapsedTime(&ms, ev.e0, ev.e1);
   if (kernel_ms) *kernel_ms = ms;
   std::vector<double> o = wd.download();
   for (size_t i = 0; i < (size_t)nrhs * full; ++i) out[i] = 0.0;

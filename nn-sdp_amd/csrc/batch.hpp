@@ -1,4 +1,5 @@
 // The batch handle (nnsdp_batch): several solvers advanced in lockstep.  Part of the translation unit api.hip, after solver.hpp.
+// Behind the projection it launches the batch forms of admm_tail.hpp over a device table of the members' nnsdp_solver::iter_args().
 #pragma once
 
 // ---------------------------------------------------------------------------------------------
@@ -23,7 +24,7 @@ struct nnsdp_batch {
   DBuf<IterArgs> d_it_sym;
   DBuf<int> d_fmem;
   DBuf<FusedPass> d_fpass;
-  int n_sym = 0, n_fgroups = 0, n_fmembers = 0, n_fpass = 0, gx_fused = 0;
+  int n_sym = 0, n_fgroups = 0, n_fmembers = 0, n_fpass = 0;
   // members of a solver family with a structured inverse: the four stages of minv.hpp once per kMinvWidth members of a group
   // (k_minv_*_multi) instead of four launches per member.  A group of one keeps its member's own launches (equal bits); so does a
   // group whose factors are too large to stage in LDS, and every group under NNSDP_FAMILY_STRUCT=0 (diagnostic).
@@ -36,7 +37,7 @@ struct nnsdp_batch {
   int nblocks = 0, nmax = 0;
   bool any_structured = false, any_big = false;
   ProjPlan plan;
-  int gx_gather = 0, gx_gather_med = 0, gx_at_s = 0, gx_at_l = 0, gx_gemv = 0, gx_ax = 0, gx_ax_med = 0, gx_long = 0, gx_upd = 0, gx_tiles = 0, gx_nb = 0;
+  TailGrid grid;                       // per stage, the largest member's block count (admm_tail.hpp)
   hipGraph_t graph = nullptr;
   hipGraphExec_t gexec = nullptr;
   static constexpr int kGraphIters = 8;
@@ -70,13 +71,13 @@ struct nnsdp_batch {
   void rebuild() {
     if (gexec) { (void)hipGraphExecDestroy(gexec); gexec = nullptr; }
     if (graph) { (void)hipGraphDestroy(graph); graph = nullptr; }
-    n_sym = n_fgroups = n_fmembers = n_fpass = gx_fused = 0;
+    n_sym = n_fgroups = n_fmembers = n_fpass = 0;
     n_sgroups = n_smembers = n_spass = 0; sgrid = MinvMultiGrid(); struct_single.clear();
     if (act.empty()) return;
     std::vector<IterArgs> it;
     std::vector<ProjArgs> pw, pc;
     std::vector<int2> map;
-    nmax = 0; gx_gather = gx_gather_med = gx_at_s = gx_at_l = gx_gemv = gx_ax = gx_ax_med = gx_long = gx_upd = gx_tiles = gx_nb = 0;
+    nmax = 0; grid = TailGrid();
     any_structured = false; any_big = false;
     std::vector<IterArgs> it_sym;
     std::vector<std::pair<int, std::vector<int>>> fam;      // family id -> its dense members here, in batch order
@@ -98,26 +99,17 @@ struct nnsdp_batch {
       }
       HIPCHK(hipStreamSynchronize(s->st));
       s->since_cold = nnsdp_solver::kColdPeriod;   // lockstep: the next batched iteration is a cold one for everybody
-      IterArgs a;
-      a.ng = s->S.ng; a.NE = s->S.NE; a.ldm = s->ldm; a.nlong = s->nlong; a.nmat = s->nmat;
-      a.sptr = s->d_sptr.p; a.soff = s->d_soff.p; a.isdiag = s->d_isdiag.p;
-      a.csc_ptr = s->D.csc_ptr.p; a.csc_row = s->D.csc_row.p; a.csc_val = s->D.csc_val.p;
-      a.csr_ptr = s->D.csr_ptr.p; a.csr_col = s->D.csr_col.p; a.csr_val = s->D.csr_val.p;
-      a.longrows = s->d_long.p; a.gidx = s->d_gidx.p;
-      a.medrows = s->d_medrows.p; a.medsrc = s->d_medsrc.p; a.nmed = s->nmed; a.nmsrc = s->nmsrc; a.nnz = s->nnz_A;
-      a.colcls = s->d_colcls.p; a.ncs = s->ncs;
-      a.z0 = s->D.z0.p; a.Dinv = s->D.Dinv.p; a.c = s->D.c.p; a.Minv = s->Minv.p;
-      a.nu = s->nu.p; a.w = s->w.p; a.g = s->g.p; a.p = s->p.p; a.qv = s->qv.p; a.ww = s->ww.p; a.x = s->x.p;
-      a.sigma = s->d_sigma(); a.kappa = s->d_kappa(); a.alpha = s->opt.alpha;
-      if (fused) { a.symv_part = nullptr; gx_fused = std::max(gx_fused, cdiv(a.ng, kFusedCols)); }
+      IterArgs a = s->iter_args();
+      TailGrid mine(a);
+      if (fused) { a.symv_part = nullptr; mine.tiles = mine.nb = 0; }      // (the family pass; the tiled product's grid covers the others only)
       else {
-        const size_t nb = (size_t)(a.ng + 63) / 64;
+        const size_t nb = (size_t)mine.nb;
         if (!s->minv_structured && s->symv_part.n != nb * nb * 64) s->symv_part.alloc(nb * nb * 64);
         a.symv_part = s->symv_part.p;
-        gx_tiles = std::max(gx_tiles, cdiv((long long)(nb * (nb + 1) / 2), kThreads / 64));
-        gx_nb = std::max(gx_nb, (int)nb);
+        mine.family = 0;
         if (!s->minv_structured) it_sym.push_back(a);
       }
+      grid.cover(mine);
       it.push_back(a);
       pw.push_back(s->proj_args(true));      // (k0 = 0, k1 = ncl: create() refuses sharded solvers)
       pc.push_back(s->proj_args(false));
@@ -132,15 +124,6 @@ struct nnsdp_batch {
         for (size_t pos = 0; pos < s->proj_small.size(); ++pos) { map.push_back(make_int2((int)b, (int)pos)); nmax = std::max(nmax, s->cn[s->proj_small[pos]]); }
         any_big = true;
       }
-      gx_gather = std::max(gx_gather, cdiv(a.NE, kThreads));
-      gx_gather_med = std::max(gx_gather_med, cdiv((long long)a.nmsrc * 16, kThreads));
-      gx_ax_med = std::max(gx_ax_med, cdiv((long long)a.nmed * 16, kThreads));
-      gx_at_s = std::max(gx_at_s, cdiv((long long)a.ncs * 16, kThreads));
-      gx_at_l = std::max(gx_at_l, cdiv((long long)(a.ng - a.ncs) * 64, kThreads));
-      gx_gemv = std::max(gx_gemv, cdiv((long long)a.ng * 64, kThreads));
-      gx_ax = std::max(gx_ax, cdiv(a.NE, kThreads));
-      gx_long = std::max(gx_long, a.nlong);
-      gx_upd = std::max(gx_upd, cdiv(a.ng + a.nmat, kThreads));
     }
     nblocks = (int)map.size();
     nmax = std::max(nmax, 1);
@@ -199,28 +182,22 @@ struct nnsdp_batch {
     const int B = (int)act.size();
     if (nblocks > 0) launch_proj_batched(plan, warm ? d_pw.p : d_pc.p, d_map.p, nblocks, st);
     if (any_big) for (nnsdp_solver* s : act) s->enqueue_big_blocks(st);
-    hipLaunchKernelGGL(k_gather_g_b, dim3(gx_gather + gx_gather_med, B), dim3(kThreads), 0, st, d_it.p, gx_gather);
-    hipLaunchKernelGGL(k_spmv_At_b, dim3(std::max(gx_at_s + gx_at_l, 1), B), dim3(kThreads), 0, st, d_it.p, gx_at_s);
+    launch_gather(grid, d_it.p, B, st);
+    launch_At(grid, d_it.p, B, st);
     static const bool full_gemv = env_flag("NNSDP_BATCH_FULL_GEMV");   // diagnostic
     if (n_fpass > 0) {
       // the batch holds family members: one pass per group over the common inverse; structured members and solvers of no family
       // take the stage they take without families around (d_it_sym: the dense ones among them)
-      hipLaunchKernelGGL(k_minv_family, dim3(gx_fused, n_fpass), dim3(kThreads), 0, st, d_it.p, d_fmem.p, d_fpass.p);
+      launch_minv_family(grid, d_it.p, d_fmem.p, d_fpass.p, n_fpass, st);
       if (any_structured) { enqueue_structured(); for (nnsdp_solver* s : act) if (!s->minv_structured && s->family == 0) s->enqueue_minv(st); }
-      else if (n_sym > 0 && full_gemv) hipLaunchKernelGGL(k_gemv_sym_b, dim3(gx_gemv, n_sym), dim3(kThreads), 0, st, d_it_sym.p);
-      else if (n_sym > 0) {
-        hipLaunchKernelGGL(k_symv_tiles_b, dim3(gx_tiles, n_sym), dim3(kThreads), 0, st, d_it_sym.p);
-        hipLaunchKernelGGL(k_symv_reduce_b, dim3(gx_nb, n_sym), dim3(64), 0, st, d_it_sym.p);
-      }
+      else if (n_sym > 0 && full_gemv) launch_gemv(grid, d_it_sym.p, n_sym, st);
+      else if (n_sym > 0) launch_symv(grid, d_it_sym.p, n_sym, st);
     }
     else if (any_structured) { enqueue_structured(); for (nnsdp_solver* s : act) if (!s->minv_structured) s->enqueue_minv(st); }     // large multiplier counts: each SDP's structured M^-1
-    else if (full_gemv) hipLaunchKernelGGL(k_gemv_sym_b, dim3(gx_gemv, B), dim3(kThreads), 0, st, d_it.p);
-    else {
-      hipLaunchKernelGGL(k_symv_tiles_b, dim3(gx_tiles, B), dim3(kThreads), 0, st, d_it.p);
-      hipLaunchKernelGGL(k_symv_reduce_b, dim3(gx_nb, B), dim3(64), 0, st, d_it.p);
-    }
-    hipLaunchKernelGGL(k_spmv_A_x_all_b, dim3(gx_ax + gx_ax_med + gx_long, B), dim3(kThreads), 0, st, d_it.p, gx_ax, gx_ax_med, 0);
-    hipLaunchKernelGGL(k_update_nu_b, dim3(gx_upd, B), dim3(kThreads), 0, st, d_it.p);
+    else if (full_gemv) launch_gemv(grid, d_it.p, B, st);
+    else launch_symv(grid, d_it.p, B, st);
+    launch_Ax(grid, d_it.p, B, st);
+    launch_update(grid, d_it.p, B, st);
     HIPCHK(hipGetLastError());
   }
 

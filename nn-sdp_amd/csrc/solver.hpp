@@ -1,6 +1,7 @@
 // The solver handle (nnsdp_solver): set-up, the iteration loop and its graphs, the clique-sharded exchange, the certificate.  With it
 // the device-resident operators, the library path of the blocks above the LDS kernel's range and the device half of the sparse NSD
-// check.  Part of the translation unit api.hip, which includes the kernel headers and host_common.hpp first.
+// check.  proj_args() and iter_args() bind its state to the kernels' argument blocks (kernels.hip, admm_tail.hpp); the iteration is the
+// sequence of their launch functions.  Part of the translation unit api.hip, which includes the kernel headers and host_common.hpp first.
 #pragma once
 
 namespace nnsdp {
@@ -311,8 +312,9 @@ struct nnsdp_solver {
   DBuf<unsigned int> d_gidx;
   DBuf<double> Tg, Ug;
   DBuf<double> nu, w, Vg, x, g, p, qv, ww, Minv, scal /* sigma, kappa */, acc /* 8 control numbers | ng multipliers (sharded resync) */, gs;
-  DBuf<double> accp;                    // per-workgroup partial sums of the residual quantities: [7][acc_stride]
-  int acc_stride = 0, nb_upd = 0, nb_dual = 0, nb_obj = 0;
+  DBuf<double> accp;                    // per-workgroup partial sums of the residual quantities: [7][tg.check_stride()]
+  nnsdp::IterArgs ia{};                 // iter_args(), bound once in setup_member: what the solver's own launches behind the projection take
+  nnsdp::TailGrid tg;                   // their workgroups per stage (admm_tail.hpp)
   bool big_fail = false;                // a library eigensolve of a block above the LDS kernel's range reported info != 0
   // structured M^-1 (minv.hpp): used instead of the dense inverse for large multiplier counts
   bool minv_structured = false;
@@ -364,7 +366,7 @@ struct nnsdp_solver {
   DBuf<int> d_sptr_own;
   DBuf<long long> d_soff_own;
   DBuf<double> hsum;
-  // device-side transport of the sharded mode (hipIpc-mapped peer buffers, kernels.hip: k_ipc_publish / k_ipc_reduce)
+  // device-side transport of the sharded mode (hipIpc-mapped peer buffers, admm_tail.hpp: k_ipc_publish / k_ipc_reduce)
   bool ipc = false;
   DBuf<double> xbuf;                    // [2][NE] slots + 2 flag words
   DBuf<unsigned long long> ipc_ctr;
@@ -624,11 +626,9 @@ struct nnsdp_solver {
     if (plan.packed()) { Tg.alloc(nmat); Tg.zero(); Ug.alloc(nmat); Ug.zero(); }      // scratch of the packed variant (warm start, rotation log; new basis of its refinement stage)
     x.alloc(S.NE); g.alloc(S.NE); p.alloc(ng); qv.alloc(ldm); ww.alloc(ng); gs.alloc(ng);
     scal.alloc(4); acc.alloc(8 + (size_t)ng); acc.zero();
-    nb_upd = cdiv(ng + nmat, kThreads);
-    nb_dual = cdiv((long long)S.NE * 16, kThreads) + nlong;
-    nb_obj = cdiv(std::max(ng, S.NE), kThreads);
-    acc_stride = std::max({nb_upd, nb_dual, nb_obj});
-    accp.alloc(7 * (size_t)acc_stride);
+    ia = iter_args();
+    tg = TailGrid(ia);
+    accp.alloc(7 * (size_t)tg.check_stride());
     nu.zero(); w.zero(); Vg.zero(); x.zero(); g.zero(); qv.zero();
     {
       std::vector<double> s0(ng);
@@ -912,7 +912,7 @@ struct nnsdp_solver {
   // ww = M^-1 qv on stream s_ (dense GEMV or the structured form)
   void enqueue_minv(hipStream_t s_) {
     if (minv_structured) apply_structured_minv(qv.p, ww.p, s_);
-    else hipLaunchKernelGGL(k_gemv_sym, dim3(cdiv((long long)S.ng * 64, kThreads)), dim3(kThreads), 0, s_, S.ng, ldm, Minv.p, qv.p, ww.p);
+    else launch_gemv(tg, ia, s_);
   }
 
   void set_comm(int nr, int rk, const char* id128, nnsdp_allreduce_fn fn = nullptr, void* user = nullptr, bool use_ipc = false) {
@@ -1085,6 +1085,24 @@ struct nnsdp_solver {
     HIPCHK(pipe.build(lst.data(), (int)lst.size(), nmat));
     pipe_on = pipe.ready && pipe_mode == 3;
   }
+  // the arguments of the launches behind the projection (admm_tail.hpp): the ONE binding of the solver's state to IterArgs, used by
+  // the solver's own launches (bound once in setup_member: `ia`), by a batch handle for its device table and by
+  // nnsdp_solver_apply_minv_multi.  Nothing it names is allocated anew after set-up but symv_part, which only batch handles read.
+  IterArgs iter_args() {
+    IterArgs a;
+    a.ng = S.ng; a.NE = S.NE; a.ldm = ldm; a.nlong = nlong; a.nmat = nmat;
+    a.sptr = d_sptr.p; a.soff = d_soff.p; a.isdiag = d_isdiag.p;
+    a.csc_ptr = D.csc_ptr.p; a.csc_row = D.csc_row.p; a.csc_val = D.csc_val.p;
+    a.csr_ptr = D.csr_ptr.p; a.csr_col = D.csr_col.p; a.csr_val = D.csr_val.p;
+    a.longrows = d_long.p; a.gidx = d_gidx.p;
+    a.medrows = d_medrows.p; a.medsrc = d_medsrc.p; a.nmed = nmed; a.nmsrc = nmsrc; a.nnz = nnz_A;
+    a.colcls = d_colcls.p; a.ncs = ncs;
+    a.z0 = D.z0.p; a.Dinv = D.Dinv.p; a.c = D.c.p; a.Minv = Minv.p;
+    a.nu = nu.p; a.w = w.p; a.g = g.p; a.p = p.p; a.qv = qv.p; a.ww = ww.p; a.x = x.p;
+    a.sigma = d_sigma(); a.kappa = d_kappa(); a.alpha = opt.alpha;
+    a.symv_part = symv_part.p;
+    return a;
+  }
   // the projection kernel's arguments for this SDP's blocks k0 .. k1 (all of them outside the clique-sharded mode): the ONE binding of
   // the iteration state to ProjArgs, used by the solver's own launches and, member by member, by a batch handle's lockstep launch
   ProjArgs proj_args(bool warm) {
@@ -1136,57 +1154,30 @@ struct nnsdp_solver {
 
   // hsum <- sum over ranks of the rank's own partial consensus sum (dual = 1: of nu - w): RCCL / the caller's collective, or the
   // device-side transport (partial into this rank's mapped slot, publish, sum of all ranks' slots in rank order)
-  void exchange_h(int dual) {
-    const int ng = S.ng, NE = S.NE;
-    hipLaunchKernelGGL(k_gather_h, dim3(cdiv((long long)NE * kGatherLanes, kThreads)), dim3(kThreads), 0, st, NE, d_sptr_own.p, d_soff_own.p, d_isdiag.p,
-                       nu.p + ng, w.p + ng, dual, ipc ? xbuf.p : hsum.p, ipc ? ipc_ctr.p : (const unsigned long long*)nullptr);
-    if (ipc) {
-      hipLaunchKernelGGL(nnsdp::k_ipc_publish, dim3(1), dim3(64), 0, st, ipa);
-      hipLaunchKernelGGL(nnsdp::k_ipc_reduce, dim3(cdiv(NE, kThreads)), dim3(kThreads), 0, st, ipa, hsum.p);
-    } else allreduce(hsum.p, NE);
+  void exchange_h(const IterArgs& a, int dual) {
+    launch_gather_h(tg, a, d_sptr_own.p, d_soff_own.p, dual, ipc ? xbuf.p : hsum.p, ipc ? ipc_ctr.p : (const unsigned long long*)nullptr, st);
+    if (ipc) launch_ipc_exchange(tg, ipa, hsum.p, st);
+    else allreduce(hsum.p, S.NE);
   }
 
   // enqueue one iteration on the stream; check=true also accumulates the residual sums
   void enqueue_iteration(bool check, bool warm, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr) {
-    int ng = S.ng, NE = S.NE;
+    const IterArgs& a = ia;
     if (e0) HIPCHK(hipEventRecord(e0, st));
     enqueue_proj(warm);
     if (e1) HIPCHK(hipEventRecord(e1, st));
     if (sharded) {
-      exchange_h(0);                              // the overlap-consensus exchange: one all-reduce per iteration
-      hipLaunchKernelGGL(k_finish_g, dim3(cdiv(NE, kThreads)), dim3(kThreads), 0, st, NE, hsum.p, D.z0.p, D.Dinv.p, d_sigma(), g.p);
-    } else {
-      const int nshort = cdiv(NE, kThreads);
-      hipLaunchKernelGGL(k_gather_g, dim3(nshort + cdiv((long long)nmsrc * 16, kThreads)), dim3(kThreads), 0, st, nshort, NE, d_sptr.p, d_soff.p, d_isdiag.p,
-                         nu.p + ng, w.p + ng, D.z0.p, D.Dinv.p, d_sigma(), g.p, d_medsrc.p, nmsrc);
-    }
-    {
-      const int nsb = cdiv((long long)ncs * 16, kThreads);
-      hipLaunchKernelGGL(k_spmv_At, dim3(std::max(nsb + cdiv((long long)(ng - ncs) * 64, kThreads), 1)), dim3(kThreads), 0, st, nsb, ng, D.csc_ptr.p, D.csc_row.p,
-                         D.csc_val.p, g.p, nu.p, D.c.p, d_kappa(), p.p, qv.p, d_colcls.p, ncs);
-    }
-    if (check) {
-      if (sharded) {
-        exchange_h(1);
-      }
-      const int nreg_cd = nb_dual - nlong;
-      hipLaunchKernelGGL(k_check_dual, dim3(nb_dual), dim3(kThreads), 0, st, NE, ng, nreg_cd, nlong, d_long.p, D.csr_ptr.p,
-                         D.csr_col.p, D.csr_val.p, d_sptr.p, d_soff.p, d_isdiag.p, nu.p, w.p, D.z0.p, d_sigma(), accp.p,
-                         sharded ? hsum.p : (const double*)nullptr, acc_stride);
-    }
+      exchange_h(a, 0);                           // the overlap-consensus exchange: one all-reduce per iteration
+      launch_finish_g(tg, a, hsum.p, st);
+    } else launch_gather(tg, a, st);
+    launch_At(tg, a, st);
+    if (check && sharded) exchange_h(a, 1);
+    if (check) launch_check_dual(tg, a, accp.p, sharded ? hsum.p : (const double*)nullptr, st);
     enqueue_minv(st);
-    {
-      const int nshort = cdiv(NE, kThreads), nreg = nshort + cdiv((long long)nmed * 16, kThreads);
-      hipLaunchKernelGGL(k_spmv_A_x_all, dim3(nreg + nlong), dim3(kThreads), 0, st, NE, nshort, nreg, nlong, d_long.p, D.csr_ptr.p, D.csr_col.p,
-                         D.csr_val.p, ww.p, g.p, D.Dinv.p, x.p, d_medrows.p, nmed, nnz_A);
-    }
-    if (check)
-      hipLaunchKernelGGL(k_check_obj, dim3(nb_obj), dim3(kThreads), 0, st, ng, NE, nu.p, D.c.p, D.z0.p, x.p, d_sigma(), accp.p, acc_stride);
-    hipLaunchKernelGGL(k_update_nu, dim3(nb_upd), dim3(kThreads), 0, st, ng, nmat, p.p, ww.p, D.c.p, x.p,
-                       d_gidx.p, nu.p, w.p, opt.alpha, d_kappa(), check ? accp.p : (double*)nullptr, coff[k0], coff[k1],
-                       (!sharded || rank == 0) ? 1 : 0, acc_stride);
-    if (check)   // fixed-order second stage of the residual sums (no atomics on the way to a stopping decision)
-      hipLaunchKernelGGL(k_acc_reduce, dim3(1), dim3(kThreads), 0, st, accp.p, acc_stride, nb_upd, nb_dual, nb_obj, acc.p);
+    launch_Ax(tg, a, st);
+    if (check) launch_check_obj(tg, a, accp.p, st);
+    launch_update(tg, a, check ? accp.p : (double*)nullptr, coff[k0], coff[k1], (!sharded || rank == 0) ? 1 : 0, st);
+    if (check) launch_acc_reduce(tg, accp.p, acc.p, st);      // fixed-order second stage of the residual sums (no atomics on the way to a stopping decision)
     if (check && sharded) {
       // every stopping / adaptation decision is taken from these 8 numbers, so they must be bit-identical on all ranks:
       // [0..2] residual sums of the clique blocks live on their owners (multiplier block counted on rank 0 only);
@@ -1196,14 +1187,14 @@ struct nnsdp_solver {
       // construction at every check iteration; x + 0 + ... + 0 is exact).  One all-reduce distributes all of it.
       if (rank != 0) {
         HIPCHK(hipMemsetAsync(acc.p + 3, 0, 4 * sizeof(double), st));
-        HIPCHK(hipMemsetAsync(acc.p + 8, 0, (size_t)ng * sizeof(double), st));
-      } else HIPCHK(hipMemcpyAsync(acc.p + 8, nu.p, (size_t)ng * sizeof(double), hipMemcpyDeviceToDevice, st));
+        HIPCHK(hipMemsetAsync(acc.p + 8, 0, (size_t)a.ng * sizeof(double), st));
+      } else HIPCHK(hipMemcpyAsync(acc.p + 8, nu.p, (size_t)a.ng * sizeof(double), hipMemcpyDeviceToDevice, st));
       const double tflag = (opt.max_time > 0 && loop_t0 > 0 && now_s() - loop_t0 > opt.max_time) ? 1.0 : 0.0;
       tflag_host = tflag;
       HIPCHK(hipMemcpyAsync(acc.p + 7, &tflag_host, sizeof(double), hipMemcpyHostToDevice, st));
       if (!big_idx.empty()) hipLaunchKernelGGL(k_fold_flag, dim3(1), dim3(1), 0, st, big_flag.p, acc.p + 7);      // (only block owners run dsyevd)
-      allreduce(acc.p, 8 + (size_t)ng);
-      HIPCHK(hipMemcpyAsync(nu.p, acc.p + 8, (size_t)ng * sizeof(double), hipMemcpyDeviceToDevice, st));
+      allreduce(acc.p, 8 + (size_t)a.ng);
+      HIPCHK(hipMemcpyAsync(nu.p, acc.p + 8, (size_t)a.ng * sizeof(double), hipMemcpyDeviceToDevice, st));
     }
     HIPCHK(hipGetLastError());
   }

@@ -7,6 +7,9 @@ batch case is a SolverBatch of three problems of different sizes after iterate(2
 Every case forces the dense M^-1 (minv_mode = 1): the solver cases then run k_gemv_sym (odd multiplier counts 203, 347, 803, 1 965 and
 the even 600 of W10-D10 beta 2, whose rows have no last single element); the batch case runs the tiled product of the batch handle
 (k_symv_tiles_b), not that kernel - it gates the batch forms of the sparse launches and the multiplier update.
+A sharded case is a solver case on a one-rank clique-sharded handle (set_comm_callback(1, 0, ...): the all-reduce of one rank leaves its
+buffer alone), the branch no other case takes: k_gather_h and k_finish_g in place of k_gather_g, k_check_dual reading the exchanged sum,
+k_update_nu with the rank's element range and the resynchronisation of the multiplier block.  Such a handle replays no graph.
 usage: python tools/tail_bits.py [out.json]     (default tests/golden/tail_bits_parent.json; run on a build of the commit to compare against)"""
 import hashlib, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -23,6 +26,8 @@ FIXTURES = (("W20-D10", 0, "single", (1, 9, 60)),      # every class of row, col
             ("W10-D10", 2, "double", (1, 9, 60)),      # ng 600: an even multiplier count
             ("W40-D20", 0, "single", (1, 9)))          # columns above 256 nonzeros, more than one GEMV group
 MODES = ("eager", "graph", "advance")
+SHARDED = (("W10-D5", 3, "double", (1, 9, 60)),)       # several cliques, NE 230, ng 347
+SHARDED_MODES = ("eager", "advance")
 BATCH = (("W10-D5", 0, "single"), ("W10-D5", 3, "double"), ("W10-D10", 2, "double"))
 BATCH_ITERS = 24
 
@@ -37,6 +42,7 @@ def _sha(*arrays):
 def cases():
     """(id, kind, ...)"""
     out = [(f"{name}-b{beta}-{dec}-{mode}", "solver", name, beta, dec, counts, mode) for name, beta, dec, counts in FIXTURES for mode in MODES]
+    out += [(f"{name}-b{beta}-{dec}-sharded1-{mode}", "sharded", name, beta, dec, counts, mode) for name, beta, dec, counts in SHARDED for mode in SHARDED_MODES]
     out.append(("batch-" + "+".join(f"{n}-b{b}" for n, b, _ in BATCH), "batch"))
     return out
 
@@ -64,10 +70,12 @@ def run_case(case):
         out = {f"residuals{i}": _sha(r) for i, r in enumerate(res)}
         out.update({f"objective{i}": _sha([v]) for i, v in enumerate(obj)})
         return out
-    _, _, name, beta, dec, counts, mode = case
+    _, kind, name, beta, dec, counts, mode = case
     q, o = _solver_args(name, beta, dec)
     s = na.Solver(q, o)
     try:
+        if kind == "sharded":
+            s.set_comm_callback(1, 0, lambda a: None)
         out, done = {}, 0
         for n in (counts if mode != "advance" else counts[-1:]):      # (advance: one call, so that the check iteration falls where the solve loop puts it)
             if mode == "eager":
