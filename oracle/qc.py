@@ -337,17 +337,18 @@ def scale_S(S, alphas, net: FeedFwdNet) -> np.ndarray:
 
 
 def make_qc_activs(net: FeedFwdNet, x1min, x1max, beta: int,
-                   intv: Optional[IntervalsInfo] = None):
+                   intv: Optional[IntervalsInfo] = None, activ: str = "relu"):
+    """activ = "tanh": the sliced intervals and the sector of TanhActiv (activ_sector.jl:76-88); the sector QC carries the activation"""
     if intv is None:
-        intv = intervals_crown_sliced(net, x1min, x1max)
+        intv = intervals_crown_sliced(net, x1min, x1max, activ=activ)
     acdim = int(sum(net.xdims[1:-1]))
     acymin = np.concatenate([iv[0] for iv in intv.x_intvs[1:-1]])
     acymax = np.concatenate([iv[1] for iv in intv.x_intvs[1:-1]])
     qc_bounded = QcActivBounded(acymin=acymin, acymax=acymax)
     sec_min = np.concatenate([iv[0] for iv in intv.acx_intvs])
     sec_max = np.concatenate([iv[1] for iv in intv.acx_intvs])
-    smin, smax = make_sector_min_max(sec_min, sec_max)
-    qc_sector = QcActivSector(acxdim=acdim, beta=beta, smin=smin, smax=smax)
+    smin, smax = make_sector_min_max(sec_min, sec_max, activ)
+    qc_sector = QcActivSector(acxdim=acdim, beta=beta, smin=smin, smax=smax, activ=activ)
     assert qc_bounded.acydim == acdim
     return qc_bounded, qc_sector
 
