@@ -447,6 +447,38 @@ int nnsdp_crown_bound_alpha(nnsdp_crown* h, int32_t nbox, const double* x1min, c
                             int32_t steps, double eta0, double decay, const double* alpha0,
                             double* a_smax, double* a_uA, double* a_ub0, double* alpha, int32_t* best_step);
 
+/* Bounds on the nodes of a ReLU split (beta-CROWN style; DESIGN.md section 5, csrc/crown_relu_split.hpp).  A node is an input box and
+ * an assignment s in {-1, 0, +1}^acdim, ordered like acymin: +1 forces the pre-activation z_n >= 0, -1 forces z_n <= 0, 0 leaves the
+ * neuron free.  Every number returned for a node is a valid bound over {x in box : s_n z_n(x) >= 0 for all forced n}.
+ * Plain pass: a forced neuron's relaxation is exact (+1: du = dl = 1, -1: du = dl = 0, bu = 0), a free neuron keeps the arithmetic of
+ * nnsdp_crown_bound; the pre-activation bounds of a forced neuron are clipped (+1: l <- max(l, 0), -1: u <- min(u, 0)) and a node with
+ * l > u afterwards is infeasible (its other numbers mean nothing).  branch: per literal the free neuron with l < 0 < u that has the
+ * largest  max(lambda, 0) bu  (lambda the upper matrix entry entering the neuron; ties: the lowest index), -1 without a candidate.
+ * Multipliers: per literal, `steps` projected-gradient steps on one multiplier beta_n >= 0 per forced neuron, which enters the upper
+ * bound's backward pass as  A[n] += s_n beta_n  behind the row scaling of the neuron's layer; g_n = s_n z_n(x*), z the pre-activations
+ * of the relaxed network at the maximiser of the linear bound; beta <- max(beta - eta g / max|g|, 0), eta <- eta decay from eta0.
+ * smax / uA / ub0 / best_step are the first iterate with the smallest smax: never above smax_plain (iterate 0), and with no forced
+ * neuron equal to it with best_step 0.  steps in 0..64, eta0 > 0 finite, decay in (0, 1].
+ * x1min / x1max [xdims[0] x nnode], assign [acdim x nnode] (neuron index fastest).  Outputs (HOST pointers, any may be NULL): pre_lo,
+ * pre_hi [acdim x nnode] the clipped pre-activation bounds; smin, smax_plain, smax, ub0 [nlit x nnode]; uA [xdims[0] x nlit x nnode];
+ * best_step, branch [nlit x nnode]; infeasible [nnode]; kernel_ms.  One upload, two launches, one download, one synchronisation; the
+ * node buffers of the handle are allocated at the first call, grow like the others and are counted by nnsdp_crown_info.  No atomics:
+ * a node's bits depend neither on nnode, nor on its position, nor on the other literals, nor on earlier calls.
+ * -1 with a message, before the GPU is touched: steps, eta0 or decay out of range (checked first, also on a NULL handle), a wide
+ * handle, a Tanh handle, a handle without literals, an assign entry outside {-1, 0, 1}. */
+int nnsdp_crown_bound_nodes(nnsdp_crown* h, int32_t nnode, const double* x1min, const double* x1max, const int8_t* assign,
+                            int32_t steps, double eta0, double decay, double* pre_lo, double* pre_hi, double* smin,
+                            double* smax_plain, double* smax, double* uA, double* ub0, int32_t* best_step, int32_t* branch,
+                            int32_t* infeasible, double* kernel_ms);
+
+/* The same recurrences for ONE node in the float32 host routine (csrc/intervals.hpp), multiplier steps included; no GPU needed.
+ * assign [acdim]; the outputs as above with nnode = 1 (uA [xdims[0] x nlit]), infeasible one int32.  -1 with a message for a Tanh
+ * network, nlit outside 1..64, an assign entry outside {-1, 0, 1}, steps, eta0 or decay out of range.  ReLU only, any width. */
+int nnsdp_make_intervals_nodes(int32_t K, const int32_t* xdims, const double* M, int32_t activ, const double* x1min,
+                               const double* x1max, const int8_t* assign, int32_t nlit, const double* normals, int32_t steps,
+                               double eta0, double decay, double* pre_lo, double* pre_hi, double* smin, double* smax_plain,
+                               double* smax, double* uA, double* ub0, int32_t* best_step, int32_t* branch, int32_t* infeasible);
+
 /* The sampled forward pass on the resident network: the kernel, launch geometry and bits of the one-shot sampled forward entry. */
 int nnsdp_crown_eval(nnsdp_crown* h, int64_t N, const double* X, double* Y, double* kernel_ms);
 

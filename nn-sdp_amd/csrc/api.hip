@@ -12,6 +12,7 @@
 #include "crown_batch.hpp"
 #include "crown_wide.hpp"
 #include "crown_alpha.hpp"
+#include "crown_relu_split.hpp"
 #include "crown_search.hpp"
 #include "crown_forest.hpp"
 #include "crown_reach.hpp"
@@ -648,6 +649,43 @@ int nnsdp_crown_bound_alpha(nnsdp_crown* h, int32_t nbox, const double* x1min, c
   if (!h) throw std::invalid_argument("null handle");
   double* const host[nnsdp::CrownLayout::kSegs] = {acymin, acymax, acxmin, acxmax, ymin, ymax, smin, smax, ub0, uA};
   h->bound_alpha(nbox, x1min, x1max, host, kernel_ms, steps, eta0, decay, alpha0, a_smax, a_uA, a_ub0, alpha, best_step);
+  API_END
+}
+
+int nnsdp_crown_bound_nodes(nnsdp_crown* h, int32_t nnode, const double* x1min, const double* x1max, const int8_t* assign,
+                            int32_t steps, double eta0, double decay, double* pre_lo, double* pre_hi, double* smin,
+                            double* smax_plain, double* smax, double* uA, double* ub0, int32_t* best_step, int32_t* branch,
+                            int32_t* infeasible, double* kernel_ms) {
+  API_BEGIN
+  const nnsdp_crown::NodeOut out{pre_lo, pre_hi, smin, smax_plain, smax, uA, ub0, best_step, branch, infeasible, kernel_ms};
+  nnsdp_crown::bound_nodes(h, nnode, x1min, x1max, assign, steps, eta0, decay, out);
+  API_END
+}
+
+int nnsdp_make_intervals_nodes(int32_t K, const int32_t* xdims, const double* M, int32_t activ, const double* x1min,
+                               const double* x1max, const int8_t* assign, int32_t nlit, const double* normals, int32_t steps,
+                               double eta0, double decay, double* pre_lo, double* pre_hi, double* smin, double* smax_plain,
+                               double* smax, double* uA, double* ub0, int32_t* best_step, int32_t* branch, int32_t* infeasible) {
+  API_BEGIN
+  check_node_options(steps, eta0, decay);
+  if (activ != NNSDP_ACTIV_RELU && activ != NNSDP_ACTIV_TANH) throw std::invalid_argument("unknown activation");
+  if (activ != NNSDP_ACTIV_RELU) throw std::invalid_argument("a ReLU split is for ReLU networks, not Tanh");
+  if (nlit < 1 || nlit > nnsdp::kCbW) throw std::invalid_argument("a ReLU split needs literals: nlit must be in 1..64, got " + std::to_string(nlit));
+  if (K < 2 || !xdims || !M || !x1min || !x1max || !assign) throw std::invalid_argument("make_intervals_nodes: bad arguments");
+  size_t acdim = 0;
+  for (int k = 0; k <= K; ++k) {
+    if (xdims[k] <= 0) throw std::invalid_argument("make_intervals_nodes: layer widths must be positive");
+    if (k > 0 && k < K) acdim += (size_t)xdims[k];
+  }
+  check_literals(xdims[K], nlit, normals);
+  nnsdp::check_boxes(1, xdims[0], x1min, x1max);
+  check_assign(assign, acdim);
+  const nnsdp::LitHead head = nnsdp::make_lit_head(K, xdims, M, nlit, normals);
+  const nnsdp::NodeOut no = nnsdp::make_intervals_nodes(K, xdims, M, head, x1min, x1max, assign, steps, eta0, decay);
+  auto put = [](const auto& v, auto* dst) { if (dst) std::copy(v.begin(), v.end(), dst); };
+  put(no.pre_lo, pre_lo); put(no.pre_hi, pre_hi); put(no.smin, smin); put(no.smax_plain, smax_plain); put(no.smax, smax);
+  put(no.uA, uA); put(no.ub0, ub0); put(no.best_step, best_step); put(no.branch, branch);
+  if (infeasible) *infeasible = no.infeasible;
   API_END
 }
 

@@ -60,6 +60,15 @@ struct CrownArgs {
   double* ub0;              // nlit x nbox
 };
 
+// The node of a ReLU split (crown_relu_split.hpp), read by crown_pass<.., SPLIT = true> alone: the assignment of the node's hidden
+// neurons (+1: z >= 0, -1: z <= 0, 0: free), where the literal pass records its branching neuron, and the thread's copy of the
+// node's infeasibility flag (the same value in all 256 threads).
+struct CrownSplit {
+  const int8_t* assign;     // acdim x nnode
+  double* branch;           // nlit x nnode, a neuron index or -1, as a double (one download brings everything back)
+  int infeasible;
+};
+
 static constexpr int kCbW = 64;        // widest layer
 static constexpr int kCbChunk = 8;     // k-steps whose weight operands are in flight together
 static constexpr size_t kCbLdsBytes = (2 * kCbW * kCbW + 8 * kCbW) * sizeof(double);
@@ -192,8 +201,13 @@ __device__ inline void cb_tanh_relax(double l, double u, double& lw, double& lb,
 // LIT: the literal pass (k == K, head_identity == 0): the head is a.H instead of M_{K-1}, nout = nlit, the results go raw to smin /
 // smax with the upper bound's coefficients and constant to uA / ub0.
 // ACT: the activation (kCbRelu / kCbTanh); the ReLU instance is what this function was before it had the parameter.
-template <bool LIT, int ACT = kCbRelu>
-__device__ void crown_pass(const CrownArgs& a, double* lds, long long box, int k, int head_identity) {
+// SPLIT (ReLU only, LDS kCbLdsBytesTanh: v_bl marks the branching candidates): the passes on a node of a ReLU split.  A forced neuron's
+// relaxation is exact (+1: du = dl = 1, -1: du = dl = 0, bu = 0 in both), a pre-activation pass clips the bounds it writes to the forced
+// side and flags l > u, and the upper row of the literal pass records the free unstable neuron with the largest max(lambda, 0) bu
+// (ties: the lowest neuron index).  SPLIT = false compiles to what the function was without the parameter.
+template <bool LIT, int ACT = kCbRelu, bool SPLIT = false>
+__device__ void crown_pass(const CrownArgs& a, double* lds, long long box, int k, int head_identity, CrownSplit* sp = nullptr) {
+  static_assert(!SPLIT || ACT == kCbRelu, "a ReLU split is for ReLU networks");
   double* A[2] = {lds, lds + kCbW * kCbW};
   double* v_du = lds + 2 * kCbW * kCbW;
   double* v_dl = v_du + kCbW;
@@ -210,6 +224,8 @@ __device__ void crown_pass(const CrownArgs& a, double* lds, long long box, int k
   int d = head_identity ? nout : a.xdims[k - 1];
   const int jtop = head_identity ? k - 1 : k - 2;
   double bias = 0.0;
+  double br_score = -1.0;      // SPLIT, LIT, the upper rows: the best branching score so far and its neuron
+  int br_n = -1;
   {
     const double* Mh = LIT ? a.H : a.M + a.moff[k - 1];
     for (int idx = tid; idx < nout * d; idx += 256) {
@@ -249,6 +265,14 @@ __device__ void crown_pass(const CrownArgs& a, double* lds, long long box, int k
       v_dl[tid] = du > 0.5 ? 1.0 : 0.0;
       v_bu[tid] = -lrx * du;
       v_bj[tid] = Mj[(size_t)in * d + tid];
+      if (SPLIT) {
+        const int sv = sp->assign[(size_t)box * a.acdim + a.acoff[j] + tid];
+        if (sv != 0) {
+          v_du[tid] = v_dl[tid] = sv > 0 ? 1.0 : 0.0;
+          v_bu[tid] = 0.0;
+        }
+        v_bl[tid] = (sv == 0 && l < 0.0 && u > 0.0) ? 1.0 : 0.0;
+      }
     }
     __syncthreads();
     if (tid < 128 && row < nout) {
@@ -260,6 +284,11 @@ __device__ void crown_pass(const CrownArgs& a, double* lds, long long box, int k
         const double du = v_du[t], dl = v_dl[t];
         if (ACT == kCbTanh) s += mat ? xp * v_bu[t] + xn * v_bl[t] : xn * v_bu[t] + xp * v_bl[t];
         else s += (mat ? xp : xn) * v_bu[t];
+        if (SPLIT && LIT && mat && v_bl[t] != 0.0) {
+          const double sc = xp * v_bu[t];
+          const int n = a.acoff[j] + t;
+          if (sc > br_score || (sc == br_score && n < br_n)) { br_score = sc; br_n = n; }
+        }
         const double y = mat ? xp * du + xn * dl : xp * dl + xn * du;
         Am[cb_idx(t, row)] = y;
         tl += y * v_bj[t];
@@ -333,6 +362,7 @@ __device__ void crown_pass(const CrownArgs& a, double* lds, long long box, int k
     }
     v_res[mat * kCbW + row] = mat ? s + rr + bias : s - rr + bias;
     if (LIT && mat && a.ub0) a.ub0[(size_t)box * nout + row] = bias;
+    if (SPLIT && LIT && mat) sp->branch[(size_t)box * nout + row] = (double)br_n;
   }
   __syncthreads();
   if (LIT) {
@@ -345,6 +375,24 @@ __device__ void crown_pass(const CrownArgs& a, double* lds, long long box, int k
         const int i = idx / d, t = idx - i * d;
         a.uA[((size_t)box * nout + i) * d + t] = A[1][cb_idx(t, i)];
       }
+  } else if (SPLIT && !head_identity && k < a.K) {
+    bool bad = false;
+    if (tid < nout) {
+      double l = v_res[tid], u = v_res[kCbW + tid];
+      const int sv = sp->assign[(size_t)box * a.acdim + a.acoff[k - 1] + tid];
+      if (sv > 0) l = l > 0.0 ? l : 0.0;
+      if (sv < 0) u = u < 0.0 ? u : 0.0;
+      bad = l > u;
+      double* pre = a.scratch + (size_t)box * kScr * a.acdim + a.acoff[k - 1];
+      pre[tid] = l;
+      pre[a.acdim + tid] = u;
+    }
+    // the node's flag through LDS, read back in a fixed order by every thread; the kernel stores it from one thread
+    __syncthreads();
+    if (tid < nout) v_res[tid] = bad ? 1.0 : 0.0;
+    __syncthreads();
+    for (int t = 0; t < nout; ++t)
+      if (v_res[t] != 0.0) sp->infeasible = 1;
   } else if (tid < nout) {
     const double l = v_res[tid], u = v_res[kCbW + tid];
     if (!head_identity && k < a.K) {

@@ -23,6 +23,18 @@ static void check_alpha0(const double* alpha0, size_t count) {
     if (!std::isfinite(alpha0[k])) throw std::invalid_argument("alpha0 has a non-finite entry (NaN or infinity) at index " + std::to_string(k));
 }
 
+// the options and the assignments of the node entries (nnsdp_crown_bound_nodes, nnsdp_make_intervals_nodes)
+static void check_node_options(int32_t steps, double eta0, double decay) {
+  if (steps < 0 || steps > 64) throw std::invalid_argument("nodes: steps must be in 0..64, got " + std::to_string(steps));
+  if (!std::isfinite(eta0) || !(eta0 > 0.0)) throw std::invalid_argument("nodes: eta0 must be positive and finite");
+  if (!(decay > 0.0 && decay <= 1.0)) throw std::invalid_argument("nodes: decay must be in (0, 1]");
+}
+static void check_assign(const int8_t* assign, size_t count) {
+  for (size_t k = 0; k < count; ++k)
+    if (assign[k] < -1 || assign[k] > 1)
+      throw std::invalid_argument("nodes: assign must hold -1, 0 or +1, got " + std::to_string((int)assign[k]) + " at index " + std::to_string(k));
+}
+
 // The device buffers of one kind of frontier search (csrc/crown_frontier_host.hpp): the two frontiers (fr: lo and hi of the first, then
 // of the second; cu: the cuts of both, then, with `roots`, the root of every box of both), one block of doubles and one of ints that
 // the search carves into records, points and leaf logs.  They only grow.  A handle has one set per kind of search
@@ -76,7 +88,10 @@ struct nnsdp_crown {
   // nnsdp_crown_bound_alpha only (nothing before its first call): boxes then alpha0; the plain outputs then the alpha outputs; the state
   DBuf<double> dain, daout, dast;
   double *hain = nullptr, *haout = nullptr;
-  size_t box_cap = 0, pin_cap = 0, sample_cap = 0, alpha_cap = 0;
+  // nnsdp_crown_bound_nodes only (nothing before its first call): boxes then assignments; every output; the multiplier state
+  DBuf<double> dnin, dnout, dnst;
+  double *hnin = nullptr, *hnout = nullptr;
+  size_t box_cap = 0, pin_cap = 0, sample_cap = 0, alpha_cap = 0, node_cap = 0;
   hipStream_t st = nullptr;
   hipEvent_t e0 = nullptr, e1 = nullptr;
   long long n_alloc = 0, n_upload = 0, n_bound = 0;
@@ -119,6 +134,7 @@ struct nnsdp_crown {
   size_t ain_per_box() const { return 2 * (size_t)n0 + layout(1).nst(); }
   size_t aout_per_box() const { return layout(1).alpha_total(); }
   size_t ast_per_box() const { return 3 * layout(1).nst(); }
+  nnsdp::CrownNodeLayout node_layout(size_t nnode) const { return nnsdp::CrownNodeLayout{nnode, (size_t)n0, (size_t)acdim, (size_t)nlit}; }
   bool wide() const { return max_width > nnsdp::kCbW; }
   size_t lds_bytes() const {
     if (wide()) return activ == NNSDP_ACTIV_TANH ? kCwLdsBytesTanh : kCwLdsBytes;
@@ -138,7 +154,7 @@ struct nnsdp_crown {
   }
   size_t device_bytes() const {
     return dxd.bytes() + dao.bytes() + dmo.bytes() + dM.bytes() + din.bytes() + dscr.bytes() + dout.bytes() + dX.bytes() + dY.bytes() +
-           dain.bytes() + daout.bytes() + dast.bytes() + sbuf.bytes() + rbuf.bytes() + fbuf.bytes();
+           dain.bytes() + daout.bytes() + dast.bytes() + dnin.bytes() + dnout.bytes() + dnst.bytes() + sbuf.bytes() + rbuf.bytes() + fbuf.bytes();
   }
   // the capacity grows geometrically and never shrinks
   // staging = false (a search: nothing of a box crosses the bus): the pinned copies wait for the next bound call
@@ -164,6 +180,19 @@ struct nnsdp_crown {
     dalloc(dain, cap * ain_per_box()); dalloc(daout, cap * aout_per_box()); dalloc(dast, cap * ast_per_box());
     pinned(hain, cap * ain_per_box()); pinned(haout, cap * aout_per_box());
     alpha_cap = cap;
+  }
+  // the buffers of the node calls: they share nothing with the box entries, whose scratch holds no clipped bounds
+  void reserve_nodes(size_t nnode) {
+    if (nnode <= node_cap) return;
+    if (!node_cap) {
+      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_crown_nodes), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kCbLdsBytesTanh));
+      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_crown_beta), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kCnLdsBytes));
+    }
+    const size_t cap = std::max(nnode, 2 * node_cap);
+    const nnsdp::CrownNodeLayout L = node_layout(cap);
+    dalloc(dnin, L.in_doubles()); dalloc(dnout, L.total()); dalloc(dnst, 2 * L.nst());
+    pinned(hnin, L.in_doubles()); pinned(hnout, L.total());
+    node_cap = cap;
   }
   void reserve_samples(size_t N) {
     if (N <= sample_cap) return;
@@ -327,6 +356,72 @@ struct nnsdp_crown {
     }
   }
 
+  // nnsdp_crown_bound_nodes (csrc/crown_relu_split.hpp).  h may be null: the scalar options come first so that their refusals can be
+  // tested on a machine without a GPU, where no handle exists
+  struct NodeOut {
+    double *pre_lo, *pre_hi, *smin, *smax_plain, *smax, *uA, *ub0;
+    int32_t *best_step, *branch, *infeasible;
+    double* kernel_ms;
+  };
+  static void bound_nodes(nnsdp_crown* h, int32_t nnode, const double* x1min, const double* x1max, const int8_t* assign, int32_t steps,
+                          double eta0, double decay, const NodeOut& out) {
+    check_node_options(steps, eta0, decay);
+    if (!h) throw std::invalid_argument("null handle");
+    if (h->wide()) throw std::invalid_argument("a ReLU split is not available on a wide bounder (max_width 128): the node kernels keep a 64-wide layout");
+    if (h->activ != NNSDP_ACTIV_RELU) throw std::invalid_argument("a ReLU split is for ReLU networks, not Tanh");
+    if (h->nlit < 1) throw std::invalid_argument("a ReLU split needs literals: the handle was created without normals");
+    if (nnode < 0) throw std::invalid_argument("nnode must be >= 0");
+    if (nnode == 0) return;
+    if (!x1min || !x1max || !assign) throw std::invalid_argument("null argument");
+    const int n0 = h->n0, acdim = h->acdim;
+    nnsdp::check_boxes(nnode, n0, x1min, x1max);
+    check_assign(assign, (size_t)nnode * acdim);
+    const nnsdp::CrownNodeLayout L = h->node_layout((size_t)nnode);
+    const size_t nin = L.nnode * n0, nl = L.nl();
+    h->reserve_nodes(L.nnode);
+    // one upload: the boxes, then the assignments as bytes
+    std::copy(x1min, x1min + nin, h->hnin);
+    std::copy(x1max, x1max + nin, h->hnin + nin);
+    int8_t* hasg = reinterpret_cast<int8_t*>(h->hnin + 2 * nin);
+    std::copy(assign, assign + L.nnode * acdim, hasg);
+    hipStream_t st = h->st;
+    HIPCHK(hipMemcpyAsync(h->dnin.p, h->hnin, 2 * nin * sizeof(double) + L.nnode * acdim, hipMemcpyHostToDevice, st));
+    nnsdp::CrownNodeArgs p;
+    p.c.K = h->K; p.c.xdims = h->dxd.p; p.c.moff = h->dmo.p; p.c.acoff = h->dao.p; p.c.M = h->dM.p; p.c.H = h->dM.p + h->moff[h->K];
+    p.c.lo = h->dnin.p; p.c.hi = h->dnin.p + nin;
+    p.sp.assign = reinterpret_cast<const int8_t*>(h->dnin.p + 2 * nin); p.sp.infeasible = 0;
+    L.point(p, h->dnout.p);
+    p.steps = steps; p.eta0 = eta0; p.decay = decay;
+    p.cur = h->dnst.p; p.lam = p.cur + L.nst();
+    HIPCHK(hipEventRecord(h->e0, st));
+    hipLaunchKernelGGL(nnsdp::k_crown_nodes, dim3((unsigned)nnode), dim3(256), nnsdp::kCbLdsBytesTanh, st, p);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(nnsdp::k_crown_beta, dim3((unsigned)nnode), dim3(256), nnsdp::kCnLdsBytes, st, p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(h->e1, st));
+    HIPCHK(hipMemcpyAsync(h->hnout, h->dnout.p, L.total() * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    ++h->n_bound;
+    const float ms = h->elapsed_ms();
+    if (out.kernel_ms) *out.kernel_ms = ms;
+    const double* src = h->hnout;
+    for (size_t b = 0; b < L.nnode; ++b, src += 2 * acdim) {
+      if (out.pre_lo) std::copy(src, src + acdim, out.pre_lo + b * acdim);
+      if (out.pre_hi) std::copy(src + acdim, src + 2 * acdim, out.pre_hi + b * acdim);
+    }
+    auto ints = [](const double* s, size_t n, int32_t* dst) {
+      if (dst) for (size_t k = 0; k < n; ++k) dst[k] = (int32_t)s[k];
+    };
+    double* const dbl[4] = {out.smin, out.smax_plain, out.smax, out.ub0};
+    for (int o = 0; o < 4; ++o, src += nl)
+      if (dbl[o]) std::copy(src, src + nl, dbl[o]);
+    ints(src, nl, out.best_step); src += nl;
+    ints(src, nl, out.branch); src += nl;
+    if (out.uA) std::copy(src, src + L.nA(), out.uA);
+    src += L.nA();
+    ints(src, L.nnode, out.infeasible);
+  }
+
   // nnsdp_crown_eval
   void eval(int64_t N, const double* X, double* Y, double* kernel_ms) {
     if (N < 0) throw std::invalid_argument("N must be >= 0");
@@ -364,7 +459,7 @@ struct nnsdp_crown {
 
   ~nnsdp_crown() {
     if (st) (void)hipStreamSynchronize(st);
-    for (double* h : {hin, hout, hX, hY, hain, haout}) if (h) (void)hipHostFree(h);
+    for (double* h : {hin, hout, hX, hY, hain, haout, hnin, hnout}) if (h) (void)hipHostFree(h);
     if (hstatus) (void)hipHostFree(hstatus);
     if (hforest) (void)hipHostFree(hforest);
     if (e0) (void)hipEventDestroy(e0);

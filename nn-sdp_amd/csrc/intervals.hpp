@@ -382,4 +382,157 @@ inline AlphaOut lits_alpha(int K, const int32_t* xdims, const double* M, const L
   return out;
 }
 
+// ---- bounds on a node of a ReLU split ("Branching on unstable ReLUs"; the kernels are in crown_relu_split.hpp): the
+// box and an assignment s in {-1, 0, +1}^acdim (+1: z_n >= 0, -1: z_n <= 0, 0: free).  float32 like the passes above.  A forced neuron's
+// relaxation is exact, the pre-activation bounds are clipped to the forced side (l > u afterwards: the node is infeasible), and per
+// literal `steps` projected-gradient steps on one multiplier beta_n >= 0 per forced neuron tighten the upper bound.
+struct NodeOut {
+  std::vector<double> pre_lo, pre_hi;            // acdim, clipped
+  std::vector<double> smin, smax_plain, smax, uA, ub0;      // nlit; uA nlit x n0 (row-major); smax / uA / ub0 of the best iterate
+  std::vector<int32_t> best_step, branch;        // nlit
+  int infeasible = 0;
+};
+inline NodeOut make_intervals_nodes(int K, const int32_t* xdims, const double* M, const LitHead& head, const double* x1min,
+                                    const double* x1max, const int8_t* assign, int steps, double eta0, double decay) {
+  const int nlit = head.nlit, n0 = xdims[0];
+  std::vector<DenseF> W(K - 1);
+  std::vector<std::vector<float>> bs(K - 1);
+  std::vector<int> aoff(K, 0);
+  size_t off = 0;
+  for (int k = 0; k + 1 < K; ++k) {
+    const int r = xdims[k + 1], c = xdims[k];
+    W[k] = DenseF(r, c); bs[k].resize(r);
+    for (int j = 0; j < c; ++j)
+      for (int i = 0; i < r; ++i) W[k].at(i, j) = (float)M[off + (size_t)j * r + i];
+    for (int i = 0; i < r; ++i) bs[k][i] = (float)M[off + (size_t)c * r + i];
+    off += (size_t)r * (c + 1);
+    aoff[k + 1] = aoff[k] + r;
+  }
+  const int acdim = aoff[K - 1];
+  std::vector<float> du(acdim), dl(acdim), bu(acdim), pl(acdim), pu(acdim), c0(n0), r0(n0);
+  std::vector<char> cand(acdim);
+  for (int q = 0; q < n0; ++q) {
+    const float lo = (float)x1min[q], hi = (float)x1max[q];
+    c0[q] = (hi + lo) / 2.0f; r0[q] = (hi - lo) / 2.0f;
+  }
+  NodeOut out;
+  // One row of a backward pass from layer `top` (its coefficients in `row`, its constant in `cst`) down to the input.  upper: the upper
+  // bound's pair (else the lower bound's).  beta (upper only): the multipliers, added behind the row scaling.  lam receives the
+  // coefficients that enter every neuron; br (upper only): the branching neuron.  Returns the concretised bound, `row` the input row.
+  std::vector<float> nxt;
+  auto backward = [&](std::vector<float>& row, float& cst, int top, bool upper, const float* beta, float* lam, int* br) {
+    float bscore = -1.0f;
+    for (int j = top; j >= 0; --j) {
+      const int d = xdims[j + 1], in = xdims[j], o = aoff[j];
+      float sb = 0.0f;
+      for (int t = 0; t < d; ++t) {
+        const float b = row[t], bp = std::max(b, 0.0f), bn = std::min(b, 0.0f);
+        if (lam) lam[o + t] = b;
+        sb += (upper ? bp : bn) * bu[o + t];
+        if (br && cand[o + t]) {
+          const float sc = bp * bu[o + t];
+          if (sc > bscore || (sc == bscore && o + t < *br)) { bscore = sc; *br = o + t; }
+        }
+        float y = upper ? bp * du[o + t] + bn * dl[o + t] : bp * dl[o + t] + bn * du[o + t];
+        if (beta && assign[o + t] != 0) y += (float)assign[o + t] * beta[o + t];
+        row[t] = y;
+      }
+      cst += sb;
+      float tl = 0.0f;
+      for (int t = 0; t < d; ++t) tl += row[t] * bs[j][t];
+      cst += tl;
+      nxt.assign(in, 0.0f);
+      for (int t = 0; t < d; ++t) {
+        const float b = row[t];
+        if (b == 0.0f) continue;
+        const float* w = &W[j].a[(size_t)t * in];
+        for (int q = 0; q < in; ++q) nxt[q] += b * w[q];
+      }
+      row.swap(nxt);
+    }
+    float sc = 0.0f, rr = 0.0f;
+    for (int q = 0; q < n0; ++q) { sc += row[q] * c0[q]; rr += std::fabs(row[q]) * r0[q]; }
+    return upper ? sc + rr + cst : sc - rr + cst;
+  };
+  // the pre-activation bounds, layer by layer, clipped; then the layer's relaxation
+  std::vector<float> row;
+  for (int k = 0; k + 1 < K; ++k) {
+    const int d = xdims[k + 1], in = xdims[k], o = aoff[k];
+    for (int t = 0; t < d; ++t) {
+      float l = 0.0f, u = 0.0f;
+      for (int side = 0; side < 2; ++side) {
+        row.assign(W[k].a.begin() + (size_t)t * in, W[k].a.begin() + (size_t)(t + 1) * in);
+        float cst = bs[k][t];
+        const float v = backward(row, cst, k - 1, side == 1, nullptr, nullptr, nullptr);
+        (side ? u : l) = v;
+      }
+      const int sv = assign[o + t];
+      if (sv > 0) l = std::max(l, 0.0f);
+      if (sv < 0) u = std::min(u, 0.0f);
+      if (l > u) out.infeasible = 1;
+      pl[o + t] = l; pu[o + t] = u;
+    }
+    for (int t = 0; t < d; ++t) {
+      const int n = o + t, sv = assign[n];
+      const float lr = std::min(pl[n], 0.0f), ur = std::max(std::max(pu[n], 0.0f), lr + 1e-8f);
+      du[n] = ur / (ur - lr);
+      dl[n] = du[n] > 0.5f ? 1.0f : 0.0f;
+      bu[n] = -lr * du[n];
+      if (sv != 0) { du[n] = dl[n] = sv > 0 ? 1.0f : 0.0f; bu[n] = 0.0f; }
+      cand[n] = sv == 0 && pl[n] < 0.0f && pu[n] > 0.0f;
+    }
+  }
+  out.pre_lo.assign(pl.begin(), pl.end()); out.pre_hi.assign(pu.begin(), pu.end());
+  out.smin.assign(nlit, 0.0); out.smax_plain.assign(nlit, 0.0); out.smax.assign(nlit, 0.0); out.ub0.assign(nlit, 0.0);
+  out.uA.assign((size_t)nlit * n0, 0.0); out.best_step.assign(nlit, 0); out.branch.assign(nlit, -1);
+  const int dtop = xdims[K - 1];
+  std::vector<float> beta(acdim), lam(acdim), g(acdim), z, zn;
+  for (int i = 0; i < nlit; ++i) {
+    auto head_row = [&](float& cst) {
+      row.assign(dtop, 0.0f);
+      for (int t = 0; t < dtop; ++t) row[t] = (float)head.H[(size_t)t * nlit + i];
+      cst = (float)head.H[(size_t)dtop * nlit + i];
+    };
+    float cst;
+    head_row(cst);
+    out.smin[i] = backward(row, cst, K - 2, false, nullptr, nullptr, nullptr);
+    std::fill(beta.begin(), beta.end(), 0.0f);
+    float best = 0.0f, eta = (float)eta0;
+    for (int s = 0; s <= steps; ++s) {
+      head_row(cst);
+      int br = -1;
+      const float smax = backward(row, cst, K - 2, true, beta.data(), lam.data(), s == 0 ? &br : nullptr);
+      if (s == 0) { out.smax_plain[i] = smax; out.branch[i] = br; }
+      if (s == 0 || smax < best) {
+        best = smax;
+        out.smax[i] = smax; out.ub0[i] = cst; out.best_step[i] = s;
+        for (int q = 0; q < n0; ++q) out.uA[(size_t)i * n0 + q] = row[q];
+      }
+      if (s == steps) break;
+      // gradient: the relaxed network the pass chose, at the maximiser x* = c + sgn(uA) r
+      z.assign(n0, 0.0f);
+      for (int q = 0; q < n0; ++q) z[q] = c0[q] + (row[q] > 0.0f ? r0[q] : row[q] < 0.0f ? -r0[q] : 0.0f);
+      float gmax = 0.0f;
+      for (int j = 0; j + 1 < K; ++j) {
+        const int d = xdims[j + 1], in = xdims[j], o = aoff[j];
+        zn.assign(d, 0.0f);
+        for (int t = 0; t < d; ++t) {
+          float v = 0.0f;
+          for (int q = 0; q < in; ++q) v += W[j].at(t, q) * z[q];
+          v += bs[j][t];
+          const int sv = assign[o + t];
+          g[o + t] = sv != 0 ? (float)sv * v : 0.0f;
+          gmax = std::max(gmax, std::fabs(g[o + t]));
+          zn[t] = lam[o + t] > 0.0f ? du[o + t] * v + bu[o + t] : dl[o + t] * v;
+        }
+        z.swap(zn);
+      }
+      if (!(gmax > 0.0f)) break;          // stationary (no forced neuron, or every one of them at zero)
+      for (int n = 0; n < acdim; ++n) beta[n] = std::max(beta[n] - eta * g[n] / gmax, 0.0f);
+      eta *= (float)decay;
+    }
+  }
+  return out;
+}
+
 }  // namespace nnsdp

@@ -10,6 +10,7 @@ from .methods import (  # noqa: F401
 from .frontend import (  # noqa: F401
     read_nnet, evalFeedFwdNet, evalFeedFwdNetBatch, sampleTrajs, randomNetwork, makeIntervalsInfo, makeQcActivs, approxEllipsoid,
     findEllipsoid, findCircle, findReach2Dpoly, write_scale_csv, runScale, ellipsoidQuery, makeIntervalsBatch, LiteralBounds, LiteralBoundsAlpha, CrownBounder,
+    NodeBounds, makeIntervalsNodes,
 )
 from . import _lib  # noqa: F401
 from . import vnnlib  # noqa: F401
@@ -18,5 +19,7 @@ from .vnnlib import (  # noqa: F401
 )
 from . import split  # noqa: F401
 from .split import SplitOptions, SplitResult, Leaf, verifySplit, verifySplitMany, reachSplit, ReachSplitResult, ReachLeaf, findReach2DpolySplit  # noqa: F401
+from . import relusplit  # noqa: F401
+from .relusplit import ReluSplitOptions, ReluLeaf, ReluSplitResult, verifyReluSplit  # noqa: F401
 
 __version__ = "0.2.0"

@@ -107,6 +107,10 @@ SYMBOLS = [
      + [C.c_int32, C.c_double, C.c_double] + [c_double_p] * 5 + [c_int32_p]),
     ("nnsdp_make_intervals_lits_alpha", C.c_int, [C.c_int32, c_int32_p, c_double_p, C.c_int32, c_double_p, c_double_p] + [c_double_p] * 8
      + [C.c_int32, c_double_p] + [c_double_p] * 4 + [C.c_int32, C.c_double, C.c_double] + [c_double_p] * 5 + [c_int32_p]),
+    ("nnsdp_crown_bound_nodes", C.c_int, [C.c_void_p, C.c_int32, c_double_p, c_double_p, C.POINTER(C.c_int8), C.c_int32, C.c_double, C.c_double]
+     + [c_double_p] * 7 + [c_int32_p] * 3 + [c_double_p]),
+    ("nnsdp_make_intervals_nodes", C.c_int, [C.c_int32, c_int32_p, c_double_p, C.c_int32, c_double_p, c_double_p, C.POINTER(C.c_int8), C.c_int32,
+                                             c_double_p, C.c_int32, C.c_double, C.c_double] + [c_double_p] * 7 + [c_int32_p] * 3),
     ("nnsdp_crown_eval", C.c_int, [C.c_void_p, C.c_int64, c_double_p, c_double_p, c_double_p]),
     ("nnsdp_crown_search", C.c_int, [C.c_void_p, c_double_p, c_double_p, C.c_int32, c_double_p, c_double_p] + [C.c_int32] * 5
      + [C.c_void_p, C.c_void_p] + [c_int32_p] * 4 + [c_double_p, c_double_p]),

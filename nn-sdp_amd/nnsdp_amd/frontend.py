@@ -346,6 +346,76 @@ def makeIntervalsBatch(net: M.FeedFwdNet, lo, hi, backend: str = "host", workers
     return res + (ms.value,) if return_ms else res
 
 
+class NodeBounds(NamedTuple):
+    """bounds on nnode nodes of a ReLU split (CrownBounder.bound_nodes, makeIntervalsNodes): node b is the box lo[:, b] / hi[:, b] with
+    the assignment assign[:, b] in {-1, 0, +1} (+1: z_n >= 0, -1: z_n <= 0, 0: free), and every number is valid over the points of
+    the box that satisfy the forced signs.  normal_i' f(x) <= A[i, :, b]' x + b0[i, b] there, and smax = A' c + |A|' r + b0."""
+    pre_lo: np.ndarray        # acdim x nnode: the pre-activation bounds, clipped at the forced neurons
+    pre_hi: np.ndarray
+    smin: np.ndarray          # nlit x nnode
+    smax_plain: np.ndarray    # nlit x nnode: without multipliers
+    smax: np.ndarray          # nlit x nnode: the best iterate of the multiplier steps, never above smax_plain
+    A: np.ndarray             # nlit x n0 x nnode, of that iterate
+    b0: np.ndarray            # nlit x nnode
+    best_step: np.ndarray     # nlit x nnode, int32
+    branch: np.ndarray        # nlit x nnode, int32: the neuron to branch on for the literal, -1 without a candidate
+    infeasible: np.ndarray    # nnode, bool: a forced sign contradicts the bounds; the node's other numbers mean nothing
+
+
+def _node_args(lo, hi, assign, n0, acdim):
+    lo = np.asarray(lo, dtype=np.float64)
+    hi = np.asarray(hi, dtype=np.float64)
+    if lo.ndim != 2 or lo.shape[0] != n0 or hi.shape != lo.shape:
+        raise ValueError("lo / hi must be xdims[0] x nnode")
+    asg = np.asarray(assign)
+    if asg.shape != (acdim, lo.shape[1]):
+        raise ValueError("assign must be acdim x nnode")
+    if not np.isin(asg, (-1, 0, 1)).all():
+        raise ValueError("assign must hold -1, 0 or +1")
+    return np.ascontiguousarray(lo.T), np.ascontiguousarray(hi.T), np.ascontiguousarray(asg.T, dtype=np.int8)
+
+
+def _node_outs(nnode, nlit, n0, acdim):
+    dbl = [np.zeros((nnode, acdim)), np.zeros((nnode, acdim))] + [np.zeros((nnode, nlit)) for _ in range(3)] + \
+        [np.zeros((nnode, nlit, n0)), np.zeros((nnode, nlit))]
+    return dbl, [np.zeros((nnode, nlit), dtype=np.int32), np.zeros((nnode, nlit), dtype=np.int32), np.zeros(nnode, dtype=np.int32)]
+
+
+def _node_bounds(dbl, ints):
+    return NodeBounds(dbl[0].T, dbl[1].T, dbl[2].T, dbl[3].T, dbl[4].T, dbl[5].transpose(1, 2, 0), dbl[6].T, ints[0].T, ints[1].T,
+                      ints[2].astype(bool))
+
+
+def makeIntervalsNodes(net: M.FeedFwdNet, lo, hi, assign, normals, steps: int = 0, eta0: float = 0.5, decay: float = 0.9,
+                       workers: int = 16) -> NodeBounds:
+    """bounds on the nodes of a ReLU split from the float32 host routine (nnsdp_make_intervals_nodes, csrc/intervals.hpp), one call per
+    node on a thread pool of at most 16 workers; no GPU needed.  lo / hi xdims[0] x nnode, assign acdim x nnode, normals nlit x xdims[K].
+    The GPU route is CrownBounder.bound_nodes."""
+    lib = _lib.load()
+    xd, Mp = _net_arrays(net)
+    n0, acdim, ny = int(xd[0]), int(xd[1:-1].sum()), int(xd[-1])
+    nrm = None if normals is None else np.ascontiguousarray(normals, dtype=np.float64)
+    if nrm is not None and (nrm.ndim != 2 or nrm.shape[1] != ny):
+        raise ValueError("normals must be nlit x xdims[K]")
+    nlit = 0 if nrm is None else nrm.shape[0]
+    loc, hic, asg = _node_args(lo, hi, assign, n0, acdim)
+    nnode, dp, ip, bp = loc.shape[0], _lib.c_double_p, _lib.c_int32_p, C.POINTER(C.c_int8)
+    dbl, ints = _node_outs(nnode, nlit, n0, acdim)
+    xdp, Mpp, nrp, activ = xd.ctypes.data_as(ip), Mp.ctypes.data_as(dp), None if nrm is None else nrm.ctypes.data_as(dp), M._activ_code(net.activ)
+
+    def one(b):
+        return lib.nnsdp_make_intervals_nodes(net.K, xdp, Mpp, activ, loc[b].ctypes.data_as(dp), hic[b].ctypes.data_as(dp),
+                                              asg[b].ctypes.data_as(bp), nlit, nrp, int(steps), float(eta0), float(decay),
+                                              *[o[b].ctypes.data_as(dp) for o in dbl], ints[0][b].ctypes.data_as(ip),
+                                              ints[1][b].ctypes.data_as(ip), ints[2][b:b + 1].ctypes.data_as(ip))
+
+    if nnode:
+        _lib.check(one(0))          # the refusals of the arguments, with their message
+        if nnode > 1:
+            _host_pool(lambda b: one(b + 1), nnode - 1, workers, "nnsdp_make_intervals_nodes")
+    return _node_bounds(dbl, ints)
+
+
 # ----------------------------------------------------------------------------- f2: callers of the path
 def evalFeedFwdNetBatch(net: M.FeedFwdNet, X, return_ms: bool = False):
     """the network at the columns of X (xdims[0] x N) on the GPU: nnsdp_eval_network (csrc/forward.hpp, fp64 MFMA, one wave per
@@ -463,6 +533,21 @@ class CrownBounder:
         if self._nlit is not None:
             res += (LiteralBounds(louts[0].T, louts[1].T, louts[2].transpose(1, 2, 0), louts[3].T),)
         return res + (ms.value,) if return_ms else res
+
+    def bound_nodes(self, lo, hi, assign, steps: int = 0, eta0: float = 0.5, decay: float = 0.9, return_ms: bool = False):
+        """nnsdp_crown_bound_nodes: bounds on the nodes of a ReLU split (csrc/crown_relu_split.hpp) -> NodeBounds (then the event time of
+        both kernels with return_ms).  lo / hi xdims[0] x nnode; assign acdim x nnode in {-1, 0, +1}; steps multiplier steps per literal.
+        Narrow ReLU bounders with normals; anything else raises before the GPU is touched."""
+        h = self._handle()
+        loc, hic, asg = _node_args(lo, hi, assign, self._n0, self._acdim)
+        nnode, dp, ip = loc.shape[0], _lib.c_double_p, _lib.c_int32_p
+        dbl, ints = _node_outs(nnode, self._nlit or 0, self._n0, self._acdim)
+        ms = C.c_double(0.0)
+        _lib.check(self._lib.nnsdp_crown_bound_nodes(h, nnode, loc.ctypes.data_as(dp), hic.ctypes.data_as(dp), asg.ctypes.data_as(C.POINTER(C.c_int8)),
+                                                     int(steps), float(eta0), float(decay), *[o.ctypes.data_as(dp) for o in dbl],
+                                                     *[o.ctypes.data_as(ip) for o in ints], C.byref(ms)))
+        res = _node_bounds(dbl, ints)
+        return (res, ms.value) if return_ms else res
 
     def eval(self, X, return_ms: bool = False):
         """what evalFeedFwdNetBatch(net, X) returns, from the resident network"""

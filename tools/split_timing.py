@@ -1,6 +1,11 @@
 #!/usr/bin/env python3
 """Batched CROWN bounds: the GPU kernel against the host routine, and where one verifySplit spends its time.
-usage: python tools/split_timing.py [--nlit | --resident | --alpha | --frontier | --reach | --wide | --forest] [case ...]   cases: W10-D5 W40-D20 acas-shape   (default: all)
+usage: python tools/split_timing.py [--nlit | --resident | --alpha | --frontier | --reach | --wide | --forest | --relu] [case ...]   cases: W10-D5 W40-D20 acas-shape   (default: all)
+With --relu only the ReLU-split leg runs (cases W10-D5 and W40-D20 by default) and profiles/split_timing_relu.json is written:
+  bound    CrownBounder.bound_nodes at 1, 256 and 4096 nodes with 0 and 16 multiplier steps beside CrownBounder.bound on the same boxes in
+           the same process: HIP-event time of the launches (median, min, max of 7 after 2 warm calls) and the median wall-clock of the call
+  search   verifyReluSplit against verifySplit (both crown_backend "resident", bounds only) on a 16-input and a 12-input net: verdict,
+           nodes / boxes visited, milliseconds (median, min, max of 5 after 1 warm run); --no-search leaves it out
 With --forest only the forest leg runs (cases W10-D5 and acas-shape by default) and profiles/split_timing_forest_<case>.json is written:
   forest   R = 1, 16, 256, 4096 roots: a regular grid of the case's root box (2^k cells, the halvings dealt to the coordinates in turn);
            per root the literal y_0 - y_last <= s_r + 0.1 (c0_r - s_r), s_r the largest of 256 sampled values in the root, c0_r its
@@ -346,8 +351,82 @@ def split_row(net, lo, hi):
     return row
 
 
+def _spread(call, runs=7, warm=2):
+    """call() -> (..., kernel ms): median, min and max of the kernel time and the median wall-clock over `runs` calls after `warm`"""
+    ker, wall = [], []
+    for i in range(runs + warm):
+        t = time.perf_counter()
+        *_, ms = call()
+        if i >= warm:
+            ker.append(ms); wall.append(1e3 * (time.perf_counter() - t))
+    return dict(kernel_ms_median=statistics.median(ker), kernel_ms_min=min(ker), kernel_ms_max=max(ker), call_ms_median=statistics.median(wall))
+
+
+def relu_bound_rows(net, lo, hi):
+    """bound_nodes at 1, 256 and 4096 nodes (sub-boxes of the root, 20 % of the neurons forced to the pattern of a seeded point) with 0 and
+    16 multiplier steps, beside CrownBounder.bound on the same boxes in the same process; one literal y_0 - y_last"""
+    import relu_split_common as rs
+    ny = net.xdims[-1]
+    Cm = np.zeros((1, ny)); Cm[0, 0] = 1.0; Cm[0, ny - 1] -= 1.0
+    rows = []
+    with na.CrownBounder(net, Cm) as bd:
+        for n in (1, 256, 4096):
+            blo, bhi = sub_boxes(lo, hi, n)
+            rng = np.random.default_rng(n)
+            asg = np.stack([rs.node_from_point(net, blo[:, b], bhi[:, b], rng, 0.2)[1] for b in range(n)], 1)
+            row = dict(nnode=n, bound=_spread(lambda: bd.bound(blo, bhi, return_ms=True)))
+            for T in (0, 16):
+                row[f"bound_nodes_steps{T}"] = _spread(lambda: bd.bound_nodes(blo, bhi, asg, steps=T, return_ms=True))
+                row[f"kernel_over_bound_steps{T}"] = row[f"bound_nodes_steps{T}"]["kernel_ms_median"] / row["bound"]["kernel_ms_median"]
+            rows.append(row)
+            print(row, flush=True)
+    return rows
+
+
+def relu_search_rows():
+    """whole searches: verifyReluSplit (crown_backend "resident", 16 steps) against verifySplit (crown_backend "resident", literal_bounds,
+    centre points, bounds only) on the literal y_0 - y_1 <= h over [-0.5, 0.5]^n0 of two seeded nets; L is the largest of 4096 sampled
+    values and the centre's, c0 the literal's plain bound on the root; 5 runs each after 1 warm run"""
+    import literal_common as lc
+    rows = []
+    for xdims, seed, f, cap in (([16, 16, 16, 2], 7, 0.5, 16384), ([12, 16, 16, 2], 5, 0.2, 16384)):
+        net = lc.random_net(xdims, seed)
+        n0 = xdims[0]
+        lo, hi, nrm = -0.5 * np.ones(n0), 0.5 * np.ones(n0), np.array([1.0, -1.0])
+        X = np.concatenate([np.zeros((n0, 1)), lo[:, None] + np.random.default_rng(0).random((n0, 4096))], axis=1)
+        L = float((nrm @ na.evalFeedFwdNet(net, X)).max())
+        c0 = float(na.makeIntervalsBatch(net, lo[:, None], hi[:, None], backend="host", normals=nrm[None, :])[-1].smax[0, 0])
+        h = L + f * (c0 - L)
+        row = dict(xdims=xdims, seed=seed, L=L, c0=c0, h=h)
+        for label, run in (("relu_split", lambda: na.verifyReluSplit(net, lo, hi, [(nrm, h)], na.ReluSplitOptions(max_nodes=cap, crown_backend="resident"))),
+                           ("input_split", lambda: na.verifySplit(net, lo, hi, [(nrm, h)], 0, na.AdmmSdpOptions(),
+                                                                  na.SplitOptions(sdp_per_level=0, max_boxes=cap, max_depth=64, crown_backend="resident",
+                                                                                  literal_bounds=True)))):
+            ms, res = [], None
+            for i in range(6):
+                t = time.perf_counter()
+                res = run()
+                if i >= 1:
+                    ms.append(1e3 * (time.perf_counter() - t))
+            row[label] = dict(verdict=res.verdict, visited=int(res.visited), ms_median=statistics.median(ms), ms_min=min(ms), ms_max=max(ms))
+        rows.append(row)
+        print(row, flush=True)
+    return rows
+
+
 if __name__ == "__main__":
     args = sys.argv[1:]
+    if "--relu" in args:
+        # the ReLU-split leg: profiles/split_timing_relu.json; cases W10-D5 and W40-D20 unless named
+        out_dir = os.environ.get("SPLIT_TIMING_OUT", os.path.join(ROOT, "profiles"))
+        os.makedirs(out_dir, exist_ok=True)
+        names = [a for a in args if not a.startswith("--")] or ["W10-D5", "W40-D20"]
+        res = dict(bound={name: relu_bound_rows(*case(name)) for name in names})
+        if "--no-search" not in args:
+            res["search"] = relu_search_rows()
+        with open(os.path.join(out_dir, "split_timing_relu.json"), "w") as fh:
+            json.dump(res, fh, indent=1)
+        sys.exit(0)
     lit_leg, res_leg, alpha_leg, frontier_leg, reach_leg, wide_leg = ("--nlit" in args, "--resident" in args, "--alpha" in args, "--frontier" in args,
                                                                       "--reach" in args, "--wide" in args)
     forest_leg = "--forest" in args
