@@ -270,8 +270,8 @@ def check_toy(run, host):
 
 def check_lp_truth(run, host):
     """test 7: fully forced nodes of 2-8-8-2 and 3-10-10-3 (row 0 of the fixture's literals, the root box), steps = 16:
-    smax >= the linprog maximum of the affine objective over box and sign half-spaces, minus tol.  The gaps are printed"""
-    from scipy.optimize import linprog
+    smax >= the maximum over the node from tests/node_truth.py (one LP over box and sign half-spaces), minus tol.  The gaps are printed"""
+    import node_truth as nt
     for name in xc.SMALL:
         st = xc.verdict_setting(name)
         net, lo, hi, Cm = st["net"], st["lo"], st["hi"], st["normal"][None, :]
@@ -280,16 +280,36 @@ def check_lp_truth(run, host):
         nb = run(net, np.repeat(lo[:, None], nn, 1), np.repeat(hi[:, None], nn, 1), s, Cm, 16)
         assert not nb.infeasible.any()
         for b in range(nn):
-            We, be, Zw, Zb = affine_of_pattern(net, s[:, b])
-            cw, cb = (Cm @ We)[0], float((Cm @ be)[0])
-            sg = s[:, b].astype(np.float64)
-            res = linprog(-cw, A_ub=-(sg[:, None] * Zw), b_ub=sg * Zb, bounds=list(zip(lo, hi)), method="highs")
-            assert res.status == 0, (name, b, res.message)
-            v = -res.fun + cb
+            top = nt.node_max(nt.node_regions(net.Ms, lo, hi, s[:, b]), Cm)
+            assert top.regions == 1, (name, b, top.regions)
+            v = float(top.v[0])
             # HiGHS stops at a primal feasibility of 1e-7: its vertex may lie that far outside the node
             tol = (xc.HOST_SLACK if host else 1e-6) * (1.0 + abs(v))
             print(f"{name} node {b}: LP {v:.9f}  smax {nb.smax[0, b]:.9f} (plain {nb.smax_plain[0, b]:.9f}, step {nb.best_step[0, b]})  gap {nb.smax[0, b] - v:.3e}")
             assert nb.smax[0, b] >= v - tol, (name, b)
+
+
+def r_tolerance(cs, b, T):
+    """what tests/test_crown_alpha_gpu.py allows a_smax against its yardstick: 8 r, r = max |R(float64) - R(long double)| / (1 + |v|)
+    of the compared arrays -> (R in long double, tolerance)"""
+    args = (cs["net"].Ms, cs["lo"][:, b], cs["hi"][:, b], cs["assign"][:, b], cs["C"], T)
+    r64, rld = R(*args, dt=np.float64), R(*args, dt=np.longdouble)
+    r = max(ca.rel_err(r64[k], rld[k]) for k in ("smax", "A", "b0"))
+    return rld, 8.0 * r
+
+
+def check_yardstick(cs, nb, T):
+    """smax, uA, ub0 within 8 r of R(long double), best_step equal; branch equal wherever the two best scores differ by more than that;
+    the infeasible flag equal"""
+    for b in range(cs["lo"].shape[1]):
+        ref, tol = r_tolerance(cs, b, T)
+        errs = [ca.rel_err(got, ref[k]) for got, k in ((nb.smax[:, b], "smax"), (nb.A[:, :, b], "A"), (nb.b0[:, b], "b0"))]
+        print(f"{cs['net'].xdims} node {b} T {T}: err {max(errs):.3e}  tol {tol:.3e}  steps gpu {nb.best_step[:, b].tolist()} R {ref['best_step'].tolist()}")
+        assert max(errs) <= tol, (b, errs, tol)
+        assert np.array_equal(nb.best_step[:, b], ref["best_step"]), b
+        clear = np.asarray(ref["gap"], dtype=np.float64) > tol * (1.0 + np.abs(np.asarray(ref["smax_plain"], dtype=np.float64)))
+        assert np.array_equal(nb.branch[clear, b], ref["branch"][clear]), b
+        assert bool(nb.infeasible[b]) == ref["infeasible"]
 
 
 # ---- the driver

@@ -54,30 +54,12 @@ def test_forced_infeasibility():
     rs.check_forced_infeasible(gpu)
 
 
-def _r_tolerance(cs, b, T):
-    """what tests/test_crown_alpha_gpu.py allows a_smax against its yardstick: 8 r, r = max |R(float64) - R(long double)| / (1 + |v|)
-    of the compared arrays -> (R in long double, tolerance)"""
-    args = (cs["net"].Ms, cs["lo"][:, b], cs["hi"][:, b], cs["assign"][:, b], cs["C"], T)
-    r64, rld = rs.R(*args, dt=np.float64), rs.R(*args, dt=np.longdouble)
-    r = max(ca.rel_err(r64[k], rld[k]) for k in ("smax", "A", "b0"))
-    return rld, 8.0 * r
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("T", rs.STEPS)
 @pytest.mark.parametrize("n", range(len(rs.NETS)))
 def test_against_the_yardstick(n, T):
     """smax, uA, ub0 within 8 r of R(long double), best_step equal; branch equal wherever the two best scores differ by more than that"""
-    cs, nb = rs.kernel_cases()[n], case(n, T)
-    for b in range(cs["lo"].shape[1]):
-        ref, tol = _r_tolerance(cs, b, T)
-        errs = [ca.rel_err(got, ref[k]) for got, k in ((nb.smax[:, b], "smax"), (nb.A[:, :, b], "A"), (nb.b0[:, b], "b0"))]
-        print(f"{cs['net'].xdims} node {b} T {T}: err {max(errs):.3e}  tol {tol:.3e}  steps gpu {nb.best_step[:, b].tolist()} R {ref['best_step'].tolist()}")
-        assert max(errs) <= tol, (b, errs, tol)
-        assert np.array_equal(nb.best_step[:, b], ref["best_step"]), b
-        clear = np.asarray(ref["gap"], dtype=np.float64) > tol * (1.0 + np.abs(np.asarray(ref["smax_plain"], dtype=np.float64)))
-        assert np.array_equal(nb.branch[clear, b], ref["branch"][clear]), b
-        assert bool(nb.infeasible[b]) == ref["infeasible"]
+    rs.check_yardstick(rs.kernel_cases()[n], case(n, T), T)
 
 
 @pytest.mark.gpu
@@ -89,7 +71,7 @@ def test_more_literals_than_one_tile(n, nlit):
     cs["C"] = lc.literal_rows(cs["net"].xdims[-1], nlit, 700 + n)
     nb = gpu(cs["net"], cs["lo"], cs["hi"], cs["assign"], cs["C"], 3)
     for b in range(cs["lo"].shape[1]):
-        ref, tol = _r_tolerance(cs, b, 3)
+        ref, tol = rs.r_tolerance(cs, b, 3)
         errs = [ca.rel_err(got, ref[k]) for got, k in ((nb.smax[:, b], "smax"), (nb.A[:, :, b], "A"), (nb.b0[:, b], "b0"))]
         assert max(errs) <= tol and np.array_equal(nb.best_step[:, b], ref["best_step"]), (b, errs, tol)
     for i in (0, 16, nlit - 1):
