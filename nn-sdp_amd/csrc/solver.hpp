@@ -1236,7 +1236,9 @@ struct nnsdp_solver {
   void iterate(int n, double* eig_ms, bool sync = true) {
     if (n <= 0) return;
     if (eig_ms) {
-      while ((int)ev.size() < 2 * n) { hipEvent_t e; HIPCHK(hipEventCreate(&e)); ev.push_back(e); }
+      // (the events only measure time: without the system-scope release / acquire of a default event - a cache write-back and
+      // invalidation in front of the loads of the projection and of the gather behind it)
+      while ((int)ev.size() < 2 * n) { hipEvent_t e; HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableSystemFence)); ev.push_back(e); }
       for (int i = 0; i < n; ++i) { enqueue_iteration(false, next_is_warm(), ev[2 * i], ev[2 * i + 1]); ++iters_done; }
       HIPCHK(hipStreamSynchronize(st));
       double tot = 0;
