@@ -417,7 +417,7 @@ static int make_intervals_impl(int32_t K, const int32_t* xdims, const double* M,
   if (ar) {
     if (activ != NNSDP_ACTIV_RELU) throw std::invalid_argument("optimised slopes (alpha) are for ReLU networks, not Tanh");
     if (nlit < 1) throw std::invalid_argument("optimised slopes (alpha) need literals: nlit must be in 1..64");
-    check_alpha_options(ar->steps, ar->eta0, ar->decay);
+    check_pg_options("alpha", ar->steps, ar->eta0, ar->decay);
   }
   nnsdp::LitHead head;
   if (nlit != 0) {
@@ -667,7 +667,7 @@ int nnsdp_make_intervals_nodes(int32_t K, const int32_t* xdims, const double* M,
                                double eta0, double decay, double* pre_lo, double* pre_hi, double* smin, double* smax_plain,
                                double* smax, double* uA, double* ub0, int32_t* best_step, int32_t* branch, int32_t* infeasible) {
   API_BEGIN
-  check_node_options(steps, eta0, decay);
+  check_pg_options("nodes", steps, eta0, decay);
   if (activ != NNSDP_ACTIV_RELU && activ != NNSDP_ACTIV_TANH) throw std::invalid_argument("unknown activation");
   if (activ != NNSDP_ACTIV_RELU) throw std::invalid_argument("a ReLU split is for ReLU networks, not Tanh");
   if (nlit < 1 || nlit > nnsdp::kCbW) throw std::invalid_argument("a ReLU split needs literals: nlit must be in 1..64, got " + std::to_string(nlit));

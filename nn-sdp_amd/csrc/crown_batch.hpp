@@ -109,7 +109,8 @@ inline void check_boxes(long long nbox, int n0, const double* lo, const double* 
 
 // The kernel's outputs for nbox boxes, packed so that one copy brings everything back: ten segments in the order
 //   acymin | acymax | acxmin | acxmax | ymin | ymax | smin | smax | ub0 | uA
-// The alpha kernel (crown_alpha.hpp) appends  a_smax | a_ub0 | a_step | a_uA | alpha  and keeps three nst()-long state arrays.
+// The alpha kernel (crown_alpha.hpp) appends  a_smax | a_ub0 | a_step | a_uA | alpha  (CrownOptArgs::smax, ub0, step, uA of crown_opt.hpp,
+// then CrownAlphaArgs::alpha) and keeps three nst()-long state arrays.
 struct CrownLayout {
   size_t nbox, n0, acdim, ny, nlit;
   static constexpr int kSegs = 10;
@@ -205,6 +206,8 @@ __device__ inline void cb_tanh_relax(double l, double u, double& lw, double& lb,
 // relaxation is exact (+1: du = dl = 1, -1: du = dl = 0, bu = 0 in both), a pre-activation pass clips the bounds it writes to the forced
 // side and flags l > u, and the upper row of the literal pass records the free unstable neuron with the largest max(lambda, 0) bu
 // (ties: the lowest neuron index).  SPLIT = false compiles to what the function was without the parameter.
+// The ReLU relaxation stays inline here: cb_relu_relax (crown_opt.hpp, which includes this file) is the same arithmetic for the two
+// optimisers, and this function's instantiations keep the code they had (profiles/crown_opt_resources.txt).
 template <bool LIT, int ACT = kCbRelu, bool SPLIT = false>
 __device__ void crown_pass(const CrownArgs& a, double* lds, long long box, int k, int head_identity, CrownSplit* sp = nullptr) {
   static_assert(!SPLIT || ACT == kCbRelu, "a ReLU split is for ReLU networks");

@@ -12,23 +12,19 @@ static void check_literals(int32_t ny, int32_t nlit, const double* normals) {
         throw std::invalid_argument("literal " + std::to_string(i) + ": the normal has a non-finite entry (NaN or infinity)");
 }
 
-// the options of the alpha entries
-static void check_alpha_options(int32_t steps, double eta0, double decay) {
-  if (steps < 0 || steps > 64) throw std::invalid_argument("alpha: steps must be in 0..64, got " + std::to_string(steps));
-  if (!std::isfinite(eta0) || !(eta0 > 0.0)) throw std::invalid_argument("alpha: eta0 must be positive and finite");
-  if (!(decay > 0.0 && decay <= 1.0)) throw std::invalid_argument("alpha: decay must be in (0, 1]");
+// the options of the projected-gradient entries; prefix: "alpha" (the slope entries) or "nodes" (nnsdp_crown_bound_nodes,
+// nnsdp_make_intervals_nodes)
+static void check_pg_options(const std::string& prefix, int32_t steps, double eta0, double decay) {
+  if (steps < 0 || steps > 64) throw std::invalid_argument(prefix + ": steps must be in 0..64, got " + std::to_string(steps));
+  if (!std::isfinite(eta0) || !(eta0 > 0.0)) throw std::invalid_argument(prefix + ": eta0 must be positive and finite");
+  if (!(decay > 0.0 && decay <= 1.0)) throw std::invalid_argument(prefix + ": decay must be in (0, 1]");
 }
 static void check_alpha0(const double* alpha0, size_t count) {
   for (size_t k = 0; k < count; ++k)
     if (!std::isfinite(alpha0[k])) throw std::invalid_argument("alpha0 has a non-finite entry (NaN or infinity) at index " + std::to_string(k));
 }
 
-// the options and the assignments of the node entries (nnsdp_crown_bound_nodes, nnsdp_make_intervals_nodes)
-static void check_node_options(int32_t steps, double eta0, double decay) {
-  if (steps < 0 || steps > 64) throw std::invalid_argument("nodes: steps must be in 0..64, got " + std::to_string(steps));
-  if (!std::isfinite(eta0) || !(eta0 > 0.0)) throw std::invalid_argument("nodes: eta0 must be positive and finite");
-  if (!(decay > 0.0 && decay <= 1.0)) throw std::invalid_argument("nodes: decay must be in (0, 1]");
-}
+// the assignments of the node entries
 static void check_assign(const int8_t* assign, size_t count) {
   for (size_t k = 0; k < count; ++k)
     if (assign[k] < -1 || assign[k] > 1)
@@ -175,7 +171,7 @@ struct nnsdp_crown {
     reserve_boxes(nbox);
     if (nbox <= alpha_cap) return;
     if (!alpha_cap)
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_crown_alpha), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kCaLdsBytes));
+      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_crown_alpha), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kCoLdsBytes));
     const size_t cap = std::max(nbox, 2 * alpha_cap);
     dalloc(dain, cap * ain_per_box()); dalloc(daout, cap * aout_per_box()); dalloc(dast, cap * ast_per_box());
     pinned(hain, cap * ain_per_box()); pinned(haout, cap * aout_per_box());
@@ -186,7 +182,7 @@ struct nnsdp_crown {
     if (nnode <= node_cap) return;
     if (!node_cap) {
       HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_crown_nodes), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kCbLdsBytesTanh));
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_crown_beta), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kCnLdsBytes));
+      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_crown_beta), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kCoLdsBytes));
     }
     const size_t cap = std::max(nnode, 2 * node_cap);
     const nnsdp::CrownNodeLayout L = node_layout(cap);
@@ -312,7 +308,7 @@ struct nnsdp_crown {
     if (wide()) throw std::invalid_argument("optimised slopes (alpha) are not available on a wide bounder (max_width 128): the alpha kernel keeps a 64-wide layout");
     if (activ != NNSDP_ACTIV_RELU) throw std::invalid_argument("optimised slopes (alpha) are for ReLU networks, not Tanh");
     if (nlit < 1) throw std::invalid_argument("optimised slopes (alpha) need literals: the handle was created without normals");
-    check_alpha_options(steps, eta0, decay);
+    check_pg_options("alpha", steps, eta0, decay);
     if (nbox < 0) throw std::invalid_argument("nbox must be >= 0");
     if (nbox == 0) return;
     if (!x1min || !x1max) throw std::invalid_argument("null argument");
@@ -328,13 +324,13 @@ struct nnsdp_crown {
     if (alpha0) std::copy(alpha0, alpha0 + nst_all, hain + 2 * nin);
     HIPCHK(hipMemcpyAsync(dain.p, hain, (2 * nin + (alpha0 ? nst_all : 0)) * sizeof(double), hipMemcpyHostToDevice, st));
     nnsdp::CrownAlphaArgs p;
-    p.c = bound_args(L, dain.p, dain.p + nin, daout.p);
-    p.steps = steps; p.eta0 = eta0; p.decay = decay; p.alpha0 = alpha0 ? dain.p + 2 * nin : nullptr;
-    p.cur = dast.p; p.lam = p.cur + nst_all; p.best = p.lam + nst_all;
-    p.a_smax = daout.p + L.total(); p.a_ub0 = p.a_smax + nl_all; p.a_step = p.a_ub0 + nl_all; p.a_uA = p.a_step + nl_all; p.alpha = p.a_uA + nA_all;
+    p.o.c = bound_args(L, dain.p, dain.p + nin, daout.p);
+    p.o.steps = steps; p.o.eta0 = eta0; p.o.decay = decay; p.alpha0 = alpha0 ? dain.p + 2 * nin : nullptr;
+    p.o.cur = dast.p; p.o.lam = p.o.cur + nst_all; p.best = p.o.lam + nst_all;
+    p.o.smax = daout.p + L.total(); p.o.ub0 = p.o.smax + nl_all; p.o.step = p.o.ub0 + nl_all; p.o.uA = p.o.step + nl_all; p.alpha = p.o.uA + nA_all;
     HIPCHK(hipEventRecord(e0, st));
-    launch_bound(p.c, L.nbox);
-    hipLaunchKernelGGL(nnsdp::k_crown_alpha, dim3((unsigned)nbox), dim3(256), nnsdp::kCaLdsBytes, st, p);
+    launch_bound(p.o.c, L.nbox);
+    hipLaunchKernelGGL(nnsdp::k_crown_alpha, dim3((unsigned)nbox), dim3(256), nnsdp::kCoLdsBytes, st, p);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(e1, st));
     HIPCHK(hipMemcpyAsync(haout, daout.p, L.alpha_total() * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -365,7 +361,7 @@ struct nnsdp_crown {
   };
   static void bound_nodes(nnsdp_crown* h, int32_t nnode, const double* x1min, const double* x1max, const int8_t* assign, int32_t steps,
                           double eta0, double decay, const NodeOut& out) {
-    check_node_options(steps, eta0, decay);
+    check_pg_options("nodes", steps, eta0, decay);
     if (!h) throw std::invalid_argument("null handle");
     if (h->wide()) throw std::invalid_argument("a ReLU split is not available on a wide bounder (max_width 128): the node kernels keep a 64-wide layout");
     if (h->activ != NNSDP_ACTIV_RELU) throw std::invalid_argument("a ReLU split is for ReLU networks, not Tanh");
@@ -387,16 +383,16 @@ struct nnsdp_crown {
     hipStream_t st = h->st;
     HIPCHK(hipMemcpyAsync(h->dnin.p, h->hnin, 2 * nin * sizeof(double) + L.nnode * acdim, hipMemcpyHostToDevice, st));
     nnsdp::CrownNodeArgs p;
-    p.c.K = h->K; p.c.xdims = h->dxd.p; p.c.moff = h->dmo.p; p.c.acoff = h->dao.p; p.c.M = h->dM.p; p.c.H = h->dM.p + h->moff[h->K];
-    p.c.lo = h->dnin.p; p.c.hi = h->dnin.p + nin;
+    p.o.c.K = h->K; p.o.c.xdims = h->dxd.p; p.o.c.moff = h->dmo.p; p.o.c.acoff = h->dao.p; p.o.c.M = h->dM.p; p.o.c.H = h->dM.p + h->moff[h->K];
+    p.o.c.lo = h->dnin.p; p.o.c.hi = h->dnin.p + nin;
     p.sp.assign = reinterpret_cast<const int8_t*>(h->dnin.p + 2 * nin); p.sp.infeasible = 0;
     L.point(p, h->dnout.p);
-    p.steps = steps; p.eta0 = eta0; p.decay = decay;
-    p.cur = h->dnst.p; p.lam = p.cur + L.nst();
+    p.o.steps = steps; p.o.eta0 = eta0; p.o.decay = decay;
+    p.o.cur = h->dnst.p; p.o.lam = p.o.cur + L.nst();
     HIPCHK(hipEventRecord(h->e0, st));
     hipLaunchKernelGGL(nnsdp::k_crown_nodes, dim3((unsigned)nnode), dim3(256), nnsdp::kCbLdsBytesTanh, st, p);
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(nnsdp::k_crown_beta, dim3((unsigned)nnode), dim3(256), nnsdp::kCnLdsBytes, st, p);
+    hipLaunchKernelGGL(nnsdp::k_crown_beta, dim3((unsigned)nnode), dim3(256), nnsdp::kCoLdsBytes, st, p);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(h->e1, st));
     HIPCHK(hipMemcpyAsync(h->hnout, h->dnout.p, L.total() * sizeof(double), hipMemcpyDeviceToHost, st));

@@ -113,6 +113,14 @@ inline void tanh_relax(float l, float u, float& lw, float& lb, float& uw, float&
   if (l < -500.0f) { uw = 0.0f; ub = yu; }
 }
 
+// the ReLU relaxation from raw pre-activation bounds (the rules at the top of this file)
+inline void relu_relax_f(float l, float u, float& du, float& dl, float& bu) {
+  const float lr = std::min(l, 0.0f), ur = std::max(std::max(u, 0.0f), lr + 1e-8f);
+  du = ur / (ur - lr);
+  dl = du > 0.5f ? 1.0f : 0.0f;
+  bu = -lr * du;
+}
+
 // backward bound of  Ws[L-1] act(... act(Ws[0] x + bs[0]) ...) + bs[L-1]  over the box [lo, hi] (act = relu, or tanh when tanh_act);
 // pre[j] = pre-activation bounds of layer j (j < L-1).  The head is Ws[L-1] / bs[L-1], whatever it is (a layer of the network, an
 // identity, a literal head); out_uA / out_ub (optional) receive the upper bound's linear form  uA x + ub  on the box.
@@ -130,11 +138,7 @@ inline void crown_backward(const std::vector<const DenseF*>& Ws, const std::vect
     std::vector<float> du(d), dl(d), bu(d), bl(d, 0.0f);
     for (int t = 0; t < d; ++t) {
       if (tanh_act) { tanh_relax(prel[j][t], preu[j][t], dl[t], bl[t], du[t], bu[t]); continue; }
-      float lr = std::min(prel[j][t], 0.0f);
-      float ur = std::max(std::max(preu[j][t], 0.0f), lr + 1e-8f);
-      du[t] = ur / (ur - lr);
-      dl[t] = du[t] > 0.5f ? 1.0f : 0.0f;
-      bu[t] = -lr * du[t];
+      relu_relax_f(prel[j][t], preu[j][t], du[t], dl[t], bu[t]);
     }
     for (int i = 0; i < nout; ++i) {
       float sl = 0.0f, su = 0.0f;
@@ -267,9 +271,126 @@ inline IntervalsOut make_intervals(int K, const int32_t* xdims, const double* M,
   return out;
 }
 
-// ---- optimised ReLU slopes for the literal pass (alpha-CROWN): per literal, projected-gradient steps on the
-// lower slope alpha in [0, 1] of every unstable neuron (l < 0 < u) of the upper bound's backward pass.  float32 like the passes above;
-// iterate 0 without alpha0 is crown_backward's upper matrix operation for operation.  The hidden layers' bounds stay plain CROWN.
+// ---- the two projected-gradient optimisers of the literal pass's upper bound, the float32 twins of the kernels
+// around crown_pg_body (crown_opt.hpp): lits_alpha on the lower slopes of the unstable neurons, make_intervals_nodes on the multipliers of
+// a node's forced neurons.  Both fill a PgContext and run pg_literal per literal.
+
+// What a backward row and the loop of a literal read: the hidden layers of (K, xdims, M) in float32 (W[k] row-major, bs[k]; aoff[k]:
+// where layer k's neurons start, aoff[K - 1] = acdim), the box as centre and radius, the relaxation du, dl, bu of every hidden neuron
+// (filled by the caller) and the step sizes
+struct PgContext {
+  int K;
+  const int32_t* xdims;
+  std::vector<DenseF> W;
+  std::vector<std::vector<float>> bs;
+  std::vector<int> aoff;
+  std::vector<float> c0, r0, du, dl, bu;
+  int steps;
+  double eta0, decay;
+  PgContext(int K_, const int32_t* xdims_, const double* M, const double* x1min, const double* x1max, int steps_, double eta0_, double decay_)
+      : K(K_), xdims(xdims_), W(K_ - 1), bs(K_ - 1), aoff(K_, 0), c0(xdims_[0]), r0(xdims_[0]), steps(steps_), eta0(eta0_), decay(decay_) {
+    size_t off = 0;
+    for (int k = 0; k + 1 < K; ++k) {
+      const int r = xdims[k + 1], c = xdims[k];
+      W[k] = DenseF(r, c); bs[k].resize(r);
+      for (int j = 0; j < c; ++j)
+        for (int i = 0; i < r; ++i) W[k].at(i, j) = (float)M[off + (size_t)j * r + i];
+      for (int i = 0; i < r; ++i) bs[k][i] = (float)M[off + (size_t)c * r + i];
+      off += (size_t)r * (c + 1);
+      aoff[k + 1] = aoff[k] + r;
+    }
+    for (int q = 0; q < xdims[0]; ++q) {
+      const float lo = (float)x1min[q], hi = (float)x1max[q];
+      c0[q] = (hi + lo) / 2.0f; r0[q] = (hi - lo) / 2.0f;
+    }
+    du.resize(acdim()); dl.resize(acdim()); bu.resize(acdim());
+  }
+  int acdim() const { return aoff.back(); }
+};
+
+// One row of a backward pass from layer `top` (its coefficients in `row`, its constant in `cst`) down to the input, concretised over the
+// box: the upper bound (else the lower).  entry(n, b, sb) returns the coefficient b of neuron n behind the row scaling and adds its bias
+// term to sb.  `row` ends as the input row; nxt is working space.
+template <class Entry>
+inline float backward_row(const PgContext& c, int top, bool upper, std::vector<float>& row, float& cst, std::vector<float>& nxt, Entry entry) {
+  for (int j = top; j >= 0; --j) {
+    const int d = c.xdims[j + 1], in = c.xdims[j], o = c.aoff[j];
+    float sb = 0.0f;
+    for (int t = 0; t < d; ++t) row[t] = entry(o + t, row[t], sb);
+    cst += sb;
+    float tl = 0.0f;
+    for (int t = 0; t < d; ++t) tl += row[t] * c.bs[j][t];
+    cst += tl;
+    nxt.assign(in, 0.0f);
+    for (int t = 0; t < d; ++t) {
+      const float b = row[t];
+      if (b == 0.0f) continue;
+      const float* w = &c.W[j].a[(size_t)t * in];
+      for (int q = 0; q < in; ++q) nxt[q] += b * w[q];
+    }
+    row.swap(nxt);
+  }
+  float sc = 0.0f, rr = 0.0f;
+  for (int q = 0; q < c.xdims[0]; ++q) { sc += row[q] * c.c0[q]; rr += std::fabs(row[q]) * c.r0[q]; }
+  return upper ? sc + rr + cst : sc - rr + cst;
+}
+
+// the head row of literal i
+inline void head_row(const LitHead& head, int i, std::vector<float>& row, float& cst) {
+  row.assign(head.d, 0.0f);
+  for (int t = 0; t < head.d; ++t) row[t] = (float)head.H[(size_t)t * head.nlit + i];
+  cst = (float)head.H[(size_t)head.d * head.nlit + i];
+}
+
+// The projected-gradient loop of literal i on `state` (acdim values, set to the first iterate by the caller): per iterate the upper
+// backward pass (entry as in backward_row; it leaves the coefficient that enters neuron n in lam[n]), keep the first smallest smax with
+// its uA and ub0 in `out`, the maximiser x* = c + sgn(uA) r, the forward pass of the relaxed network that the backward pass chose
+// (lambda > 0: du z + bu, else lower_slope(n) z) with the gradient g[n] = grad(n, lambda, z) and max|g|, the stationary break, and
+// state <- project(state - eta g / max|g|), eta <- eta decay.  iterate(s, smax, better) sees every iterate behind its backward pass.
+template <class Out, class Entry, class Grad, class Slope, class Project, class Iterate>
+inline void pg_literal(const PgContext& c, const LitHead& head, int i, std::vector<float>& state, const std::vector<float>& lam, Out& out,
+                       Entry entry, Grad grad, Slope lower_slope, Project project, Iterate iterate) {
+  const int n0 = c.xdims[0], acdim = c.acdim();
+  std::vector<float> g(acdim), row, nxt, z;
+  float best = 0.0f, eta = (float)c.eta0;
+  for (int s = 0; s <= c.steps; ++s) {
+    float cst;
+    head_row(head, i, row, cst);
+    const float smax = backward_row(c, c.K - 2, true, row, cst, nxt, entry);
+    const bool better = s == 0 || smax < best;
+    if (better) {
+      best = smax;
+      out.smax[i] = smax; out.ub0[i] = cst; out.best_step[i] = s;
+      for (int q = 0; q < n0; ++q) out.uA[(size_t)i * n0 + q] = row[q];
+    }
+    iterate(s, smax, better);
+    if (s == c.steps) break;
+    z.assign(n0, 0.0f);
+    for (int q = 0; q < n0; ++q) z[q] = c.c0[q] + (row[q] > 0.0f ? c.r0[q] : row[q] < 0.0f ? -c.r0[q] : 0.0f);
+    float gmax = 0.0f;
+    for (int j = 0; j + 1 < c.K; ++j) {
+      const int d = c.xdims[j + 1], in = c.xdims[j], o = c.aoff[j];
+      nxt.assign(d, 0.0f);
+      for (int t = 0; t < d; ++t) {
+        float v = 0.0f;
+        for (int q = 0; q < in; ++q) v += c.W[j].at(t, q) * z[q];
+        v += c.bs[j][t];
+        const float lm = lam[o + t];
+        g[o + t] = grad(o + t, lm, v);
+        gmax = std::max(gmax, std::fabs(g[o + t]));
+        nxt[t] = lm > 0.0f ? c.du[o + t] * v + c.bu[o + t] : lower_slope(o + t) * v;
+      }
+      z.swap(nxt);
+    }
+    if (!(gmax > 0.0f)) break;          // stationary
+    for (int n = 0; n < acdim; ++n) state[n] = project(state[n] - eta * g[n] / gmax);
+    eta *= (float)c.decay;
+  }
+}
+
+// ---- optimised ReLU slopes (alpha-CROWN): per literal, projected-gradient steps on the lower slope alpha in [0, 1] of every unstable
+// neuron (l < 0 < u).  Iterate 0 without alpha0 is crown_backward's upper matrix operation for operation.  The hidden layers' bounds
+// stay plain CROWN.
 struct AlphaOut {
   std::vector<double> smax, uA, ub0, alpha;      // nlit, nlit x n0 (row-major), nlit, nlit x acdim (row-major)
   std::vector<int32_t> best_step;                // nlit
@@ -279,113 +400,44 @@ inline AlphaOut lits_alpha(int K, const int32_t* xdims, const double* M, const L
                            const std::vector<std::vector<float>>& preu, const double* x1min, const double* x1max, int steps, double eta0,
                            double decay, const double* alpha0) {
   const int nlit = head.nlit, n0 = xdims[0];
-  std::vector<DenseF> W(K - 1);
-  std::vector<std::vector<float>> bs(K - 1);
-  std::vector<int> aoff(K, 0);
-  size_t off = 0;
-  for (int k = 0; k + 1 < K; ++k) {
-    const int r = xdims[k + 1], c = xdims[k];
-    W[k] = DenseF(r, c); bs[k].resize(r);
-    for (int j = 0; j < c; ++j)
-      for (int i = 0; i < r; ++i) W[k].at(i, j) = (float)M[off + (size_t)j * r + i];
-    for (int i = 0; i < r; ++i) bs[k][i] = (float)M[off + (size_t)c * r + i];
-    off += (size_t)r * (c + 1);
-    aoff[k + 1] = aoff[k] + r;
-  }
-  const int acdim = aoff[K - 1];
-  std::vector<float> du(acdim), dl(acdim), bu(acdim), c0(n0), r0(n0);
+  PgContext c(K, xdims, M, x1min, x1max, steps, eta0, decay);
+  const int acdim = c.acdim();
   std::vector<char> uns(acdim);
   for (int j = 0; j + 1 < K; ++j)
     for (int t = 0; t < xdims[j + 1]; ++t) {
-      const int n = aoff[j] + t;
-      const float lr = std::min(prel[j][t], 0.0f), ur = std::max(std::max(preu[j][t], 0.0f), lr + 1e-8f);
-      du[n] = ur / (ur - lr);
-      dl[n] = du[n] > 0.5f ? 1.0f : 0.0f;
-      bu[n] = -lr * du[n];
+      const int n = c.aoff[j] + t;
+      relu_relax_f(prel[j][t], preu[j][t], c.du[n], c.dl[n], c.bu[n]);
       uns[n] = prel[j][t] < 0.0f && preu[j][t] > 0.0f;
     }
-  for (int q = 0; q < n0; ++q) {
-    const float lo = (float)x1min[q], hi = (float)x1max[q];
-    c0[q] = (hi + lo) / 2.0f; r0[q] = (hi - lo) / 2.0f;
-  }
   AlphaOut out;
   out.smax.assign(nlit, 0.0); out.uA.assign((size_t)nlit * n0, 0.0); out.ub0.assign(nlit, 0.0);
   out.alpha.assign((size_t)nlit * acdim, 0.0); out.best_step.assign(nlit, 0);
-  const int dtop = xdims[K - 1];
-  std::vector<float> al(acdim), lam(acdim), g(acdim), row, nxt, z;
+  std::vector<float> al(acdim), lam(acdim);
   for (int i = 0; i < nlit; ++i) {
     for (int n = 0; n < acdim; ++n) {
-      al[n] = dl[n];
+      al[n] = c.dl[n];
       if (alpha0 && uns[n]) al[n] = (float)std::min(std::max(alpha0[(size_t)i * acdim + n], 0.0), 1.0);
     }
-    float best = 0.0f, eta = (float)eta0;
-    for (int s = 0; s <= steps; ++s) {
-      // backward pass of row i at al (crown_backward's upper matrix)
-      row.assign(dtop, 0.0f);
-      for (int t = 0; t < dtop; ++t) row[t] = (float)head.H[(size_t)t * nlit + i];
-      float ub = (float)head.H[(size_t)dtop * nlit + i];
-      for (int j = K - 2; j >= 0; --j) {
-        const int d = xdims[j + 1], in = xdims[j], o = aoff[j];
-        float su = 0.0f;
-        for (int t = 0; t < d; ++t) {
-          const float b = row[t];
-          lam[o + t] = b;
-          su += std::max(b, 0.0f) * bu[o + t] + std::min(b, 0.0f) * 0.0f;
-          row[t] = std::max(b, 0.0f) * du[o + t] + std::min(b, 0.0f) * al[o + t];
-        }
-        ub += su;
-        float tu = 0.0f;
-        for (int t = 0; t < d; ++t) tu += row[t] * bs[j][t];
-        ub += tu;
-        nxt.assign(in, 0.0f);
-        for (int t = 0; t < d; ++t) {
-          const float b = row[t];
-          if (b == 0.0f) continue;
-          const float* w = &W[j].a[(size_t)t * in];
-          for (int q = 0; q < in; ++q) nxt[q] += b * w[q];
-        }
-        row.swap(nxt);
-      }
-      float su = 0.0f, ru = 0.0f;
-      for (int q = 0; q < n0; ++q) { su += row[q] * c0[q]; ru += std::fabs(row[q]) * r0[q]; }
-      const float smax = su + ru + ub;
-      if (s == 0 || smax < best) {
-        best = smax;
-        out.smax[i] = smax; out.ub0[i] = ub; out.best_step[i] = s;
-        for (int q = 0; q < n0; ++q) out.uA[(size_t)i * n0 + q] = row[q];
-        for (int n = 0; n < acdim; ++n) out.alpha[(size_t)i * acdim + n] = al[n];
-      }
-      if (s == steps) break;
-      // gradient: the relaxed network the pass chose, at the maximiser x* = c + sgn(uA) r
-      z.assign(n0, 0.0f);
-      for (int q = 0; q < n0; ++q) z[q] = c0[q] + (row[q] > 0.0f ? r0[q] : row[q] < 0.0f ? -r0[q] : 0.0f);
-      float gmax = 0.0f;
-      for (int j = 0; j + 1 < K; ++j) {
-        const int d = xdims[j + 1], in = xdims[j], o = aoff[j];
-        nxt.assign(d, 0.0f);
-        for (int t = 0; t < d; ++t) {
-          float v = 0.0f;
-          for (int q = 0; q < in; ++q) v += W[j].at(t, q) * z[q];
-          v += bs[j][t];
-          const float lm = lam[o + t];
-          g[o + t] = uns[o + t] ? std::min(lm, 0.0f) * v : 0.0f;
-          gmax = std::max(gmax, std::fabs(g[o + t]));
-          nxt[t] = lm > 0.0f ? du[o + t] * v + bu[o + t] : al[o + t] * v;
-        }
-        z.swap(nxt);
-      }
-      if (!(gmax > 0.0f)) break;          // stationary
-      for (int n = 0; n < acdim; ++n) al[n] = std::min(std::max(al[n] - eta * g[n] / gmax, 0.0f), 1.0f);
-      eta *= (float)decay;
-    }
+    pg_literal(c, head, i, al, lam, out,
+               [&](int n, float b, float& su) {
+                 lam[n] = b;
+                 su += std::max(b, 0.0f) * c.bu[n] + std::min(b, 0.0f) * 0.0f;
+                 return std::max(b, 0.0f) * c.du[n] + std::min(b, 0.0f) * al[n];
+               },
+               [&](int n, float lm, float v) { return uns[n] ? std::min(lm, 0.0f) * v : 0.0f; },
+               [&](int n) { return al[n]; },
+               [](float x) { return std::min(std::max(x, 0.0f), 1.0f); },
+               [&](int, float, bool better) {
+                 if (better) for (int n = 0; n < acdim; ++n) out.alpha[(size_t)i * acdim + n] = al[n];
+               });
   }
   return out;
 }
 
 // ---- bounds on a node of a ReLU split ("Branching on unstable ReLUs"; the kernels are in crown_relu_split.hpp): the
-// box and an assignment s in {-1, 0, +1}^acdim (+1: z_n >= 0, -1: z_n <= 0, 0: free).  float32 like the passes above.  A forced neuron's
-// relaxation is exact, the pre-activation bounds are clipped to the forced side (l > u afterwards: the node is infeasible), and per
-// literal `steps` projected-gradient steps on one multiplier beta_n >= 0 per forced neuron tighten the upper bound.
+// box and an assignment s in {-1, 0, +1}^acdim (+1: z_n >= 0, -1: z_n <= 0, 0: free).  A forced neuron's relaxation is exact, the
+// pre-activation bounds are clipped to the forced side (l > u afterwards: the node is infeasible), and per literal `steps`
+// projected-gradient steps on one multiplier beta_n >= 0 per forced neuron tighten the upper bound.
 struct NodeOut {
   std::vector<double> pre_lo, pre_hi;            // acdim, clipped
   std::vector<double> smin, smax_plain, smax, uA, ub0;      // nlit; uA nlit x n0 (row-major); smax / uA / ub0 of the best iterate
@@ -395,76 +447,32 @@ struct NodeOut {
 inline NodeOut make_intervals_nodes(int K, const int32_t* xdims, const double* M, const LitHead& head, const double* x1min,
                                     const double* x1max, const int8_t* assign, int steps, double eta0, double decay) {
   const int nlit = head.nlit, n0 = xdims[0];
-  std::vector<DenseF> W(K - 1);
-  std::vector<std::vector<float>> bs(K - 1);
-  std::vector<int> aoff(K, 0);
-  size_t off = 0;
-  for (int k = 0; k + 1 < K; ++k) {
-    const int r = xdims[k + 1], c = xdims[k];
-    W[k] = DenseF(r, c); bs[k].resize(r);
-    for (int j = 0; j < c; ++j)
-      for (int i = 0; i < r; ++i) W[k].at(i, j) = (float)M[off + (size_t)j * r + i];
-    for (int i = 0; i < r; ++i) bs[k][i] = (float)M[off + (size_t)c * r + i];
-    off += (size_t)r * (c + 1);
-    aoff[k + 1] = aoff[k] + r;
-  }
-  const int acdim = aoff[K - 1];
-  std::vector<float> du(acdim), dl(acdim), bu(acdim), pl(acdim), pu(acdim), c0(n0), r0(n0);
+  PgContext c(K, xdims, M, x1min, x1max, steps, eta0, decay);
+  const int acdim = c.acdim();
+  std::vector<float> pl(acdim), pu(acdim);
   std::vector<char> cand(acdim);
-  for (int q = 0; q < n0; ++q) {
-    const float lo = (float)x1min[q], hi = (float)x1max[q];
-    c0[q] = (hi + lo) / 2.0f; r0[q] = (hi - lo) / 2.0f;
-  }
   NodeOut out;
-  // One row of a backward pass from layer `top` (its coefficients in `row`, its constant in `cst`) down to the input.  upper: the upper
-  // bound's pair (else the lower bound's).  beta (upper only): the multipliers, added behind the row scaling.  lam receives the
-  // coefficients that enter every neuron; br (upper only): the branching neuron.  Returns the concretised bound, `row` the input row.
-  std::vector<float> nxt;
-  auto backward = [&](std::vector<float>& row, float& cst, int top, bool upper, const float* beta, float* lam, int* br) {
-    float bscore = -1.0f;
-    for (int j = top; j >= 0; --j) {
-      const int d = xdims[j + 1], in = xdims[j], o = aoff[j];
-      float sb = 0.0f;
-      for (int t = 0; t < d; ++t) {
-        const float b = row[t], bp = std::max(b, 0.0f), bn = std::min(b, 0.0f);
-        if (lam) lam[o + t] = b;
-        sb += (upper ? bp : bn) * bu[o + t];
-        if (br && cand[o + t]) {
-          const float sc = bp * bu[o + t];
-          if (sc > bscore || (sc == bscore && o + t < *br)) { bscore = sc; *br = o + t; }
-        }
-        float y = upper ? bp * du[o + t] + bn * dl[o + t] : bp * dl[o + t] + bn * du[o + t];
-        if (beta && assign[o + t] != 0) y += (float)assign[o + t] * beta[o + t];
-        row[t] = y;
-      }
-      cst += sb;
-      float tl = 0.0f;
-      for (int t = 0; t < d; ++t) tl += row[t] * bs[j][t];
-      cst += tl;
-      nxt.assign(in, 0.0f);
-      for (int t = 0; t < d; ++t) {
-        const float b = row[t];
-        if (b == 0.0f) continue;
-        const float* w = &W[j].a[(size_t)t * in];
-        for (int q = 0; q < in; ++q) nxt[q] += b * w[q];
-      }
-      row.swap(nxt);
-    }
-    float sc = 0.0f, rr = 0.0f;
-    for (int q = 0; q < n0; ++q) { sc += row[q] * c0[q]; rr += std::fabs(row[q]) * r0[q]; }
-    return upper ? sc + rr + cst : sc - rr + cst;
+  // backward_row's entry.  upper: the upper bound's pair (else the lower bound's).  beta (upper only): the multipliers, added behind the
+  // row scaling.  lam receives the coefficients that enter every neuron.
+  auto entry = [&](bool upper, const float* beta, float* lam, int n, float b, float& sb) {
+    const float bp = std::max(b, 0.0f), bn = std::min(b, 0.0f);
+    if (lam) lam[n] = b;
+    sb += (upper ? bp : bn) * c.bu[n];
+    float y = upper ? bp * c.du[n] + bn * c.dl[n] : bp * c.dl[n] + bn * c.du[n];
+    if (beta && assign[n] != 0) y += (float)assign[n] * beta[n];
+    return y;
   };
+  auto plain = [&](bool upper) { return [&entry, upper](int n, float b, float& sb) { return entry(upper, nullptr, nullptr, n, b, sb); }; };
   // the pre-activation bounds, layer by layer, clipped; then the layer's relaxation
-  std::vector<float> row;
+  std::vector<float> row, nxt;
   for (int k = 0; k + 1 < K; ++k) {
-    const int d = xdims[k + 1], in = xdims[k], o = aoff[k];
+    const int d = xdims[k + 1], in = xdims[k], o = c.aoff[k];
     for (int t = 0; t < d; ++t) {
       float l = 0.0f, u = 0.0f;
       for (int side = 0; side < 2; ++side) {
-        row.assign(W[k].a.begin() + (size_t)t * in, W[k].a.begin() + (size_t)(t + 1) * in);
-        float cst = bs[k][t];
-        const float v = backward(row, cst, k - 1, side == 1, nullptr, nullptr, nullptr);
-        (side ? u : l) = v;
+        row.assign(c.W[k].a.begin() + (size_t)t * in, c.W[k].a.begin() + (size_t)(t + 1) * in);
+        float cst = c.bs[k][t];
+        (side ? u : l) = backward_row(c, k - 1, side == 1, row, cst, nxt, plain(side == 1));
       }
       const int sv = assign[o + t];
       if (sv > 0) l = std::max(l, 0.0f);
@@ -474,63 +482,35 @@ inline NodeOut make_intervals_nodes(int K, const int32_t* xdims, const double* M
     }
     for (int t = 0; t < d; ++t) {
       const int n = o + t, sv = assign[n];
-      const float lr = std::min(pl[n], 0.0f), ur = std::max(std::max(pu[n], 0.0f), lr + 1e-8f);
-      du[n] = ur / (ur - lr);
-      dl[n] = du[n] > 0.5f ? 1.0f : 0.0f;
-      bu[n] = -lr * du[n];
-      if (sv != 0) { du[n] = dl[n] = sv > 0 ? 1.0f : 0.0f; bu[n] = 0.0f; }
+      relu_relax_f(pl[n], pu[n], c.du[n], c.dl[n], c.bu[n]);
+      if (sv != 0) { c.du[n] = c.dl[n] = sv > 0 ? 1.0f : 0.0f; c.bu[n] = 0.0f; }
       cand[n] = sv == 0 && pl[n] < 0.0f && pu[n] > 0.0f;
     }
   }
   out.pre_lo.assign(pl.begin(), pl.end()); out.pre_hi.assign(pu.begin(), pu.end());
   out.smin.assign(nlit, 0.0); out.smax_plain.assign(nlit, 0.0); out.smax.assign(nlit, 0.0); out.ub0.assign(nlit, 0.0);
   out.uA.assign((size_t)nlit * n0, 0.0); out.best_step.assign(nlit, 0); out.branch.assign(nlit, -1);
-  const int dtop = xdims[K - 1];
-  std::vector<float> beta(acdim), lam(acdim), g(acdim), z, zn;
+  std::vector<float> beta(acdim), lam(acdim);
   for (int i = 0; i < nlit; ++i) {
-    auto head_row = [&](float& cst) {
-      row.assign(dtop, 0.0f);
-      for (int t = 0; t < dtop; ++t) row[t] = (float)head.H[(size_t)t * nlit + i];
-      cst = (float)head.H[(size_t)dtop * nlit + i];
-    };
     float cst;
-    head_row(cst);
-    out.smin[i] = backward(row, cst, K - 2, false, nullptr, nullptr, nullptr);
+    head_row(head, i, row, cst);
+    out.smin[i] = backward_row(c, K - 2, false, row, cst, nxt, plain(false));
     std::fill(beta.begin(), beta.end(), 0.0f);
-    float best = 0.0f, eta = (float)eta0;
-    for (int s = 0; s <= steps; ++s) {
-      head_row(cst);
-      int br = -1;
-      const float smax = backward(row, cst, K - 2, true, beta.data(), lam.data(), s == 0 ? &br : nullptr);
-      if (s == 0) { out.smax_plain[i] = smax; out.branch[i] = br; }
-      if (s == 0 || smax < best) {
-        best = smax;
-        out.smax[i] = smax; out.ub0[i] = cst; out.best_step[i] = s;
-        for (int q = 0; q < n0; ++q) out.uA[(size_t)i * n0 + q] = row[q];
-      }
-      if (s == steps) break;
-      // gradient: the relaxed network the pass chose, at the maximiser x* = c + sgn(uA) r
-      z.assign(n0, 0.0f);
-      for (int q = 0; q < n0; ++q) z[q] = c0[q] + (row[q] > 0.0f ? r0[q] : row[q] < 0.0f ? -r0[q] : 0.0f);
-      float gmax = 0.0f;
-      for (int j = 0; j + 1 < K; ++j) {
-        const int d = xdims[j + 1], in = xdims[j], o = aoff[j];
-        zn.assign(d, 0.0f);
-        for (int t = 0; t < d; ++t) {
-          float v = 0.0f;
-          for (int q = 0; q < in; ++q) v += W[j].at(t, q) * z[q];
-          v += bs[j][t];
-          const int sv = assign[o + t];
-          g[o + t] = sv != 0 ? (float)sv * v : 0.0f;
-          gmax = std::max(gmax, std::fabs(g[o + t]));
-          zn[t] = lam[o + t] > 0.0f ? du[o + t] * v + bu[o + t] : dl[o + t] * v;
-        }
-        z.swap(zn);
-      }
-      if (!(gmax > 0.0f)) break;          // stationary (no forced neuron, or every one of them at zero)
-      for (int n = 0; n < acdim; ++n) beta[n] = std::max(beta[n] - eta * g[n] / gmax, 0.0f);
-      eta *= (float)decay;
-    }
+    pg_literal(c, head, i, beta, lam, out,
+               [&](int n, float b, float& sb) { return entry(true, beta.data(), lam.data(), n, b, sb); },
+               [&](int n, float, float v) { return assign[n] != 0 ? (float)assign[n] * v : 0.0f; },
+               [&](int n) { return c.dl[n]; },
+               [](float x) { return std::max(x, 0.0f); },
+               [&](int s, float smax, bool) {
+                 if (s != 0) return;
+                 // the plain pass: its bound, and the branching neuron - the candidate with the largest max(lambda, 0) bu, the first of equals
+                 out.smax_plain[i] = smax;
+                 float bscore = -1.0f;
+                 for (int n = 0; n < acdim; ++n) {
+                   const float sc = std::max(lam[n], 0.0f) * c.bu[n];
+                   if (cand[n] && sc > bscore) { bscore = sc; out.branch[i] = n; }
+                 }
+               });
   }
   return out;
 }

@@ -31,10 +31,13 @@ With --frontier only the frontier leg runs and profiles/split_timing_frontier_<c
            run: total seconds, seconds["crown"], and for the device frontier the HIP-event time of its kernels; visited and levels
 With --alpha only the optimised-slope leg runs and profiles/split_timing_alpha_<case>.json is written:
   bound    CrownBounder.bound at nbox = 256 with alpha_steps 0, 4 and 8 and 1 and 10 literals: wall-clock of the call and HIP-event time of
-           its kernels (the plain one, and k_crown_alpha behind it when alpha_steps > 0), median of 7 after 2 warm calls
+           its kernels (the plain one, and k_crown_alpha of csrc/crown_alpha.hpp behind it when alpha_steps > 0), median of 7 after 2 warm calls
   host     makeIntervalsBatch(backend="host", workers=16) on the same boxes with the same settings, wall-clock, one run
   split    one verifySplit (bounds only, literal_bounds, crown_backend "resident", at most 512 boxes) of the literal y_0 - y_last per
            alpha_steps 0, 4, 8 and 4 with alpha_inherit: verdict, visited, `seconds`
+  with --no-host only `bound` runs, in the form of the --relu leg, and profiles/split_timing_alpha_bound_<case>.json is written instead:
+           nbox = 1, 256 and 4096, one literal, alpha_steps 0 and 4, median, min and max of the HIP-event time over 7 calls after 2 warm
+           ones - the rows a change of k_crown_alpha is compared on
 With --resident only the resident leg runs and profiles/split_timing_resident_<case>.json is written:
   bound    CrownBounder.bound beside makeIntervalsBatch(backend="gpu") at nbox = 1, 16, 256: wall-clock of the call and HIP-event time
            of the launch, median of 7 after 2 warm calls - what keeping the network on the device saves per level of a split tree
@@ -362,6 +365,19 @@ def _spread(call, runs=7, warm=2):
     return dict(kernel_ms_median=statistics.median(ker), kernel_ms_min=min(ker), kernel_ms_max=max(ker), call_ms_median=statistics.median(wall))
 
 
+def alpha_bound_rows(net, lo, hi):
+    """bound at 1, 256 and 4096 boxes with alpha_steps 0 and 4, one literal y_0 - y_last, on one bounder"""
+    ny = net.xdims[-1]
+    Cm = np.zeros((1, ny)); Cm[0, 0] = 1.0; Cm[0, ny - 1] -= 1.0
+    rows = []
+    with na.CrownBounder(net, Cm) as bd:
+        for n in (1, 256, 4096):
+            blo, bhi = sub_boxes(lo, hi, n)
+            rows.append(dict(nbox=n, **{f"alpha_steps{T}": _spread(lambda: bd.bound(blo, bhi, return_ms=True, alpha_steps=T)) for T in (0, 4)}))
+            print(rows[-1], flush=True)
+    return rows
+
+
 def relu_bound_rows(net, lo, hi):
     """bound_nodes at 1, 256 and 4096 nodes (sub-boxes of the root, 20 % of the neurons forced to the pattern of a seeded point) with 0 and
     16 multiplier steps, beside CrownBounder.bound on the same boxes in the same process; one literal y_0 - y_last"""
@@ -430,7 +446,7 @@ if __name__ == "__main__":
     lit_leg, res_leg, alpha_leg, frontier_leg, reach_leg, wide_leg = ("--nlit" in args, "--resident" in args, "--alpha" in args, "--frontier" in args,
                                                                       "--reach" in args, "--wide" in args)
     forest_leg = "--forest" in args
-    names = [a for a in args if a not in ("--nlit", "--resident", "--alpha", "--frontier", "--reach", "--wide", "--forest")] or \
+    names = [a for a in args if not a.startswith("--")] or \
         (["W40-D20", "acas-shape", "5-100x4-5"] if wide_leg else ["W10-D5", "acas-shape"] if forest_leg else ["W10-D5", "W40-D20", "acas-shape"])
     out_dir = os.environ.get("SPLIT_TIMING_OUT", os.path.join(ROOT, "profiles"))
     os.makedirs(out_dir, exist_ok=True)
@@ -451,6 +467,10 @@ if __name__ == "__main__":
         if frontier_leg:
             with open(os.path.join(out_dir, f"split_timing_frontier_{name}.json"), "w") as fh:
                 json.dump(dict(case=name, xdims=net.xdims, **frontier_rows(net, lo, hi)), fh, indent=1)
+            continue
+        if alpha_leg and "--no-host" in args:
+            with open(os.path.join(out_dir, f"split_timing_alpha_bound_{name}.json"), "w") as fh:
+                json.dump(dict(case=name, xdims=net.xdims, bound=alpha_bound_rows(net, lo, hi)), fh, indent=1)
             continue
         if alpha_leg:
             with open(os.path.join(out_dir, f"split_timing_alpha_{name}.json"), "w") as fh:
