@@ -591,8 +591,48 @@ int nnsdp_crown_reach(nnsdp_crown* h, const double* x1min, const double* x1max, 
  * nleaves, bound nlit x nleaves, column-major): closed 1 ("crown") or 0 (open: the budget ended the search); bound: ub of every direction. */
 int nnsdp_crown_reach_leaves(nnsdp_crown* h, double* lo, double* hi, int32_t* depth, int32_t* closed, double* bound);
 
-/* what: 0 device allocations made so far, 1 network uploads so far, 2 box capacity, 3 sample capacity, 4 bound calls (a search and a
- * search_many count one per chunk), 5 device bytes held, 6 reach searches so far, 7 the handle's max_width (64 or 128). */
+/* The ReLU-split search of nnsdp_amd/relusplit.py (verifyReluSplit, _levels) with the node frontier kept on the device
+ * (csrc/crown_node_search.hpp): decides the clause  OR_i normal_i' f(x) <= hs[i]  of the handle's literals on the root box x1min / x1max
+ * (xdims[0] each) by forcing the signs of unstable ReLUs.  A node is an assignment in {-1, 0, +1}^acdim; the frontier is two buffers
+ * of acdim x max_nodes bytes.  Per level: the two node kernels of nnsdp_crown_bound_nodes on chunks of at most `chunk` nodes, their
+ * assignments read directly from the frontier and their boxes from one chunk of copies of the root box written once; per node the
+ * infeasible flag first, else the first minimum over i of smax_i - hs[i] (closed by "bound" when it is <= 0, else stuck when the best
+ * literal has no neuron to branch on, else branching); the forward pass on the level's points: the box centre and (corner_points) per
+ * node and literal  c + sign(uA_i) r, c = 0.5 (lo + hi), r = 0.5 (hi - lo), sign(0) = 0, product and sum rounded separately; a point is
+ * a candidate when every literal is false there and (except the centre) its node is open; closed nodes write assignment, depth, kind
+ * and bound to a leaf log, stuck nodes to a second log, the r-th branching node its children 2r (its neuron forced +1) and 2r + 1 (-1)
+ * into the other frontier, all in device memory.  The host reads back five integers per level (bounded, closed, stuck, branching,
+ * candidates), the flags and points only on a level that counts candidates, and the leaves once at the end.  Verdict, reason, visited,
+ * depth, witness and the order and bits of the leaves are those of the Python loop on the resident bounder, for any chunk.  No atomics.
+ * confirm: called on the host for the flagged points of a level without duplicates, in lexicographic order of their coordinates (the
+ * first most significant); a return value other than 0 makes the point the witness.  NULL accepts the first.
+ * The search ends "holds" (verdict 0) when every node is closed, "violated" (1) with the witness, "unknown" (2) with reason 1 (budget:
+ * the children of the branching nodes would make more than max_nodes nodes bounded, or be deeper than max_depth; a level is only
+ * created when the budget holds all of it) or 2 (exhausted: stuck nodes remain and nothing branches).  Outputs: verdict, reason (0
+ * unless unknown), visited, depth_reached, nleaves (closed leaves), nopen (open nodes), witness (xdims[0], written when violated),
+ * kernel_ms (may be NULL: event time of all launches).
+ * Device memory: 4 acdim max_nodes bytes of frontiers and logs, and per node of max_nodes 8 (3 + p (xdims[0] + xdims[K])) + 4 (9 + p)
+ * bytes of records and points (p = nlit with corner_points, else 0), allocated at the first search and reused by a later one that
+ * needs no more; the node kernels' buffers are those of nnsdp_crown_bound_nodes and hold min(chunk, max_nodes) nodes unless an
+ * earlier call made them larger.  Counted by nnsdp_crown_info.
+ * -1 with a message, before the GPU is touched and before anything is allocated: max_nodes < 1, chunk < 1, max_depth < 0, steps, eta0
+ * or decay out of range (in this order, also on a NULL handle), a null handle, a wide handle, a Tanh handle, a handle without
+ * literals, a null argument, nlit that is not the handle's, a non-finite threshold or box entry, x1min > x1max, buffers above 2^31
+ * bytes.  Not thread-safe. */
+int nnsdp_crown_search_nodes(nnsdp_crown* h, const double* x1min, const double* x1max, int32_t nlit, const double* hs, int32_t steps,
+                             double eta0, double decay, int32_t corner_points, int32_t max_nodes, int32_t max_depth, int32_t chunk,
+                             nnsdp_confirm_fn confirm, void* user, int32_t* verdict, int32_t* reason, int32_t* visited, int32_t* depth_reached,
+                             int32_t* nleaves, int32_t* nopen, double* witness, double* kernel_ms);
+
+/* The leaves of the handle's last node search (HOST arrays of nleaves + nopen rows; assign acdim per row): the closed leaves in level
+ * order and then node order (closed_by 0 infeasible, with a NaN bound, or 1 bound), then the open nodes (closed_by -1) in the order of
+ * the Python loop: the stuck nodes of earlier levels, then on "violated" every open node of the last level, on "budget" its stuck
+ * and then its branching nodes.  bound: smax of the literal closest to its threshold. */
+int nnsdp_crown_search_nodes_leaves(nnsdp_crown* h, int8_t* assign, int32_t* depth, int32_t* closed_by, double* bound);
+
+/* what: 0 device allocations made so far, 1 network uploads so far, 2 box capacity, 3 sample capacity, 4 bound calls (a search, a
+ * search_many and a node search count one per chunk), 5 device bytes held, 6 reach searches so far, 7 the handle's max_width (64 or
+ * 128), 8 node searches so far, 9 status records (levels) they read back, 10 levels whose flags and points they downloaded. */
 int nnsdp_crown_info(nnsdp_crown* h, int32_t what, double* out);
 
 /* NULL is a no-op returning 0. */

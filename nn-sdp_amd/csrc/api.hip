@@ -16,6 +16,7 @@
 #include "crown_search.hpp"
 #include "crown_forest.hpp"
 #include "crown_reach.hpp"
+#include "crown_node_search.hpp"
 #include "solver.hpp"
 #include "batch.hpp"
 #include "crown_handle.hpp"
@@ -769,6 +770,28 @@ int nnsdp_crown_reach_leaves(nnsdp_crown* h, double* lo, double* hi, int32_t* de
   API_END
 }
 
+int nnsdp_crown_search_nodes(nnsdp_crown* h, const double* x1min, const double* x1max, int32_t nlit, const double* hs, int32_t steps,
+                             double eta0, double decay, int32_t corner_points, int32_t max_nodes, int32_t max_depth, int32_t chunk,
+                             nnsdp_confirm_fn confirm, void* user, int32_t* verdict, int32_t* reason, int32_t* visited, int32_t* depth_reached,
+                             int32_t* nleaves, int32_t* nopen, double* witness, double* kernel_ms) {
+  API_BEGIN
+  nnsdp_crown::search_nodes(h, x1min, x1max, nlit, hs, steps, eta0, decay, corner_points, max_nodes, max_depth, chunk, confirm, user, verdict,
+                            reason, visited, depth_reached, nleaves, nopen, witness, kernel_ms);
+  API_END
+}
+
+int nnsdp_crown_search_nodes_leaves(nnsdp_crown* h, int8_t* assign, int32_t* depth, int32_t* closed_by, double* bound) {
+  API_BEGIN
+  if (!h) throw std::invalid_argument("null handle");
+  const nnsdp_crown::NodeLeaves& L = h->nleaves_;
+  if (!L.depth.empty() && (!assign || !depth || !closed_by || !bound)) throw std::invalid_argument("null argument");
+  std::copy(L.assign.begin(), L.assign.end(), assign);
+  std::copy(L.depth.begin(), L.depth.end(), depth);
+  std::copy(L.closed_by.begin(), L.closed_by.end(), closed_by);
+  std::copy(L.bound.begin(), L.bound.end(), bound);
+  API_END
+}
+
 int nnsdp_crown_info(nnsdp_crown* h, int32_t what, double* out) {
   API_BEGIN
   if (!h || !out) throw std::invalid_argument("null argument");
@@ -781,7 +804,10 @@ int nnsdp_crown_info(nnsdp_crown* h, int32_t what, double* out) {
     case 5: *out = (double)h->device_bytes(); break;
     case 6: *out = (double)h->n_reach; break;
     case 7: *out = (double)h->max_width; break;
-    default: throw std::invalid_argument("nnsdp_crown_info: what must be in 0..7");
+    case 8: *out = (double)h->n_node_search; break;
+    case 9: *out = (double)h->n_node_levels; break;
+    case 10: *out = (double)h->n_node_downloads; break;
+    default: throw std::invalid_argument("nnsdp_crown_info: what must be in 0..10");
   }
   API_END
 }

@@ -1,7 +1,8 @@
-// What the three device-resident split searches share on the device: the single clause search (csrc/crown_search.hpp), the reach search
-// (csrc/crown_reach.hpp) and the forest of searches (csrc/crown_forest.hpp).  Each search's result is defined as the Python loop's tree
-// (nnsdp_amd/split.py) bit for bit, so every piece of arithmetic that decides something is stated here ONCE and the kernels of the three
-// headers are thin bodies over it: a literal's bound and the best literal of a box, the split coordinate, the centre and a corner of
+// What the device-resident split searches share on the device: the single clause search (csrc/crown_search.hpp), the reach search
+// (csrc/crown_reach.hpp), the forest of searches (csrc/crown_forest.hpp) and the ReLU-split node search (csrc/crown_node_search.hpp,
+// which takes the centre, its own corner, the flag "every literal false" and the scan tile from here).  Each search's result is defined
+// as the Python loop's tree (nnsdp_amd/split.py, nnsdp_amd/relusplit.py) bit for bit, so every piece of arithmetic that decides
+// something is stated here ONCE and the kernels of the headers are thin bodies over it: a literal's bound and the best literal of a box, the split coordinate, the centre and a corner of
 // a box, normal' y and the flag "every literal false", the bisection, the head of a leaf-log row, the 256-wide scan tile.
 //
 // The arithmetic restates numpy's operation for operation: products and sums are rounded separately, sums have numpy's order, minima
@@ -110,6 +111,18 @@ __device__ __forceinline__ void frontier_centre(double* x, const double* lo, con
 }
 __device__ __forceinline__ void frontier_corner(double* x, const double* A, const double* lo, const double* hi, int n0) {
   for (int t = 0; t < n0; ++t) x[t] = A[t] >= 0.0 ? hi[t] : lo[t];
+}
+
+// the ReLU-split driver's corner  c + sign(A) r  with c = 0.5 (lo + hi), r = 0.5 (hi - lo) and numpy's sign (sign(0) = 0, sign(NaN) =
+// NaN); the product and the sum are rounded separately.  Not frontier_corner: where A is zero this is the centre's coordinate
+__device__ __forceinline__ void frontier_sign_corner(double* x, const double* A, const double* lo, const double* hi, int n0) {
+#pragma clang fp contract(off)
+  for (int t = 0; t < n0; ++t) {
+    const double c = 0.5 * (lo[t] + hi[t]), r = 0.5 * (hi[t] - lo[t]), v = A[t];
+    const double sg = v > 0.0 ? 1.0 : v < 0.0 ? -1.0 : v == 0.0 ? 0.0 : v;
+    const double m = sg * r;
+    x[t] = c + m;
+  }
 }
 
 // normal' y as numpy's  (normal[:, None] * Y).sum(axis=0)  gives it: n_0 y_0, then + n_j y_j for j ascending (ny >= 1)

@@ -1,13 +1,14 @@
-// The level loops of the three device-resident split searches of the resident bounder: nnsdp_crown::search (kernels: csrc/crown_search.hpp),
-// nnsdp_crown::reach (csrc/crown_reach.hpp) and nnsdp_crown::search_many (csrc/crown_forest.hpp), and what they share on the host: the
+// The level loops of the device-resident split searches of the resident bounder: nnsdp_crown::search (kernels: csrc/crown_search.hpp),
+// nnsdp_crown::reach (csrc/crown_reach.hpp), nnsdp_crown::search_many (csrc/crown_forest.hpp) and nnsdp_crown::search_nodes (the ReLU
+// split, csrc/crown_node_search.hpp; its frontier holds assignments, not boxes), and what they share on the host: the
 // refusals, the carving of a level's frontier (FrontierBufs, csrc/crown_handle.hpp), the chunked "bound, then classify" pass and the
 // end of a level.  Part of the translation unit api.hip, behind crown_handle.hpp.
 #pragma once
 
 // the scalar options of every search; they come before the null handle, and the null handle before the null arguments, so that these
 // refusals can be tested on a machine without a GPU, where no handle exists
-static void check_search_options(int32_t max_boxes, int32_t chunk, int32_t max_depth) {
-  if (max_boxes < 1) throw std::invalid_argument("max_boxes must be >= 1, got " + std::to_string(max_boxes));
+static void check_search_options(int32_t max_boxes, int32_t chunk, int32_t max_depth, const char* budget = "max_boxes") {
+  if (max_boxes < 1) throw std::invalid_argument(std::string(budget) + " must be >= 1, got " + std::to_string(max_boxes));
   if (chunk < 1) throw std::invalid_argument("chunk must be >= 1, got " + std::to_string(chunk));
   if (max_depth < 0) throw std::invalid_argument("max_depth must be >= 0, got " + std::to_string(max_depth));
 }
@@ -508,6 +509,147 @@ inline void nnsdp_crown::reach(nnsdp_crown* h, const double* x1min, const double
   HIPCHK(hipMemcpy(incumbent, r.L, nlit * sizeof(double), hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(witnesses, r.xw, (size_t)nlit * n0 * sizeof(double), hipMemcpyDeviceToHost));
   *status = stat; *visited = vis; *depth_reached = depth; *nleaves = (int32_t)Lv.depth.size();
+  if (kernel_ms) *kernel_ms = ms_all;
+}
+
+// nnsdp_crown_search_nodes: the level loop of relusplit.py (_levels) on the handle's stream (csrc/crown_node_search.hpp); every refusal
+// comes before anything is allocated
+inline void nnsdp_crown::search_nodes(nnsdp_crown* h, const double* x1min, const double* x1max, int32_t nlit, const double* hs, int32_t steps,
+                                      double eta0, double decay, int32_t corner_points, int32_t max_nodes, int32_t max_depth, int32_t chunk,
+                                      nnsdp_confirm_fn confirm, void* user, int32_t* verdict, int32_t* reason, int32_t* visited,
+                                      int32_t* depth_reached, int32_t* nleaves, int32_t* nopen_out, double* witness, double* kernel_ms) {
+  check_search_options(max_nodes, chunk, max_depth, "max_nodes");
+  check_pg_options("nodes", steps, eta0, decay);
+  if (!h) throw std::invalid_argument("null handle");
+  if (h->wide()) throw std::invalid_argument("a ReLU split is not available on a wide bounder (max_width 128): the node kernels keep a 64-wide layout");
+  if (h->activ != NNSDP_ACTIV_RELU) throw std::invalid_argument("a ReLU split is for ReLU networks, not Tanh");
+  if (h->nlit < 1) throw std::invalid_argument("a ReLU split needs literals: the handle was created without normals");
+  if (!x1min || !x1max || !hs || !verdict || !reason || !visited || !depth_reached || !nleaves || !nopen_out || !witness) throw std::invalid_argument("null argument");
+  if (nlit != h->nlit) throw std::invalid_argument("nlit must be the handle's " + std::to_string(h->nlit) + ", got " + std::to_string(nlit));
+  for (int i = 0; i < nlit; ++i)
+    if (!std::isfinite(hs[i])) throw std::invalid_argument("literal " + std::to_string(i) + ": the threshold hs is not finite (NaN or infinity)");
+  const int n0 = h->n0, ny = h->ny, acdim = h->acdim;
+  (void)root_box_mask(n0, x1min, x1max);
+  // every level fits the budget as a whole, so no level, no log and no set of children has more than max_nodes nodes
+  const size_t mn = (size_t)max_nodes, npmax = corner_points ? 1 + mn * (size_t)nlit : 1, cb = std::min((size_t)chunk, mn);
+  // bytes: the two frontiers, the leaf log, the stuck log
+  const size_t nby = 4 * mn * (size_t)acdim;
+  // doubles: bound, points in, points out, the bounds of the two logs, normals, hs, the root box
+  const size_t o_bound = 0, o_X = o_bound + mn, o_Y = o_X + npmax * n0, o_lb = o_Y + npmax * ny, o_sb = o_lb + mn, o_nrm = o_sb + mn,
+               o_hs = o_nrm + (size_t)nlit * ny, o_root = o_hs + nlit, nd = o_root + 2 * (size_t)n0;
+  // ints: kind, best, neuron, the three ranks, depth and kind of the leaf log, depth of the stuck log, point flags, status
+  const size_t o_pf = 9 * mn, o_st = o_pf + npmax, ni = o_st + 5;
+  const size_t worst = std::max(nby, std::max(nd * sizeof(double), ni * sizeof(int)));
+  if (worst > nnsdp::kSearchFrontierCap)
+    throw std::invalid_argument("max_nodes = " + std::to_string(max_nodes) + " needs " + std::to_string(worst) +
+                                " bytes of " + (worst == nby ? "frontier and log" : worst == nd * sizeof(double) ? "point and record" : "record") +
+                                " buffers, above the cap of 2^31 bytes");
+  h->nleaves_.clear();
+  h->reserve_nodes(cb);
+  if (nby > h->nsby.n) { h->nsby.alloc(nby); ++h->n_alloc; }
+  if (nd > h->nsdb.n) { h->nsdb.alloc(nd); ++h->n_alloc; }
+  if (ni > h->nsib.n) { h->nsib.alloc(ni); ++h->n_alloc; }
+  if (!h->hnstatus) HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&h->hnstatus), 5 * sizeof(int), hipHostMallocDefault));
+  ++h->n_node_search;
+  hipStream_t st = h->st;
+  double* D = h->nsdb.p;
+  int* I = h->nsib.p;
+  int8_t* const fr[2] = {h->nsby.p, h->nsby.p + mn * acdim};
+  HIPCHK(hipMemcpyAsync(D + o_nrm, h->normals.data(), (size_t)nlit * ny * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(D + o_hs, hs, nlit * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(D + o_root, x1min, n0 * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(D + o_root + n0, x1max, n0 * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemsetAsync(fr[0], 0, (size_t)acdim, st));      // the root: every neuron free
+  HIPCHK(hipStreamSynchronize(st));      // (the sources are the caller's pageable arrays)
+  // the boxes of one chunk, written once: every node has the root's
+  double* const blo = h->dnin.p;
+  double* const bhi = blo + cb * n0;
+  FRONTIER_LAUNCH(nnsdp::k_node_boxes, cdiv(cb * n0, 256), (const double*)(D + o_root), (const double*)(D + o_root + n0), n0, (long long)cb, blo, bhi);
+
+  nnsdp::NodeSearchArgs a;
+  a.n0 = n0; a.ny = ny; a.nlit = nlit; a.acdim = acdim; a.corner_points = corner_points != 0; a.max_nodes = max_nodes;
+  a.normals = D + o_nrm; a.hs = D + o_hs; a.lo = blo; a.hi = bhi;
+  a.kind = I; a.best = I + mn; a.neuron = I + 2 * mn; a.rclosed = I + 3 * mn; a.rstuck = I + 4 * mn; a.rbranch = I + 5 * mn;
+  a.ldepth = I + 6 * mn; a.lkind = I + 7 * mn; a.sdepth = I + 8 * mn; a.pflag = I + o_pf; a.status = I + o_st;
+  a.bound = D + o_bound; a.X = D + o_X; a.Y = D + o_Y; a.lbound = D + o_lb; a.sbound = D + o_sb;
+  a.lassign = h->nsby.p + 2 * mn * acdim; a.sassign = h->nsby.p + 3 * mn * acdim;
+
+  int cur = 0, nb = 1, vis = 0, depth = 0, verd = -1, reas = 0, tail = 0;      // tail: 0 no open node of the last level, 1 all, 2 the branching ones
+  long long log_n = 0, slog_n = 0;
+  double ms_all = 0.0;
+  std::vector<double> wit;
+  for (;;) {
+    vis += nb;
+    a.nb = nb; a.depth = depth; a.visited = vis; a.children = depth + 1 <= max_depth;
+    a.cur = fr[cur]; a.nxt = fr[cur ^ 1]; a.log_base = log_n; a.slog_base = slog_n;
+    HIPCHK(hipEventRecord(h->e0, st));
+    for (int off = 0; off < nb; off += (int)cb) {
+      const size_t nc = std::min(cb, (size_t)(nb - off));
+      const nnsdp::CrownNodeArgs p = h->node_args(h->node_layout(nc), blo, bhi, a.cur + (size_t)off * acdim, steps, eta0, decay);
+      h->launch_nodes(p, nc);
+      FRONTIER_LAUNCH(nnsdp::k_node_classify, cdiv(nc, 256), a, off, (int)nc, (const double*)p.o.smax, (const double*)p.o.uA,
+                      (const double*)p.sp.branch, (const double*)p.infeasible);
+      ++h->n_bound;
+    }
+    const long long npts = corner_points ? 1 + (long long)nb * nlit : 1;
+    h->launch_forward(a.X, D + o_Y, npts);
+    FRONTIER_LAUNCH(nnsdp::k_node_refute, cdiv(npts, 256), a, npts);
+    FRONTIER_LAUNCH(nnsdp::k_node_scan, 1, a, npts);
+    FRONTIER_LAUNCH(nnsdp::k_node_scatter, cdiv(nb, 256 / nnsdp::kNodeLanes), a);
+    ms_all += finish_level(h, h->hnstatus, a.status, 5);
+    ++h->n_node_levels;
+    const int nclosed = h->hnstatus[1], nstuck = h->hnstatus[2], nbranch = h->hnstatus[3], ncand = h->hnstatus[4];
+    if (h->hnstatus[0] != nb || nclosed < 0 || nstuck < 0 || nbranch < 0 || nclosed + nstuck + nbranch != nb)
+      throw std::runtime_error("nnsdp_crown_search_nodes: inconsistent status record");
+    log_n += nclosed;
+    if (nstuck + nbranch == 0) { verd = slog_n > 0 ? 2 : 0; reas = slog_n > 0 ? 2 : 0; break; }
+    if (ncand > 0) {      // the level's flags and points; the flagged points without duplicates, in lexicographic order (np.unique(axis=1))
+      ++h->n_node_downloads;
+      const std::vector<int> pf = from_device(a.pflag, (size_t)npts);
+      const std::vector<double> X = from_device(a.X, (size_t)npts * n0);
+      std::vector<size_t> cand;
+      for (size_t p = 0; p < (size_t)npts; ++p)
+        if (pf[p]) cand.push_back(p);
+      auto less = [&](size_t p, size_t q) { return std::lexicographical_compare(X.begin() + p * n0, X.begin() + (p + 1) * n0, X.begin() + q * n0, X.begin() + (q + 1) * n0); };
+      auto same = [&](size_t p, size_t q) { return std::equal(X.begin() + p * n0, X.begin() + (p + 1) * n0, X.begin() + q * n0); };
+      std::stable_sort(cand.begin(), cand.end(), less);
+      cand.erase(std::unique(cand.begin(), cand.end(), same), cand.end());
+      for (size_t k = 0; k < cand.size() && wit.empty(); ++k) {
+        const double* x = X.data() + cand[k] * n0;
+        if (!confirm || confirm(user, x) != 0) wit.assign(x, x + n0);
+      }
+    }
+    if (!wit.empty()) { verd = 1; tail = 1; break; }
+    slog_n += nstuck;
+    if (nbranch == 0) { verd = 2; reas = 2; break; }
+    if ((long long)vis + 2LL * nbranch > (long long)max_nodes || depth + 1 > max_depth) { verd = 2; reas = 1; tail = 2; break; }      // (k_node_scatter's rule)
+    cur ^= 1; nb = 2 * nbranch; ++depth;
+  }
+  // the leaves once, at the end: the closed log; then the open nodes: the stuck log, then what the last level leaves open
+  NodeLeaves& Lv = h->nleaves_;
+  {
+    const std::vector<int8_t> as = from_device((const int8_t*)a.lassign, (size_t)log_n * acdim);
+    const std::vector<int> dp = from_device((const int*)a.ldepth, (size_t)log_n), kd = from_device((const int*)a.lkind, (size_t)log_n);
+    const std::vector<double> bd = from_device((const double*)a.lbound, (size_t)log_n);
+    for (size_t r = 0; r < (size_t)log_n; ++r) Lv.add(acdim, as.data() + r * acdim, dp[r], kd[r], bd[r]);
+  }
+  const size_t nclosed_all = Lv.depth.size();
+  {
+    const std::vector<int8_t> as = from_device((const int8_t*)a.sassign, (size_t)slog_n * acdim);
+    const std::vector<int> dp = from_device((const int*)a.sdepth, (size_t)slog_n);
+    const std::vector<double> bd = from_device((const double*)a.sbound, (size_t)slog_n);
+    for (size_t r = 0; r < (size_t)slog_n; ++r) Lv.add(acdim, as.data() + r * acdim, dp[r], -1, bd[r]);
+  }
+  if (tail) {
+    const std::vector<int8_t> as = from_device((const int8_t*)a.cur, (size_t)nb * acdim);
+    const std::vector<int> kd = from_device((const int*)a.kind, (size_t)nb);
+    const std::vector<double> bd = from_device((const double*)a.bound, (size_t)nb);
+    for (size_t b = 0; b < (size_t)nb; ++b)
+      if (tail == 1 ? kd[b] >= nnsdp::kNodeStuck : kd[b] == nnsdp::kNodeBranching) Lv.add(acdim, as.data() + b * acdim, depth, -1, bd[b]);
+  }
+  *verdict = verd; *reason = reas; *visited = vis; *depth_reached = depth;
+  *nleaves = (int32_t)nclosed_all; *nopen_out = (int32_t)(Lv.depth.size() - nclosed_all);
+  if (verd == 1) std::copy(wit.begin(), wit.end(), witness);
   if (kernel_ms) *kernel_ms = ms_all;
 }
 

@@ -123,6 +123,24 @@ struct nnsdp_crown {
     std::vector<int32_t> depth, closed;
     void clear() { lo.clear(); hi.clear(); bound.clear(); depth.clear(); closed.clear(); }
   } rleaves;
+  // nnsdp_crown_search_nodes (csrc/crown_node_search.hpp; nothing before its first call): the two frontiers and the two logs of
+  // assignments, one block of doubles and one of ints, sized from max_nodes at the call; they only grow.  The node kernels' buffers
+  // (reserve_nodes) are shared with nnsdp_crown_bound_nodes and hold one chunk
+  DBuf<int8_t> nsby;
+  DBuf<double> nsdb;
+  DBuf<int> nsib;
+  int* hnstatus = nullptr;               // pinned: the five integers of a level
+  long long n_node_search = 0, n_node_levels = 0, n_node_downloads = 0;      // searches, status records read, levels whose points came back
+  struct NodeLeaves {                    // closed leaves, then the open nodes, each in the order of the Python loop; assign acdim per row
+    std::vector<int8_t> assign;
+    std::vector<int32_t> depth, closed_by;      // closed_by: 0 infeasible, 1 bound, -1 open
+    std::vector<double> bound;
+    void clear() { assign.clear(); depth.clear(); closed_by.clear(); bound.clear(); }
+    void add(int acdim, const int8_t* s, int d, int by, double bnd) {
+      assign.insert(assign.end(), s, s + acdim);
+      depth.push_back(d); closed_by.push_back(by); bound.push_back(bnd);
+    }
+  } nleaves_;
 
   size_t scr_per_box() const { return (size_t)(activ == NNSDP_ACTIV_TANH ? 6 : 2) * acdim; }
   nnsdp::CrownLayout layout(size_t nbox) const { return nnsdp::CrownLayout{nbox, (size_t)n0, (size_t)acdim, (size_t)ny, (size_t)nlit}; }
@@ -150,7 +168,8 @@ struct nnsdp_crown {
   }
   size_t device_bytes() const {
     return dxd.bytes() + dao.bytes() + dmo.bytes() + dM.bytes() + din.bytes() + dscr.bytes() + dout.bytes() + dX.bytes() + dY.bytes() +
-           dain.bytes() + daout.bytes() + dast.bytes() + dnin.bytes() + dnout.bytes() + dnst.bytes() + sbuf.bytes() + rbuf.bytes() + fbuf.bytes();
+           dain.bytes() + daout.bytes() + dast.bytes() + dnin.bytes() + dnout.bytes() + dnst.bytes() + sbuf.bytes() + rbuf.bytes() + fbuf.bytes() +
+           nsby.bytes() + nsdb.bytes() + nsib.bytes();
   }
   // the capacity grows geometrically and never shrinks
   // staging = false (a search: nothing of a box crosses the bus): the pinned copies wait for the next bound call
@@ -382,18 +401,9 @@ struct nnsdp_crown {
     std::copy(assign, assign + L.nnode * acdim, hasg);
     hipStream_t st = h->st;
     HIPCHK(hipMemcpyAsync(h->dnin.p, h->hnin, 2 * nin * sizeof(double) + L.nnode * acdim, hipMemcpyHostToDevice, st));
-    nnsdp::CrownNodeArgs p;
-    p.o.c.K = h->K; p.o.c.xdims = h->dxd.p; p.o.c.moff = h->dmo.p; p.o.c.acoff = h->dao.p; p.o.c.M = h->dM.p; p.o.c.H = h->dM.p + h->moff[h->K];
-    p.o.c.lo = h->dnin.p; p.o.c.hi = h->dnin.p + nin;
-    p.sp.assign = reinterpret_cast<const int8_t*>(h->dnin.p + 2 * nin); p.sp.infeasible = 0;
-    L.point(p, h->dnout.p);
-    p.o.steps = steps; p.o.eta0 = eta0; p.o.decay = decay;
-    p.o.cur = h->dnst.p; p.o.lam = p.o.cur + L.nst();
+    const nnsdp::CrownNodeArgs p = h->node_args(L, h->dnin.p, h->dnin.p + nin, reinterpret_cast<const int8_t*>(h->dnin.p + 2 * nin), steps, eta0, decay);
     HIPCHK(hipEventRecord(h->e0, st));
-    hipLaunchKernelGGL(nnsdp::k_crown_nodes, dim3((unsigned)nnode), dim3(256), nnsdp::kCbLdsBytesTanh, st, p);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(nnsdp::k_crown_beta, dim3((unsigned)nnode), dim3(256), nnsdp::kCoLdsBytes, st, p);
-    HIPCHK(hipGetLastError());
+    h->launch_nodes(p, L.nnode);
     HIPCHK(hipEventRecord(h->e1, st));
     HIPCHK(hipMemcpyAsync(h->hnout, h->dnout.p, L.total() * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
@@ -416,6 +426,26 @@ struct nnsdp_crown {
     if (out.uA) std::copy(src, src + L.nA(), out.uA);
     src += L.nA();
     ints(src, L.nnode, out.infeasible);
+  }
+
+  // the node kernels' arguments for the nodes lo / hi / assign of layout L: outputs in dnout, multiplier state in dnst (reserve_nodes)
+  nnsdp::CrownNodeArgs node_args(const nnsdp::CrownNodeLayout& L, const double* lo, const double* hi, const int8_t* assign, int32_t steps,
+                                 double eta0, double decay) const {
+    nnsdp::CrownNodeArgs p;
+    p.o.c.K = K; p.o.c.xdims = dxd.p; p.o.c.moff = dmo.p; p.o.c.acoff = dao.p; p.o.c.M = dM.p; p.o.c.H = dM.p + moff[K];
+    p.o.c.lo = lo; p.o.c.hi = hi;
+    p.sp.assign = assign; p.sp.infeasible = 0;
+    L.point(p, dnout.p);
+    p.o.steps = steps; p.o.eta0 = eta0; p.o.decay = decay;
+    p.o.cur = dnst.p; p.o.lam = p.o.cur + L.nst();
+    return p;
+  }
+  // the one place that launches the two node kernels (nnsdp_crown_bound_nodes, and every chunk of nnsdp_crown_search_nodes)
+  void launch_nodes(const nnsdp::CrownNodeArgs& p, size_t nnode) {
+    hipLaunchKernelGGL(nnsdp::k_crown_nodes, dim3((unsigned)nnode), dim3(256), nnsdp::kCbLdsBytesTanh, st, p);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(nnsdp::k_crown_beta, dim3((unsigned)nnode), dim3(256), nnsdp::kCoLdsBytes, st, p);
+    HIPCHK(hipGetLastError());
   }
 
   // nnsdp_crown_eval
@@ -452,12 +482,17 @@ struct nnsdp_crown {
   static void reach(nnsdp_crown* h, const double* x1min, const double* x1max, int32_t nlit, const double* tol, int32_t corner_points,
                     int32_t max_boxes, int32_t max_depth, int32_t chunk, int32_t* status, int32_t* visited, int32_t* depth_reached,
                     int32_t* nleaves, double* incumbent, double* witnesses, double* kernel_ms);
+  static void search_nodes(nnsdp_crown* h, const double* x1min, const double* x1max, int32_t nlit, const double* hs, int32_t steps, double eta0,
+                           double decay, int32_t corner_points, int32_t max_nodes, int32_t max_depth, int32_t chunk, nnsdp_confirm_fn confirm,
+                           void* user, int32_t* verdict, int32_t* reason, int32_t* visited, int32_t* depth_reached, int32_t* nleaves,
+                           int32_t* nopen, double* witness, double* kernel_ms);
 
   ~nnsdp_crown() {
     if (st) (void)hipStreamSynchronize(st);
     for (double* h : {hin, hout, hX, hY, hain, haout, hnin, hnout}) if (h) (void)hipHostFree(h);
     if (hstatus) (void)hipHostFree(hstatus);
     if (hforest) (void)hipHostFree(hforest);
+    if (hnstatus) (void)hipHostFree(hnstatus);
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
     if (st) (void)hipStreamDestroy(st);

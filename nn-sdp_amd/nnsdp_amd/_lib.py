@@ -122,6 +122,9 @@ SYMBOLS = [
     ("nnsdp_crown_reach", C.c_int, [C.c_void_p, c_double_p, c_double_p, C.c_int32, c_double_p] + [C.c_int32] * 4 + [c_int32_p] * 4
      + [c_double_p] * 3),
     ("nnsdp_crown_reach_leaves", C.c_int, [C.c_void_p, c_double_p, c_double_p, c_int32_p, c_int32_p, c_double_p]),
+    ("nnsdp_crown_search_nodes", C.c_int, [C.c_void_p, c_double_p, c_double_p, C.c_int32, c_double_p, C.c_int32, C.c_double, C.c_double]
+     + [C.c_int32] * 4 + [C.c_void_p, C.c_void_p] + [c_int32_p] * 6 + [c_double_p, c_double_p]),
+    ("nnsdp_crown_search_nodes_leaves", C.c_int, [C.c_void_p, C.POINTER(C.c_int8), c_int32_p, c_int32_p, c_double_p]),
     ("nnsdp_crown_info", C.c_int, [C.c_void_p, C.c_int32, c_double_p]),
     ("nnsdp_crown_destroy", C.c_int, [C.c_void_p]),
     ("nnsdp_project_psd_batched", C.c_int, [C.c_int32, c_int32_p, c_double_p, c_double_p, c_double_p, c_double_p]),

@@ -457,10 +457,13 @@ class CrownBounder:
     max_width=128 (nnsdp_crown_create_wide) asks for the wide instance of the kernel (csrc/crown_wide.hpp): hidden layers up to 128
     wide, while xdims[0], xdims[K] and nlit stay at 64 or below.  It runs one workgroup per CU where the narrow one runs two, so it is
     never chosen silently; on a network of widths <= 64 it returns the bits of the narrow instance.  bound, eval, search, search_many,
-    reach and info work on it; optimised slopes (alpha_steps, alpha0) do not - the alpha kernel keeps its 64-wide layout - and raise ValueError.
+    reach and info work on it; optimised slopes (alpha_steps, alpha0) do not - the alpha kernel keeps its 64-wide layout - and raise ValueError,
+    and neither do bound_nodes and search_nodes (the ReLU split's node kernels keep that layout too).
     A context manager; not thread-safe."""
 
     _INFO = ("device_allocations", "network_uploads", "box_capacity", "sample_capacity", "bound_calls", "device_bytes", "reach_calls")
+    # search_nodes: calls, status records read back (one per level), levels whose flags and points were downloaded (nnsdp_crown_info 8..10)
+    _INFO_NODES = ((8, "node_searches"), (9, "node_search_levels"), (10, "node_point_downloads"))
 
     def __init__(self, net: M.FeedFwdNet, normals=None, max_width: int = 64):
         self._h = None
@@ -702,9 +705,55 @@ class CrownBounder:
         return dict(status=("converged", "budget")[status], visited=visited, depth=depth, incumbent=inc, witnesses=wit, kernel_ms=ms.value,
                     lo=llo, hi=lhi, leaf_depth=ldepth, closed=lclosed, bound=lbound)
 
+    def search_nodes(self, lo, hi, hs, *, steps: int = 16, eta0: float = 0.5, decay: float = 0.9, corner_points: bool = True,
+                     max_nodes: int = 4096, max_depth: int = 64, chunk: int = 4096, confirm=None) -> dict:
+        """nnsdp_crown_search_nodes: the level loop of relusplit.verifyReluSplit on the root box lo / hi (xdims[0] each) for the clause
+        OR_i normal_i' f(x) <= hs[i] of the bounder's literals, with the node frontier kept on the GPU (csrc/crown_node_search.hpp).
+        confirm(x) -> bool decides whether a point that the device flagged is a witness (None: the first flagged point is).  Returns
+        the pieces of a ReluSplitResult: verdict, reason (None, "budget", "exhausted"), visited, depth, witness (or None), kernel_ms,
+        nleaves, and the closed leaves followed by the open nodes, in the Python loop's order, as arrays: assign (rows x acdim, int8),
+        leaf_depth, closed_by (0 infeasible, 1 bound, -1 open), bound."""
+        h, dp, ip = self._handle(), _lib.c_double_p, _lib.c_int32_p
+        lo = np.ascontiguousarray(lo, dtype=np.float64)
+        hi = np.ascontiguousarray(hi, dtype=np.float64)
+        if lo.shape != (self._n0,) or hi.shape != (self._n0,):
+            raise ValueError("lo / hi must have xdims[0] entries")
+        hs = np.ascontiguousarray(hs, dtype=np.float64)
+        if hs.ndim != 1 or hs.size < 1:
+            raise ValueError("hs must have one threshold per literal")
+        failed = []
+
+        def call(_user, x):
+            try:
+                return 1 if confirm(np.ctypeslib.as_array(x, shape=(self._n0,)).copy()) else 0
+            except BaseException as e:       # an exception cannot cross the C frames: the search ends at this level, it is raised again below
+                failed.append(e)
+                return 1
+
+        keep = _CONFIRM(call) if confirm is not None else None
+        cb = C.cast(keep, C.c_void_p) if keep is not None else None
+        out = (C.c_int32 * 6)()
+        wit, ms = np.zeros(self._n0), C.c_double(0.0)
+        _lib.check(self._lib.nnsdp_crown_search_nodes(h, lo.ctypes.data_as(dp), hi.ctypes.data_as(dp), hs.size, hs.ctypes.data_as(dp), int(steps),
+                                                      float(eta0), float(decay), int(bool(corner_points)), int(max_nodes), int(max_depth),
+                                                      int(chunk), cb, None, *[C.cast(C.byref(out, 4 * k), ip) for k in range(6)],
+                                                      wit.ctypes.data_as(dp), C.byref(ms)))
+        if failed:
+            raise failed[0]
+        verdict, reason, visited, depth, nleaves, nopen = (int(v) for v in out)
+        n = nleaves + nopen
+        assign = np.zeros((n, self._acdim), dtype=np.int8)
+        ldepth, lby = (np.zeros(n, dtype=np.int32) for _ in range(2))
+        lbound = np.zeros(n)
+        _lib.check(self._lib.nnsdp_crown_search_nodes_leaves(h, assign.ctypes.data_as(C.POINTER(C.c_int8)), ldepth.ctypes.data_as(ip),
+                                                             lby.ctypes.data_as(ip), lbound.ctypes.data_as(dp)))
+        return dict(verdict=("holds", "violated", "unknown")[verdict], reason=(None, "budget", "exhausted")[reason], visited=visited, depth=depth,
+                    witness=wit if verdict == 1 else None, kernel_ms=ms.value, nleaves=nleaves, assign=assign, leaf_depth=ldepth,
+                    closed_by=lby, bound=lbound)
+
     def info(self) -> dict:
         h, v, out = self._handle(), C.c_double(0.0), {}
-        for what, name in enumerate(self._INFO):
+        for what, name in tuple(enumerate(self._INFO)) + self._INFO_NODES:
             _lib.check(self._lib.nnsdp_crown_info(h, what, C.byref(v)))
             out[name] = int(v.value)
         return out

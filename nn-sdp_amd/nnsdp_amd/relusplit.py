@@ -3,9 +3,12 @@ clause  OR_i normal_i' f(x) <= h_i  on one input box by splitting a node into th
 the box, so the tree grows with the number of unstable neurons and not with 2^n0.  The bounds of a node come from
 CrownBounder.bound_nodes (crown_backend="resident", csrc/crown_relu_split.hpp) or makeIntervalsNodes (crown_backend="host", float32, no GPU):
 exact relaxations of the forced neurons, clipped pre-activation bounds, and per literal a few projected-gradient steps on the Lagrange
-multipliers of the forced signs.  The level loop is on the host.
+multipliers of the forced signs.  The level loop is on the host (frontier="host"), or, with crown_backend="resident" and
+frontier="device", on the bounder's stream (CrownBounder.search_nodes, csrc/crown_node_search.hpp): the assignments of a level stay in
+device memory, the host reads back five integers per level, the points only on a level where the device flagged a possible
+counterexample, and the leaves once at the end; the result is the host loop's on the resident bounder, bit for bit.
 
-Not here: a device-resident node frontier, bisecting the box of an exhausted node, SDPs on nodes, verifyAcasSpec, the wide bounder
+Not here: bisecting the box of an exhausted node, SDPs on nodes, verifyAcasSpec, the wide bounder
 (max_width 128) and Tanh networks."""
 import time
 from dataclasses import dataclass, field
@@ -27,6 +30,8 @@ class ReluSplitOptions:
     crown_backend: str = "host"    # "host": makeIntervalsNodes; "resident": one CrownBounder for the search
     workers: int = 16              # threads of the host routine
     corner_points: bool = True     # try the maximiser of every literal's linear bound besides the box centre
+    frontier: str = "host"         # "host": the level loop below; "device": CrownBounder.search_nodes (needs crown_backend "resident")
+    chunk: int = 4096              # frontier "device": nodes per launch of the node kernels; the result does not depend on it
 
 
 @dataclass
@@ -66,6 +71,12 @@ def _check(net, x1min, x1max, literals, split):
         raise ValueError("decay must be in (0, 1]")
     if split.max_nodes < 1 or split.max_depth < 0:
         raise ValueError("max_nodes must be >= 1 and max_depth >= 0")
+    if split.frontier not in ("host", "device"):
+        raise ValueError("frontier must be 'host' or 'device'")
+    if split.frontier == "device" and split.crown_backend != "resident":
+        raise ValueError("frontier 'device' needs crown_backend 'resident': the nodes live beside the resident bounder's network")
+    if int(split.chunk) < 1:
+        raise ValueError("chunk must be >= 1")
     lo, hi = np.asarray(x1min, dtype=np.float64), np.asarray(x1max, dtype=np.float64)
     if lo.shape != (net.xdims[0],) or hi.shape != lo.shape or not np.all(lo <= hi):
         raise ValueError("x1min / x1max must have xdims[0] entries with x1min <= x1max")
@@ -87,10 +98,26 @@ def verifyReluSplit(net: M.FeedFwdNet, x1min, x1max, literals, split: ReluSplitO
     seconds = dict(bound=0.0, points=0.0)
     bounder = F.CrownBounder(net, normals) if split.crown_backend == "resident" else None
     try:
+        if split.frontier == "device":
+            return _device_levels(net, lo, hi, normals, hs, split, bounder, t_start)
         return _levels(net, lo, hi, normals, hs, split, bounder, seconds, t_start)
     finally:
         if bounder is not None:
             bounder.close()
+
+
+def _device_levels(net, lo, hi, normals, hs, split, bounder, t_start):
+    """the level loop on the bounder's stream; a flagged point is confirmed in fp64 on the host, as in _levels"""
+    def confirm(x):
+        return bool(_violates_all(F.evalFeedFwdNet(net, x)[:, None], normals, hs)[0])
+
+    r = bounder.search_nodes(lo, hi, hs, steps=split.steps, eta0=split.eta0, decay=split.decay, corner_points=split.corner_points,
+                             max_nodes=split.max_nodes, max_depth=split.max_depth, chunk=split.chunk, confirm=confirm)
+    by = {0: "infeasible", 1: "bound", -1: None}
+    nodes = [ReluLeaf(r["assign"][k].copy(), int(r["leaf_depth"][k]), by[int(r["closed_by"][k])],
+                      float("nan") if r["closed_by"][k] == 0 else float(r["bound"][k])) for k in range(len(r["bound"]))]
+    seconds = dict(kernel=r["kernel_ms"] * 1e-3, total=time.perf_counter() - t_start)
+    return ReluSplitResult(r["verdict"], r["witness"], nodes[:r["nleaves"]], nodes[r["nleaves"]:], r["visited"], r["depth"], r["reason"], seconds)
 
 
 def _violates_all(Y, normals, hs):

@@ -1,6 +1,10 @@
 #!/usr/bin/env python3
 """Batched CROWN bounds: the GPU kernel against the host routine, and where one verifySplit spends its time.
-usage: python tools/split_timing.py [--nlit | --resident | --alpha | --frontier | --reach | --wide | --forest | --relu] [case ...]   cases: W10-D5 W40-D20 acas-shape   (default: all)
+usage: python tools/split_timing.py [--nlit | --resident | --alpha | --frontier | --reach | --wide | --forest | --relu | --relu-frontier] [case ...]   cases: W10-D5 W40-D20 acas-shape   (default: all)
+With --relu-frontier only the node-frontier leg runs (it takes no cases) and profiles/split_timing_relu_frontier.json is written:
+  search   the two whole-search instances of the --relu leg, verifyReluSplit with crown_backend "resident" and frontier "host" and then
+           "device" in this process: verdict, nodes visited, levels, milliseconds (median, min, max of 5 after 1 warm run), and for the
+           device frontier the HIP-event time of its kernels
 With --relu only the ReLU-split leg runs (cases W10-D5 and W40-D20 by default) and profiles/split_timing_relu.json is written:
   bound    CrownBounder.bound_nodes at 1, 256 and 4096 nodes with 0 and 16 multiplier steps beside CrownBounder.bound on the same boxes in
            the same process: HIP-event time of the launches (median, min, max of 7 after 2 warm calls) and the median wall-clock of the call
@@ -430,8 +434,47 @@ def relu_search_rows():
     return rows
 
 
+def relu_frontier_rows():
+    """the two whole-search instances of relu_search_rows, crown_backend "resident", with the host frontier against the device frontier
+    (CrownBounder.search_nodes) in one process; 5 runs each after 1 warm run, and the device frontier's HIP-event time"""
+    import literal_common as lc
+    rows = []
+    for xdims, seed, f, cap in (([16, 16, 16, 2], 7, 0.5, 16384), ([12, 16, 16, 2], 5, 0.2, 16384)):
+        net = lc.random_net(xdims, seed)
+        n0 = xdims[0]
+        lo, hi, nrm = -0.5 * np.ones(n0), 0.5 * np.ones(n0), np.array([1.0, -1.0])
+        X = np.concatenate([np.zeros((n0, 1)), lo[:, None] + np.random.default_rng(0).random((n0, 4096))], axis=1)
+        L = float((nrm @ na.evalFeedFwdNet(net, X)).max())
+        c0 = float(na.makeIntervalsBatch(net, lo[:, None], hi[:, None], backend="host", normals=nrm[None, :])[-1].smax[0, 0])
+        h = L + f * (c0 - L)
+        row = dict(xdims=xdims, seed=seed, L=L, c0=c0, h=h, max_nodes=cap)
+        for frontier in ("host", "device"):
+            ms, ker, res = [], [], None
+            for i in range(6):
+                t = time.perf_counter()
+                res = na.verifyReluSplit(net, lo, hi, [(nrm, h)], na.ReluSplitOptions(max_nodes=cap, crown_backend="resident", frontier=frontier))
+                if i >= 1:
+                    ms.append(1e3 * (time.perf_counter() - t)); ker.append(1e3 * res.seconds.get("kernel", 0.0))
+            row[frontier] = dict(verdict=res.verdict, visited=int(res.visited), levels=int(res.depth) + 1, ms_median=statistics.median(ms),
+                                 ms_min=min(ms), ms_max=max(ms))
+            if frontier == "device":
+                row[frontier].update(kernel_ms_median=statistics.median(ker), kernel_ms_min=min(ker), kernel_ms_max=max(ker))
+        assert (row["host"]["verdict"], row["host"]["visited"]) == (row["device"]["verdict"], row["device"]["visited"])
+        row["host_over_device"] = row["host"]["ms_median"] / row["device"]["ms_median"]
+        rows.append(row)
+        print(row, flush=True)
+    return rows
+
+
 if __name__ == "__main__":
     args = sys.argv[1:]
+    if "--relu-frontier" in args:
+        # the node-frontier leg: profiles/split_timing_relu_frontier.json
+        out_dir = os.environ.get("SPLIT_TIMING_OUT", os.path.join(ROOT, "profiles"))
+        os.makedirs(out_dir, exist_ok=True)
+        with open(os.path.join(out_dir, "split_timing_relu_frontier.json"), "w") as fh:
+            json.dump(dict(search=relu_frontier_rows()), fh, indent=1)
+        sys.exit(0)
     if "--relu" in args:
         # the ReLU-split leg: profiles/split_timing_relu.json; cases W10-D5 and W40-D20 unless named
         out_dir = os.environ.get("SPLIT_TIMING_OUT", os.path.join(ROOT, "profiles"))
